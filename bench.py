@@ -88,7 +88,17 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous check only: every rank joins the process group, rank 0 prints one JSON line "
                          "(n_gpus, ranks_seen_by_backend) and nothing touches a GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all (a fixed seeded row sample of a larger array): two builds run with the "
+                         "same arguments can be compared output for output.  Not available for --workload e2e yet: its timed "
+                         "epochs run inside chromegcn_amd.e2e.bench, which does not return their outputs")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "e2e":
+        ap.error("--dump-outputs: the e2e workload's timed epochs run inside chromegcn_amd.e2e and return no outputs to dump")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -392,6 +402,49 @@ def ranks_seen(world, dev):
     t = torch.ones(1, device=dev, dtype=torch.float32)
     dist.all_reduce(t)
     return int(round(float(t.item())))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor / number; None is skipped) as out_dir/<name>.npy -- float64
+    stays float64, everything else becomes float32.  Arrays that fit under an equal share of the 64 MB are written whole;
+    the others split what is left equally (equal shapes, equal shares, the same rows) and are replaced by a sample of their
+    rows (leading dimensions flattened), drawn without replacement by numpy's default_rng(0) and kept in row order, so that
+    equal arguments give the same sample.  Returns the record for the JSON line."""
+    tensors = {}
+    for name, v in arrays.items():
+        if v is None:
+            continue
+        t = torch.as_tensor(v, dtype=torch.float64) if isinstance(v, float) else torch.as_tensor(v).detach()
+        tensors[name] = t if t.dtype == torch.float64 else t.float()
+    nbytes = {k: t.numel() * t.element_size() for k, t in tensors.items()}
+    budget = DUMP_BUDGET_BYTES - 4096 * len(tensors)   # (4 KB per file for the .npy header)
+    whole, share = set(), budget
+    while len(whole) < len(tensors):
+        share = (budget - sum(nbytes[k] for k in whole)) // (len(tensors) - len(whole))
+        fits = {k for k in tensors if k not in whole and nbytes[k] <= share}
+        if not fits:
+            break
+        whole |= fits
+    os.makedirs(out_dir, exist_ok=True)
+    rec = {"dir": os.path.abspath(out_dir), "files": {},
+           "sample": "arrays over %d bytes: rows drawn by numpy.random.default_rng(0) without replacement, in row order" % share}
+    for name, t in tensors.items():
+        full = list(t.shape)
+        sampled = name not in whole
+        if sampled:
+            rows = t.reshape(-1, full[-1]) if t.dim() >= 2 else t.reshape(-1, 1)
+            if full[-1] * t.element_size() > share:
+                rows = t.reshape(-1, 1)
+            k = share // (rows.shape[1] * t.element_size())
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))
+            t = rows[torch.from_numpy(idx).to(rows.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        rec["files"][name] = {"shape": full, "saved_shape": list(a.shape), "dtype": str(a.dtype), "rows_sampled": sampled}
+    return rec
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -998,6 +1051,11 @@ def main():
         step()
     elapsed, per, last = timed(step, steps)
     final_loss = float(last[2]) if genome else float(last[0].item())   # (a deferred device loss is read here, after the timed region)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # now: the step's tensors are views of the stage's arena, which the extras overwrite
+        dumped = dump_outputs(args.dump_outputs,
+                              {"predictions": last[0], "targets": last[1], "total_loss": last[2]} if genome else
+                              {"loss": last[0], "probs": last[1], "dx": last[2]})
 
     extras = {}
     if not args.no_extras:
@@ -1313,6 +1371,8 @@ def main():
             out["probe"] = True
         if ladder_rec is not None:
             out["launch_ladder"] = ladder_rec
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         out.update(extras)
         print(json.dumps(out))
         sys.stdout.flush()

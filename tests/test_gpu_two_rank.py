@@ -20,6 +20,12 @@ D, NC = 128, 23
 SIZES = {"chr2": 900, "chr4": 610, "chr5": 1200, "chr6": 750, "chr7": 330}
 EPOCHS = 2
 GENOME = False   # set by the genome-scale test (module globals travel to the spawned children through the args)
+# Every rank is a process of its own with the GPU open, and so is the test process: world + 1 processes hold the device at
+# once.  The shared MI355X machines that run this suite's GPU tier stop a job once more than 6 processes hold the GPU (a
+# clean-checkout run of the 8-rank cases was stopped at 9), and the limit is visible to no process (environment, rlimits
+# and cgroup all say "unlimited").  So it is stated here: CGCN_TEST_MAX_GPU_PROCESSES (default 6; raise it on a dedicated
+# box to run the 8-rank cases), and a world that does not fit under it is skipped before any rank starts.
+MAX_GPU_PROCESSES = int(os.environ.get("CGCN_TEST_MAX_GPU_PROCESSES", "6"))
 
 
 def make_data(genome=False):
@@ -120,14 +126,22 @@ def free_port():
 
 
 @pytest.mark.timeout(1800)
-@pytest.mark.parametrize("world,genome", [(2, False), (2, True), (8, False), (8, True)],
+@pytest.mark.parametrize("world,genome", [(2, False), (2, True), (4, False), (4, True), (8, False), (8, True)],
                          ids=["2_ranks_five_small_chromosomes", "2_ranks_full_size_train_genome_configs2",
+                              "4_ranks_five_small_chromosomes_idle_ranks_last_group_not_full",
+                              "4_ranks_full_size_train_genome_four_step_groups",
                               "8_ranks_five_small_chromosomes_idle_ranks", "8_ranks_full_size_train_genome_two_step_groups"])
 def test_ranks_on_one_gpu_match_the_gradient_averaging_emulation(world, genome):
     """genome=True is BASELINE.json configs[2]'s code path at full size -- the 16 train chromosomes (242 908 windows,
     250 000 contact pairs each) sharded by plan_shards -- on ranks that share the one GPU a test box has (gloo: RCCL refuses
     two ranks per device).  world 8 is the driver's 8-GPU shape: two chromosomes per rank = exactly two step groups, seven
-    ranks' rows gathered; with five small chromosomes three ranks hold nothing at all (VERDICT r5 #2)."""
+    ranks' rows gathered; with five small chromosomes three ranks hold nothing at all.  world 4 (fits under
+    the process cap of the shared machines): the full genome as four full step groups with three ranks' rows gathered, and
+    five small chromosomes as a full step group, then one chromosome and three idle ranks.  The host logic of the world-8
+    shapes (three idle ranks in the one step group, rows sent to rank 0) also runs in tests/test_distributed_cpu.py."""
+    if world + 1 > MAX_GPU_PROCESSES:
+        pytest.skip("needs %d processes with the GPU open at once (%d ranks + this one); the cap is %d "
+                    "(CGCN_TEST_MAX_GPU_PROCESSES)" % (world + 1, world, MAX_GPU_PROCESSES))
     import torch.multiprocessing as mp
     epochs = 1 if genome else EPOCHS
     ctx = mp.get_context("spawn")
@@ -143,10 +157,10 @@ def test_ranks_on_one_gpu_match_the_gradient_averaging_emulation(world, genome):
     ref_sd, ref_tot, ref_preds, ref_ev, plan = emulate(world, genome, epochs)
     if genome:
         assert len(plan.rounds) == 16 // world and all(g is not None for r in plan.rounds for g in r)
-    elif world == 2:
-        assert len(plan.rounds) == 3 and all(any(g is None for g in r) is (i == 2) for i, r in enumerate(plan.rounds))
-    else:
-        assert len(plan.rounds) == 1 and sum(g is None for g in plan.rounds[0]) == world - 5
+    else:   # five chromosomes: full step groups, then the last one with the idle ranks (world 8: only that one)
+        n_rounds = -(-5 // world)
+        assert len(plan.rounds) == n_rounds and all(any(g is None for g in r) is (i == n_rounds - 1) for i, r in enumerate(plan.rounds))
+        assert sum(g is None for g in plan.rounds[-1]) == n_rounds * world - 5
     results.sort(key=lambda r: r[0])
     for rank, sd, tot, preds, preds_dev, ev, rng in results:
         # dropout RNG state: the seed is untouched by the statistics sync, the step counter advanced once per step group
