@@ -151,3 +151,42 @@ def test_backward_split_not_less_accurate_than_chain(lib, n):
         # (measured +14 % rms at 1.6e-7 ... 2.6e-7 of max |dW|; the second-stage sum over the workgroups is common to both)
         assert err["split"][k + "_rms"] <= (1.3 if k == "dW" else 1.0) * err["fp32_chain"][k + "_rms"], (k, err)
         assert err["split"][k] <= 2 * err["fp32_chain"][k] + 2e-8, (k, err)
+
+
+@pytest.mark.parametrize("C", [103, 240])
+@pytest.mark.parametrize("n", [333, 5776, 36865])
+def test_head_split_not_less_accurate_than_chain(lib, n, C):
+    """The three products of the training head at d = 128 (cgcn_head_train: k_head_fused_sp / k_head_fused_rs), both forms,
+    against float64: pred = ym W_out^T (read through probs), dym = Pt W_out (from the workspace) and dW_out += Pt^T Yt
+    (finished by cgcn_layer_bwd in head mode).  Accumulator layouts of the split form: pred three accumulators (SpAcc), dym two
+    (SpAcc2), dW_out ONE 32 x 32 accumulator that takes all six partial products (as the ring's dW)."""
+    from test_gpu_head import fused_step, head_params, ref_head_train
+    S, d = 2, 128
+    g = torch.Generator().manual_seed(n + C)
+    x = torch.randn(S, n, d, generator=g) * 1.3 + 0.2
+    tgt = (torch.rand(n, C, generator=g) < 0.2).float()
+    prm = head_params(d, C, n + C)
+    ref = None
+    out, err = {}, {}
+    for form, mode in FORMS.items():
+        lib.cgcn_debug_set_products(mode)
+        o = fused_step(lib, x.to(DEV), prm, tgt.to(DEV), want_dx=False)
+        if ref is None:
+            ref = ref_head_train(o["xn"].cpu(), prm, tgt)
+        out[form] = {k: o[k].cpu() for k in ("probs", "dym", "dW_out")}
+        err[form] = {}
+        for k in ("probs", "dym", "dW_out"):
+            err[form][k] = _rel(out[form][k], ref[k])
+            err[form][k + "_rms"] = _rms(out[form][k], ref[k])
+    print("head n=%d C=%d" % (n, C))
+    for k in ("probs", "dym", "dW_out"):
+        print("  %-6s  split rms %.3g max %.3g   chain rms %.3g max %.3g" % (k, err["split"][k + "_rms"], err["split"][k],
+                                                                         err["fp32_chain"][k + "_rms"], err["fp32_chain"][k]))
+    assert not torch.equal(out["split"]["dym"], out["fp32_chain"]["dym"]), "the two forms differ in the last bits"
+    for k in ("probs", "dym", "dW_out"):
+        assert err["split"][k] < 1e-5 and err["fp32_chain"][k] < 1e-5, (k, err)
+    # measured (n = 333 ... 36 865, C = 103 / 240): split / chain rms 0.6-0.7 for probs, 0.3-0.5 for dym, 0.93-1.01 for dW_out;
+    # every max error below 7e-7 of max |ref|
+    assert err["split"]["probs_rms"] <= err["fp32_chain"]["probs_rms"], err
+    assert err["split"]["dym_rms"] <= err["fp32_chain"]["dym_rms"], err
+    assert err["split"]["dW_out_rms"] <= 1.3 * err["fp32_chain"]["dW_out_rms"], err
