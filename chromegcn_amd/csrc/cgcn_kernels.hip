@@ -2881,6 +2881,71 @@ __global__ __launch_bounds__(256) void k_sgd(int count, float* __restrict__ p, c
 }
 
 // ------------------------------------------------------------------------------------------
+// k_adam: torch.optim.Adam semantics (_single_tensor_adam; amsgrad = maximize = False) on four flat buffers
+// (utils/util_methods.py:14-16 builds Adam(betas=(0.9, 0.98), lr)):
+//   g = grad_scale grad + wd p;  t = step + 1;  m += (1 - b1)(g - m);  v = b2 v + (1 - b2) g g;
+//   p -= (lr / bc1) (m / (sqrt(v) / bc2s + eps)),  bc1 = 1 - b1^t, bc2s = sqrt(1 - b2^t) in double, cast once to fp32.
+// An element with m == 0 is left as it is (0 / 0 when eps == 0 and v == 0 would make it NaN): the arenas' padding stays 0.
+// Also advances the dropout step counter: this is the last kernel of a train step.
+//
+// The step counter lives on the device (one float per parameter, torch's 0-d `state[p]["step"]` of fused / capturable
+// Adam): every workgroup reads step[0], and all n_step entries go up by one exactly once per launch.  Incrementing in
+// place would race with a workgroup that has not read step[0] yet, so the LAST workgroup to finish writes the new
+// counts: each workgroup waits for its own load of step[0] to return before it draws a ticket (one relaxed agent-scope
+// fetch_add on a caller-owned int32), and the one that draws gridDim.x - 1 writes the steps and puts the ticket back to 0.
+// Nothing is published to another workgroup inside the launch -- the new counts are read by the NEXT launch -- so no
+// release / acquire fence is needed (an agent-scope fence costs microseconds per launch, MI355X_MICROARCH "fences").
+// Chosen over a one-thread increment launch in front of this one: that costs a dependent kernel boundary (~1.5 us) per
+// step, the ticket one atomic per workgroup.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_adam(int count, float* __restrict__ p, const float* __restrict__ g,
+                                              float* __restrict__ m, float* __restrict__ v, float* __restrict__ step,
+                                              int n_step, int* __restrict__ ticket, float lr, float beta1, float beta2,
+                                              float eps, float wd, float grad_scale, unsigned long long* __restrict__ rng_state) {
+  __shared__ int last;
+  const float t = step[0] + 1.f;                      // torch: step_t += 1 (fp32), then the bias corrections from it
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)t));
+  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)t));
+  const float step_size = lr / bc1;
+  const float ob1 = 1.f - beta1, ob2 = 1.f - beta2;
+  auto one = [&](float& pi, float gi, float& mi, float& vi) {
+    const float d = gi * grad_scale + wd * pi;
+    mi = mi + ob1 * (d - mi);                         // exp_avg.lerp_(d, 1 - beta1)
+    vi = beta2 * vi + ob2 * d * d;                    // exp_avg_sq.mul_(beta2).addcmul_(d, d, 1 - beta2)
+    const float denom = sqrtf(vi) / bc2s + eps;
+    if (mi != 0.f) pi = pi - step_size * (mi / denom);   // param.addcdiv_(exp_avg, denom, -step_size)
+  };
+  const int n4 = count >> 2;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    one(pv.x, gv.x, mv.x, vv.x);
+    one(pv.y, gv.y, mv.y, vv.y);
+    one(pv.z, gv.z, mv.z, vv.z);
+    one(pv.w, gv.w, mv.w, vv.w);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {   // tail of a count that is not a multiple of 4
+    const int i = (n4 << 2) + threadIdx.x;
+    one(p[i], g[i], m[i], v[i]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && rng_state) rng_state[1] += 1ull;
+  // the ticket: this workgroup's load of step[0] has returned (every wave waits for its loads) before lane 0 draws
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0)
+    last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!last) return;
+  for (int i = threadIdx.x; i < n_step; i += blockDim.x) step[i] = t;
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
 
@@ -3510,6 +3575,24 @@ int cgcn_sgd_step(cgcn_stream_t stream, long long count, float* param, const flo
   const int blocks = count > 0 ? (int)((count + 255) / 256) : 1;
   hipLaunchKernelGGL(k_sgd, dim3(blocks), dim3(256), 0, st, (int)count, param, grad, momentum != 0.f ? momentum_buf : nullptr,
                      lr, momentum, weight_decay, nesterov, grad_scale, rng_state);
+  return launch_status();
+}
+
+int cgcn_adam_step(cgcn_stream_t stream, long long count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                   float* step, int n_step, int32_t* ticket, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, float grad_scale, unsigned long long* rng_state) {
+  if (count < 0 || n_step < 1) return CGCN_ERR_BAD_ARG;
+  if (count > 2147483647LL) return CGCN_ERR_UNSUPPORTED;
+  if (!step || !ticket) return CGCN_ERR_BAD_ARG;
+  if (count > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)) return CGCN_ERR_BAD_ARG;
+  if (misaligned16(param) || misaligned16(grad) || misaligned16(exp_avg) || misaligned16(exp_avg_sq)) return CGCN_ERR_BAD_ARG;
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f)) return CGCN_ERR_BAD_ARG;
+  const long long n4 = count / 4;
+  long long blocks = (n4 + 255) / 256;
+  if (blocks < 1) blocks = 1;
+  if (blocks > 1024) blocks = 1024;   // grid-stride beyond: 4 workgroups per CU of the MI355X
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (int)count, param, grad, exp_avg,
+                     exp_avg_sq, step, n_step, (int*)ticket, lr, beta1, beta2, eps, weight_decay, grad_scale, rng_state);
   return launch_status();
 }
 

@@ -145,7 +145,9 @@ class GCNStage:
     """Device-resident state + step engine of the GCN stage for one split-independent model.
 
     model      : ChromeGCN-like module with forward_strands(x_fr [2,n,d], graph) -> (logits [2,n,C], gates)
-    optimizer  : torch optimizer over model.parameters() (utils/util_methods.py:14-19 builds SGD/Adam)
+    optimizer  : torch optimizer over model.parameters() (utils/util_methods.py:14-19 builds SGD/Adam).  Plain SGD and
+                 Adam(fused=True) / Adam(capturable=True) step in one launch of ours over the flat arenas, inside the
+                 captured graphs (_fused_kind); any other optimizer's step() runs eagerly after a captured fwd+bwd
     hip_graphs : capture each chromosome's step into a HIP graph (needs a GPU)
     input_grad : also produce d loss / d features.  finetune.py:33-34 sets requires_grad on the features, but the
                  resulting x.grad is unobservable there (the tensors are loop-local and finetune returns only
@@ -225,7 +227,13 @@ class GCNStage:
         self._flat_grad: Optional[torch.Tensor] = None
         self._flat_param: Optional[torch.Tensor] = None
         self._flat_mom: Optional[torch.Tensor] = None
-        self._fused_sgd = False
+        # Adam's state as flat arenas (exp_avg, exp_avg_sq), one device step count per parameter, and the ticket word of
+        # cgcn_adam_step; torch's optimizer.state holds views into them
+        self._flat_m: Optional[torch.Tensor] = None
+        self._flat_v: Optional[torch.Tensor] = None
+        self._flat_step: Optional[torch.Tensor] = None
+        self._ticket: Optional[torch.Tensor] = None
+        self._fused: Optional[str] = None   # "sgd" / "adam": the optimizer step is one launch of ours (capturable); None: step()
         self._captured_lr = None
         self._one: Optional[torch.Tensor] = None
         self._targets_cpu: Dict[tuple, torch.Tensor] = {}
@@ -394,13 +402,83 @@ class GCNStage:
     def _params(self):
         return [p for p in self.model.parameters() if p.requires_grad]
 
-    def _fused_sgd_eligible(self, ps):
+    def _fused_kind(self, ps):
+        """which optimizer step of ours replaces optimizer.step(): "sgd" (plain torch SGD), "adam" (torch Adam the caller
+        asked to step on the device: fused=True or capturable=True), or None (step() eagerly)"""
         o = self.optimizer
-        if o is None or type(o) is not torch.optim.SGD or len(o.param_groups) != 1 or self.device.type != "cuda":
-            return False
+        if o is None or type(o) not in (torch.optim.SGD, torch.optim.Adam) or len(o.param_groups) != 1 or self.device.type != "cuda":
+            return None
         g = o.param_groups[0]
-        same = len(g["params"]) == len(ps) and all(a is b for a, b in zip(g["params"], ps))
-        return bool(same and g.get("dampening", 0) == 0 and not g.get("maximize", False))
+        if not (len(g["params"]) == len(ps) and all(a is b for a, b in zip(g["params"], ps))):
+            return None
+        if type(o) is torch.optim.SGD:
+            return "sgd" if g.get("dampening", 0) == 0 and not g.get("maximize", False) else None
+        return "adam" if self._adam_eligible(g, ps) else None
+
+    def _adam_eligible(self, g, ps) -> bool:
+        """torch.optim.Adam as cgcn_adam_step computes it: fused / capturable (the caller asked for a device-side step,
+        whose rounding already differs from foreach's -- a plain Adam keeps torch's own step bit for bit), no amsgrad /
+        maximize / differentiable / decoupled decay, plain-number hyperparameters, and either no state yet or one step
+        count shared by every parameter (the kernel keeps ONE count for all of them)"""
+        if not (g.get("fused") or g.get("capturable")):
+            return False
+        if g.get("amsgrad") or g.get("maximize") or g.get("differentiable") or g.get("decoupled_weight_decay", False):
+            return False
+        if any(torch.is_tensor(x) for x in (g["lr"], g["eps"], g["weight_decay"], *g["betas"])):
+            return False
+        if self._adam_adopted(ps):
+            return True
+        sts = [self.optimizer.state.get(p) for p in ps]
+        if not any(sts):
+            return True
+        for p, st in zip(ps, sts):
+            if not st or set(st) != {"step", "exp_avg", "exp_avg_sq"}:
+                return False
+            if not all(torch.is_tensor(st[k]) and st[k].shape == p.shape for k in ("exp_avg", "exp_avg_sq")):
+                return False
+        steps = torch.stack([torch.as_tensor(st["step"]).detach().to("cpu", torch.float64).reshape(()) for st in sts])
+        return bool((steps == steps[0]).all())   # one host read, only when state is adopted (not per step)
+
+    def _adam_adopted(self, ps) -> bool:
+        """is every parameter's Adam state still the views _adopt_adam_state made?  (optimizer.load_state_dict
+        replaces them: the next step adopts the new tensors)"""
+        if self._flat_step is None or self._flat_step.numel() != len(ps):
+            return False
+        offs, total = self._offsets(ps)
+        if self._flat_m.numel() != total:
+            return False
+        bs, bm, bv = self._flat_step.data_ptr(), self._flat_m.data_ptr(), self._flat_v.data_ptr()
+        for i, (p, off) in enumerate(zip(ps, offs)):
+            st = self.optimizer.state.get(p)
+            if not st:
+                return False
+            s, m, v = st.get("step"), st.get("exp_avg"), st.get("exp_avg_sq")
+            if not (torch.is_tensor(s) and torch.is_tensor(m) and torch.is_tensor(v)):
+                return False
+            if s.data_ptr() != bs + 4 * i or m.data_ptr() != bm + 4 * off or v.data_ptr() != bv + 4 * off:
+                return False
+        return True
+
+    def _adopt_adam_state(self, ps, offs, total, dev):
+        """exp_avg / exp_avg_sq of every parameter become views into two flat arenas and its step a 0-d view into one
+        float32 device array -- the tensors torch's own fused Adam keeps (state_dict() / load_state_dict() see torch's
+        layout); existing values are copied in, missing state starts at zero (= torch's state before its first step)"""
+        self._flat_m = torch.zeros(total, device=dev, dtype=torch.float32)
+        self._flat_v = torch.zeros(total, device=dev, dtype=torch.float32)
+        self._flat_step = torch.zeros(len(ps), device=dev, dtype=torch.float32)
+        if self._ticket is None or self._ticket.device != dev:
+            self._ticket = torch.zeros(1, device=dev, dtype=torch.int32)
+        for i, (p, off) in enumerate(zip(ps, offs)):
+            st = self.optimizer.state[p]
+            m = self._flat_m[off:off + p.numel()].view(p.shape)
+            v = self._flat_v[off:off + p.numel()].view(p.shape)
+            if "step" in st:
+                self._flat_step[i].copy_(torch.as_tensor(st["step"]).reshape(()))
+            if torch.is_tensor(st.get("exp_avg")):
+                m.copy_(st["exp_avg"])
+            if torch.is_tensor(st.get("exp_avg_sq")):
+                v.copy_(st["exp_avg_sq"])
+            st["step"], st["exp_avg"], st["exp_avg_sq"] = self._flat_step[i], m, v   # torch's key order for new state
 
     @staticmethod
     def _offsets(ps):
@@ -423,14 +501,15 @@ class GCNStage:
         return True
 
     def _ensure_flat_grad(self):
-        """Make every parameter, its .grad and (plain SGD) its momentum buffer a view into one flat fp32
-        buffer each: one all-reduce for the gradients, one launch for the optimizer step, and gradient
-        'sinks' the backward kernels write into directly (no per-parameter autograd accumulate kernels)."""
+        """Make every parameter, its .grad and (plain SGD) its momentum buffer / (fused Adam) its moments and step count
+        a view into one flat fp32 buffer each: one all-reduce for the gradients, one launch for the optimizer step, and
+        gradient 'sinks' the backward kernels write into directly (no per-parameter autograd accumulate kernels)."""
         ps = self._params()
         offs, total = self._offsets(ps)
         dev = ps[0].device
         ok = self._views_ok(ps, self._flat_param, "data") and self._views_ok(ps, self._flat_grad, "grad")
-        if ok and self._fused_sgd == self._fused_sgd_eligible(ps):
+        kind = self._fused_kind(ps)
+        if ok and self._fused == kind and (kind != "adam" or self._adam_adopted(ps)):
             return
         with torch.no_grad():
             flat_p = torch.zeros(total, device=dev, dtype=torch.float32)
@@ -441,9 +520,12 @@ class GCNStage:
             self._flat_grad = self._alloc_flat_grad(total, dev)
             for p, off in zip(ps, offs):
                 p.grad = self._flat_grad[off:off + p.numel()].view(p.shape)
-            self._fused_sgd = self._fused_sgd_eligible(ps)
+            self._fused = kind
             self._flat_mom = None
-            if self._fused_sgd and self.optimizer.param_groups[0].get("momentum", 0) != 0:
+            self._flat_m = self._flat_v = self._flat_step = None
+            if kind == "adam":
+                self._adopt_adam_state(ps, offs, total, dev)
+            if kind == "sgd" and self.optimizer.param_groups[0].get("momentum", 0) != 0:
                 self._flat_mom = torch.zeros(total, device=dev, dtype=torch.float32)
                 for p, off in zip(ps, offs):
                     st = self.optimizer.state[p]
@@ -457,15 +539,20 @@ class GCNStage:
         self._drop_graphs()
 
     def _optimizer_step(self, grad_scale: float = 1.0):
-        """finetune.py:49.  Plain torch SGD runs as one fused launch over the flat buffers (which also
-        advances the dropout counter and applies the 1/k of a k-rank step group); anything else goes
+        """finetune.py:49.  Plain torch SGD and fused / capturable torch Adam run as one launch over the flat buffers
+        (which also advances the dropout counter and applies the 1/k of a k-rank step group); anything else goes
         through optimizer.step()."""
         rng = self.model._rng_state if getattr(self.model, "_rng_managed", False) else None
-        if self._fused_sgd:
+        if self._fused == "sgd":
             from . import ops
             g = self.optimizer.param_groups[0]
             ops.sgd_step(self._flat_param, self._flat_grad, self._flat_mom, g["lr"], g.get("momentum", 0),
                          g.get("weight_decay", 0), g.get("nesterov", False), rng, grad_scale)
+        elif self._fused == "adam":
+            from . import ops
+            g = self.optimizer.param_groups[0]
+            ops.adam_step(self._flat_param, self._flat_grad, self._flat_m, self._flat_v, self._flat_step, self._ticket,
+                          g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], rng, grad_scale)
         else:
             if grad_scale != 1.0:
                 self._flat_grad.mul_(grad_scale)
@@ -497,7 +584,7 @@ class GCNStage:
         d loss / d features, its partial-sum launch -- carries it in extra workgroups) instead of being a launch of
         its own."""
         from . import ops
-        fuse = self._fused_sgd and getattr(self.model, "_grad_sink", False) and getattr(self.model, "n_layers", 0) >= 1
+        fuse = self._fused == "sgd" and getattr(self.model, "_grad_sink", False) and getattr(self.model, "n_layers", 0) >= 1
         if fuse:
             g = self.optimizer.param_groups[0]
             ops._sgd_fuse = {"param": self._flat_param, "grad": self._flat_grad, "mom": self._flat_mom, "lr": g["lr"],
@@ -558,7 +645,8 @@ class GCNStage:
     def _lr_signature(self):
         if self.optimizer is None:
             return None
-        return tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("nesterov")) for g in self.optimizer.param_groups)
+        return tuple((g.get("lr"), g.get("momentum"), g.get("weight_decay"), g.get("nesterov"),
+                      tuple(g["betas"]) if "betas" in g else None, g.get("eps")) for g in self.optimizer.param_groups)
 
     def _capture(self, c: Optional[_Chrom], kind: str, group_size: int = 1):
         """kind: 'train' (zero_grad+fwd+bwd+step), 'fwdbwd' (no optimizer step: multi-rank), 'eval', 'group' (multi-rank:
@@ -590,10 +678,10 @@ class GCNStage:
                 return out
             return self._fwd_bwd(c)
 
-        if kind in ("train", "epoch") and not self._fused_sgd:
+        if kind in ("train", "epoch") and not self._fused:
             # torch optimizers are not capturable by default (Adam.step raises under capture): callers replay
             # 'fwdbwd' and step eagerly instead (train_step)
-            raise RuntimeError("only the fused SGD step can be captured; use kind='fwdbwd' + an eager optimizer.step()")
+            raise RuntimeError("only the fused SGD / Adam step can be captured; use kind='fwdbwd' + an eager optimizer.step()")
         try:
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
@@ -637,7 +725,7 @@ class GCNStage:
         return ent["loss"], ent["probs"], ent["dx"]
 
     def _replay_epoch(self, names, train: bool) -> bool:
-        """The chromosomes `names` of a split as ONE captured graph (single rank; training needs the fused SGD): one graph
+        """The chromosomes `names` of a split as ONE captured graph (single rank; training needs the fused step): one graph
         launch instead of one per chromosome -- the launches' gaps were 3 % of the genome epoch
         (profiles/r04_epoch_graph_experiment.txt).  False = not applicable, the caller steps chromosome by chromosome."""
         if not (self.epoch_graph and self.hip_graphs and len(names) > 1):
@@ -645,7 +733,7 @@ class GCNStage:
         if train:
             self.model.train()
             self._ensure_flat_grad()
-            if not self._fused_sgd:
+            if not self._fused:
                 return False
         else:
             self.model.eval()
@@ -693,9 +781,9 @@ class GCNStage:
         self._ensure_arena()
         if self.multi:
             raise RuntimeError("use train_group() when running on more than one rank")
-        if self._fused_sgd:                          # zero_grad + fwd + bwd + fused SGD: one HIP graph (or the same, eagerly)
+        if self._fused:                              # zero_grad + fwd + bwd + fused SGD / Adam: one HIP graph (or the same, eagerly)
             return self._replay(c, "train") if self.hip_graphs else self._fwd_bwd_step(c)
-        # any other optimizer (Adam is the reference's -optim adam, utils/util_methods.py:20-21): its step() is
+        # any other optimizer (a plain Adam is the reference's -optim adam, utils/util_methods.py:20-21): its step() is
         # not capturable, so the graph ends after the backward and the step runs eagerly on the flat buffers
         loss, probs, dx = self._replay(c, "fwdbwd") if self.hip_graphs else self._fwd_bwd(c)
         self._optimizer_step()
@@ -726,7 +814,7 @@ class GCNStage:
         """Multi-rank step group: every rank runs fwd+bwd on its own chromosome (or none), gradients are
         summed across ranks in ONE all-reduce of the flat buffer and divided by the number of chromosomes
         in the group, then every rank takes the same optimizer step.
-        With a stream-ordered collective backend (nccl = RCCL) and the fused SGD the WHOLE group step -- forward,
+        With a stream-ordered collective backend (nccl = RCCL) and the fused SGD / Adam the WHOLE group step -- forward,
         backward, all-reduce, 1/k scaling + optimizer step -- is one HIP graph per (chromosome, group size): nothing
         is launched from the host between the last backward kernel and the collective, or between the collective and
         the step.  Otherwise: captured fwd+bwd, then the collective and ONE fused scale+step launch, stream-ordered."""
@@ -756,7 +844,7 @@ class GCNStage:
         return out
 
     def _group_graph_enabled(self) -> bool:
-        if not (self.multi and self.hip_graphs and self._fused_sgd and self._group_graph_opt and self._group_graph_ok):
+        if not (self.multi and self.hip_graphs and self._fused and self._group_graph_opt and self._group_graph_ok):
             return False
         return torch.distributed.get_backend(self.group) == "nccl"
 

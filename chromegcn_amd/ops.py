@@ -542,3 +542,15 @@ def sgd_step(flat_param, flat_grad, flat_mom, lr, momentum, weight_decay, nester
     _lib.check(lib.cgcn_sgd_step(_lib.stream_ptr(), flat_param.numel(), flat_param.data_ptr(), flat_grad.data_ptr(),
                                  _lib.ptr(flat_mom), float(lr), float(momentum), float(weight_decay),
                                  1 if nesterov else 0, float(grad_scale), _lib.ptr(rng_state)), "cgcn_sgd_step")
+
+
+def adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq, step, ticket, lr, beta1, beta2, eps, weight_decay,
+              rng_state=None, grad_scale=1.0):
+    """torch.optim.Adam step on flat buffers in one launch (cgcn_adam_step): `step` is a float32 device tensor of
+    per-parameter counts (all advanced by one), `ticket` an int32 device word that stays 0 between launches; also
+    advances the dropout counter."""
+    lib = _lib.load()
+    _lib.check(lib.cgcn_adam_step(_lib.stream_ptr(), flat_param.numel(), flat_param.data_ptr(), flat_grad.data_ptr(),
+                                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(), step.numel(),
+                                  ticket.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
+                                  float(weight_decay), float(grad_scale), _lib.ptr(rng_state)), "cgcn_adam_step")

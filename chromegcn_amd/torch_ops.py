@@ -7,6 +7,7 @@
     torch.ops.chromegcn.head_loss_backward
     torch.ops.chromegcn.head_logits           eval-mode relu/BatchNorm/Linear per strand   models/ChromeModels.py:48-51 (model.eval())
     torch.ops.chromegcn.sgd_step              SGD(momentum, weight decay) in place     utils/util_methods.py:14-19
+    torch.ops.chromegcn.adam_step_            Adam (L2 weight decay) in place          utils/util_methods.py:14-16
 
 Pure-tensor signatures (the graph is passed as its CSR tensors), fake/meta implementations, and `register_autograd`
 formulas whose backward is itself made of registered ops, so `torch.library.opcheck`, FakeTensor tracing and
@@ -356,4 +357,30 @@ def sgd_step(param: Tensor, grad: Tensor, momentum_buf: Optional[Tensor], lr: fl
 
 @sgd_step.register_fake
 def _(param, grad, momentum_buf, lr, momentum, weight_decay, nesterov, grad_scale, rng_state):
+    return None
+
+
+@torch.library.custom_op("chromegcn::adam_step_", mutates_args=("param", "exp_avg", "exp_avg_sq", "step", "ticket", "rng_state"),
+                         device_types="cuda")
+def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step: Tensor, ticket: Tensor, lr: float,
+               beta1: float, beta2: float, eps: float, weight_decay: float, grad_scale: float,
+               rng_state: Optional[Tensor]) -> None:
+    """torch.optim.Adam semantics on flat fp32 buffers in one launch: d = grad_scale g + wd p; t = step + 1;
+    m += (1 - b1)(d - m); v = b2 v + (1 - b2) d^2; p -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+    step: float32 per-parameter counts, all advanced by one; ticket: int32 [1], 0 between launches;
+    rng_state (optional): the dropout step counter, advanced by one."""
+    n = param.numel()
+    if not all(t.is_contiguous() and t.numel() == n for t in (grad, exp_avg, exp_avg_sq)) or not param.is_contiguous():
+        raise RuntimeError("chromegcn::adam_step_: param, grad, exp_avg and exp_avg_sq must be contiguous and of equal size")
+    if step.dtype != torch.float32 or not step.is_contiguous() or ticket.dtype != torch.int32 or ticket.numel() < 1:
+        raise RuntimeError("chromegcn::adam_step_: step must be contiguous float32, ticket int32 with one element")
+    lib = _lib.load()
+    _lib.check(lib.cgcn_adam_step(_lib.stream_ptr(), n, param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
+                                  exp_avg_sq.data_ptr(), step.data_ptr(), step.numel(), ticket.data_ptr(), float(lr),
+                                  float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale),
+                                  _P(rng_state)), "cgcn_adam_step")
+
+
+@adam_step_.register_fake
+def _(param, grad, exp_avg, exp_avg_sq, step, ticket, lr, beta1, beta2, eps, weight_decay, grad_scale, rng_state):
     return None

@@ -33,6 +33,9 @@ def parse(argv=None):
     ap.add_argument("-gcn_dropout", type=float, default=0.2)         # config_args.py:24
     ap.add_argument("-gate", action="store_true")                    # accepted, ignored (ChromeModels.py:22-31)
     ap.add_argument("-optim", type=str, default="sgd", choices=["adam", "sgd"])
+    ap.add_argument("-fused_adam", action="store_true",
+                    help="-optim adam: build Adam(fused=True), whose step runs as one HIP launch inside the captured graphs "
+                         "(off: torch's default Adam, stepped eagerly after each captured forward + backward)")
     ap.add_argument("-lr", type=float, default=0.25)
     ap.add_argument("-lr_decay2", type=float, default=0)
     ap.add_argument("-epochs", type=int, default=100)
@@ -88,7 +91,7 @@ def main(argv=None):
             model.batch_norm.weight.copy_(pick("model.batch_norm.weight")); model.batch_norm.bias.copy_(pick("model.batch_norm.bias"))
     model.to(dev)
     if opt.optim == "adam":                                                          # utils/util_methods.py:14-19
-        optimizer = torch.optim.Adam(model.parameters(), betas=(0.9, 0.98), lr=opt.lr)
+        optimizer = torch.optim.Adam(model.parameters(), betas=(0.9, 0.98), lr=opt.lr, fused=bool(opt.fused_adam) or None)
     else:
         optimizer = torch.optim.SGD(model.parameters(), lr=opt.lr, weight_decay=1e-6, momentum=0.9)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=100, gamma=0.5)  # main.py:86

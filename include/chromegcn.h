@@ -32,7 +32,7 @@
  *   - Dropout (F.dropout of models/ChromeModels.py:42,50) is counter based: a mask bit is a pure
  *     function of rng_state = {seed, step counter} (uint64[2] in DEVICE memory), a stream id and
  *     the element index, so the backward regenerates the forward's mask.  Every kernel of one
- *     train step must see the same counter; cgcn_sgd_step (the last kernel of a step) advances it.
+ *     train step must see the same counter; cgcn_sgd_step or cgcn_adam_step (the last kernel of a step) advances it.
  */
 #ifndef CHROMEGCN_H
 #define CHROMEGCN_H
@@ -50,7 +50,7 @@ extern "C" {
 #define CGCN_ERR_LAUNCH (-3)      /* hipGetLastError() != hipSuccess after a launch      */
 #define CGCN_ERR_WORKSPACE (-4)   /* workspace too small (see cgcn_*_workspace_bytes)    */
 
-#define CGCN_ABI_VERSION 25
+#define CGCN_ABI_VERSION 26
 
 typedef void *cgcn_stream_t; /* hipStream_t */
 
@@ -485,6 +485,32 @@ int cgcn_multilabel_metrics_nonneg(cgcn_stream_t stream, long long n, int C, con
 int cgcn_sgd_step(cgcn_stream_t stream, long long count, float *param, const float *grad, float *momentum_buf,
                   float lr, float momentum, float weight_decay, int nesterov, float grad_scale,
                   unsigned long long *rng_state);
+
+/*
+ * torch.optim.Adam step on flat fp32 buffers (utils/util_methods.py:14-16 builds Adam(betas=(0.9, 0.98), lr), the
+ * reference's default optimizer; amsgrad = maximize = False, L2 weight decay as torch.optim.Adam, not AdamW):
+ *     g = grad_scale * grad + weight_decay * param;  t = step + 1;
+ *     exp_avg += (1 - beta1) * (g - exp_avg);  exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g * g;
+ *     param -= (lr / bc1) * exp_avg / (sqrt(exp_avg_sq) / bc2s + eps)
+ * with bc1 = 1 - beta1^t, bc2s = sqrt(1 - beta2^t) computed in double and rounded once to fp32.  ABI 26.
+ * beta1 / beta2 are the fp32 values given: 1 - beta is formed from them (1 - 0.9f is 2.4e-7 off 0.1, torch rounds 0.1).
+ * exp_avg / exp_avg_sq zero-initialised with step 0 reproduce torch's first step.  An element whose exp_avg is 0 keeps
+ * its value (padding between parameters stays 0 even with eps == 0).
+ * step: device float[n_step], one count per parameter (torch keeps a 0-d float32 device tensor per parameter for
+ *     fused / capturable Adam); the launch reads step[0] and adds 1 to every entry exactly once.
+ * ticket: device int32[1], zero before the first launch and left at 0 by every launch (the last workgroup to finish
+ *     writes the new step counts and resets it).  One launch at a time per ticket: launches that share one must be
+ *     ordered (same stream, or events).
+ * param, grad, exp_avg, exp_avg_sq: 16-byte aligned, count elements each (count need not be a multiple of 4).
+ * grad_scale: 1, or 1/k when grad holds the all-reduced SUM of k ranks' gradients (multi-GPU step group).
+ * rng_state (may be NULL): its step counter is advanced by one -- this is the last kernel of a train step.
+ * Rejected on the host, nothing launched: CGCN_ERR_BAD_ARG for count < 0, n_step < 1, a NULL step / ticket, a NULL
+ * buffer when count > 0, a misaligned buffer, beta1 or beta2 outside [0, 1), eps < 0 (or NaN);
+ * CGCN_ERR_UNSUPPORTED for count >= 2^31.
+ */
+int cgcn_adam_step(cgcn_stream_t stream, long long count, float *param, const float *grad, float *exp_avg,
+                   float *exp_avg_sq, float *step, int n_step, int32_t *ticket, float lr, float beta1, float beta2,
+                   float eps, float weight_decay, float grad_scale, unsigned long long *rng_state);
 
 #ifdef __cplusplus
 }
