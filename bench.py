@@ -22,6 +22,13 @@ per epoch instead of 16: the documented semantics change of data-parallel chromo
         bench.py --gpus N --steps K --warmup W
     python bench.py --workload chr21|chr1|config1     # one chromosome per rank (weak scaling), secondary lines
     python bench.py --workload e2e                    # config 5: Expecto-shaped encoder -> hand-off -> GCN stage
+    python bench.py --full                            # + roofline, CPU baseline and the secondary measurements
+
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line (`roofline`, `cpu_baseline` null).  --full adds everything else the benchmark
+measures -- the live roofline of every kernel, the oracle on the host cores, the extras (the same epoch with a deferred
+loss sync, returning CPU predictions, on the other generators and adjacency types, in the fp32 chain form, inference,
+metrics, saliency, the engine's defaults) -- each behind its own --no-* switch as before.
 """
 import argparse
 import json
@@ -61,10 +68,13 @@ def parse():
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--no-hip-graph", action="store_true")
     ap.add_argument("--no-epoch-graph", action="store_true", help="A/B: one HIP graph launch per chromosome instead of one per epoch (single rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (profiling runs)")
-    ap.add_argument("--no-roofline", action="store_true", help="tuning runs only: skip the isolated layer-forward timing (roofline = null)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the host baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, CPU baseline and the secondary measurements "
+                         "(off: set up, warm up, time the steps, dump, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (profiling runs)")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the isolated kernel timing (roofline = null)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: budget of the host baseline sample")
     ap.add_argument("--backend", default=os.environ.get("CGCN_DIST_BACKEND", "nccl"),
                     help="torch.distributed backend (nccl = RCCL; gloo only for single-GPU functional tests)")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
@@ -98,6 +108,8 @@ def parse():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload == "e2e":
         ap.error("--dump-outputs: the e2e workload's timed epochs run inside chromegcn_amd.e2e and return no outputs to dump")
+    if not args.full:   # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extras = args.no_roofline = True
     return args
 
 
@@ -1366,6 +1378,7 @@ def main():
                         "note": "per-step host time on rank 0" + (" (each epoch ends with its own loss sync)" if genome else " (launch only: steps are asynchronous)")},
             "value_at_median": windows / (float(np.median(per_ms)) * 1e-3) if genome else None,
             "roofline": roof, "roofline_top3": top3 if roof else None, "cpu_baseline": cpu, "final_loss": final_loss,
+            "full": bool(args.full),
         }
         if args.probe:
             out["probe"] = True

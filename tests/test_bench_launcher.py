@@ -76,6 +76,24 @@ def test_single_rank_dry_run_needs_no_launcher():
     assert json.loads(lines[0])["n_gpus"] == 1
 
 
+def test_plain_run_measures_the_headline_alone(monkeypatch):
+    """a plain run sets up, warms up, times the steps and prints the line; roofline, CPU baseline and the secondary
+    measurements run with --full only, where each keeps its own --no-* switch"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("cgcn_bench_cli", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(argv))
+        a = bench.parse()
+        return a.full, a.no_extras, a.no_roofline, a.no_cpu_baseline
+    assert parsed("--gpus", "1", "--steps", "3", "--warmup", "1") == (False, True, True, True)
+    assert parsed("--full") == (True, False, False, False)
+    assert parsed("--full", "--no-cpu-baseline") == (True, False, False, True)
+    assert parsed("--full", "--no-extras", "--no-roofline") == (True, True, True, False)
+
+
 def test_launcher_mismatch_is_an_error_not_an_assert():
     # under a launcher environment that disagrees with --gpus: refused with a message and a non-zero exit code
     rc, lines, err = _run(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

@@ -1,5 +1,6 @@
-"""Copy the summaries of a tools/final_profiles.sh run from gpurun_out/ into profiles/ (tracked) and rebuild
-profiles/traffic.json:  python tools/collect_profiles.py <tag> [<old tag to remove>]"""
+"""Copy the summaries of a tools/final_profiles.sh run from its output folder ($CGCN_PROFILE_OUT, default profile_out/ in
+the repository root) into profiles/ (tracked) and rebuild profiles/traffic.json:
+    python tools/collect_profiles.py <tag> [<old tag to remove>]"""
 import glob
 import json
 import os
@@ -7,6 +8,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("CGCN_PROFILE_OUT") or os.path.join(ROOT, "profile_out")
 
 
 def main():
@@ -20,20 +22,20 @@ def main():
             if f.endswith(".csv") or (f.endswith(".json") and "_bench_line_" in f):
                 os.remove(f)
     traffic = {}
-    for d in sorted(glob.glob(os.path.join(ROOT, "gpurun_out", tag + "_*", "summary"))):
+    for d in sorted(glob.glob(os.path.join(OUT, tag + "_*", "summary"))):
         for f in glob.glob(os.path.join(d, "*")):
             name = os.path.basename(f)
             if name.startswith("traffic_"):
                 traffic.update(json.load(open(f)))
             else:
                 shutil.copy(f, os.path.join(prof, name))
-    for f in glob.glob(os.path.join(ROOT, "gpurun_out", tag, "bench_*.json")):
+    for f in glob.glob(os.path.join(OUT, tag, "bench_*.json")):
         lines = [l for l in open(f).read().splitlines() if l.startswith("{")]
         if lines:
             wl = os.path.basename(f)[len("bench_"):-len(".json")]
             open(os.path.join(prof, "%s_bench_line_%s.json" % (tag, wl)), "w").write(lines[-1] + "\n")
     for extra in ("saliency_kernel_stats.csv", "pytest.log"):
-        src = os.path.join(ROOT, "gpurun_out", tag, extra)
+        src = os.path.join(OUT, tag, extra)
         if os.path.exists(src):
             shutil.copy(src, os.path.join(prof, "%s_%s" % (tag, "pytest_gpu.log" if extra == "pytest.log" else extra)))
     if "chr21_d256L4_d256" in traffic:   # bench.py keys its lookup by workload (+ generator) + width
@@ -44,7 +46,7 @@ def main():
         out["_note"] = note
     # the library sources these counters were measured on: bench.py reports a stored value only for the same sources
     # (recorded on the GPU box from the very snapshot that was profiled: tools/final_profiles.sh; an argument overrides it)
-    hfile = os.path.join(ROOT, "gpurun_out", tag, "src_hash.txt")
+    hfile = os.path.join(OUT, tag, "src_hash.txt")
     if len(sys.argv) > 3:
         out["_src_hash"] = sys.argv[3]
     elif os.path.exists(hfile):

@@ -3,7 +3,7 @@
 tag=$1; shift
 R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/ks_$tag
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$tag -- python3 $R/bench.py --no-cpu-baseline --no-extras "$@" > /tmp/ks_$tag.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$tag -- python3 $R/bench.py --full --no-cpu-baseline --no-extras "$@" > /tmp/ks_$tag.log 2>&1
 f=$(find /tmp/ks_$tag -name "*kernel_stats.csv" | head -1)
 [ -z "$f" ] && { tail -5 /tmp/ks_$tag.log; exit 1; }
 python3 - "$f" <<'PY'

@@ -5,13 +5,13 @@
 #        tools/profile_round.sh r02 chr1_hic --workload chr1 --hic-like
 # One kernel-trace/stats pass and four separate --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ_*, MFMA/LDS + L2 hit/miss), never
 # combined with sys/hip/hsa traces.  The program after `--` is python3 itself (no wrapper hop); the library must
-# already be built (chromegcn_amd._lib never compiles).  Raw output: gpurun_out/<tag>_<wl>/ ; summaries:
-# gpurun_out/<tag>_<wl>/summary/ (copy those to profiles/).
+# already be built (chromegcn_amd._lib never compiles).  Raw output: $CGCN_PROFILE_OUT/<tag>_<wl>/ (default
+# profile_out/ in the repository root); summaries: <that folder>/summary/ (tools/collect_profiles.py copies those to profiles/).
 set -u
 TAG=${1:-r02}; WL=${2:-genome}; shift 2 || true
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-O=$R/gpurun_out/${TAG}_${WL}
-mkdir -p "$O"
+O=${CGCN_PROFILE_OUT:-$R/profile_out}/${TAG}_${WL}
+mkdir -p "$O" && O=$(cd "$O" && pwd)   # (absolute: the steps below run from /tmp)
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --no-cpu-baseline --no-extras $*"
 # the PMC passes skip the isolated roofline launches too (they would be averaged into the per-kernel counters)

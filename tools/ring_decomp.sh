@@ -5,7 +5,7 @@
 for v in base rowonly matonly nowait base; do
   if [ $v = base ]; then unset CHROMEGCN_LIB; else export CHROMEGCN_LIB=$GRAFT_REPO_ROOT/variants/libcgcn_$v.so; fi
   for wl in chr1 genome; do
-    python bench.py --no-cpu-baseline --no-extras --steps 10 --workload $wl 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-extras --steps 10 --workload $wl 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['roofline']['all_kernels_us']
 print('$v $wl', {x:k[x] for x in k if 'ring' in x}, round(d['ms_per_step'],4))"
