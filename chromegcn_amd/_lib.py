@@ -6,7 +6,7 @@ library binds to; streams and device pointers are then interchangeable."""
 import ctypes
 import os
 
-import torch  # noqa: F401  (must precede CDLL: shares torch's HIP runtime)
+import torch  # must precede CDLL: shares torch's HIP runtime
 
 from . import _build
 
@@ -16,42 +16,67 @@ _c_sz = ctypes.c_size_t
 _c_float = ctypes.c_float
 _c_uint = ctypes.c_uint
 
-_SIGNATURES = {
-    # name: (restype, argtypes)
-    "cgcn_abi_version": (_c_int, []),
-    "cgcn_strerror": (ctypes.c_char_p, [_c_int]),
-    "cgcn_spmm": (_c_int, [_c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
-    "cgcn_layer_fwd": (_c_int, [_c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 13 + [_c_float, _c_vp, _c_uint, _c_vp, _c_vp, _c_int, _c_vp]),
-    "cgcn_layer_fwd_colstats_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_vp]),
-    "cgcn_debug_set_fwd_split_bytes": (None, [ctypes.c_longlong]),
-    "cgcn_debug_set_products": (None, [ctypes.c_int]),
-    "cgcn_debug_get_products": (ctypes.c_int, []),
-    "cgcn_debug_layer_fwd_route": (_c_int, [_c_int, _c_int, _c_int, _c_vp, _c_int]),
-    "cgcn_debug_layer_bwd_route": (_c_int, [_c_int, _c_int, _c_int]),
-    "cgcn_layer_bwd_workspace_bytes": (_c_sz, [_c_int, _c_int, _c_int]),
-    "cgcn_layer_bwd": (_c_int, [_c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 18 + [_c_int, _c_float, _c_vp, _c_uint, _c_vp, _c_vp, _c_sz, _c_vp, _c_vp, _c_vp]),
-    "cgcn_debug_layer_bwd_phases": (_c_int, [_c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 18 + [_c_int, _c_float, _c_vp, _c_uint, _c_vp, _c_vp, _c_sz, _c_int, _c_vp]),
-    "cgcn_head_workspace_bytes": (_c_sz, [_c_int] * 4),
-    "cgcn_head_workspace_layout": (_c_int, [_c_int] * 4 + [ctypes.POINTER(_c_sz)] * 3),
-    "cgcn_head_bwd_partials": (_c_int, [_c_int]),
-    "cgcn_head_fwd": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 6 + [_c_float, _c_float, _c_int] + [_c_vp] * 3
-                      + [_c_float] + [_c_vp] * 7 + [_c_sz]),
-    "cgcn_head_logits": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 5 + [_c_float] + [_c_vp] * 3),
-    "cgcn_head_train": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 6 + [_c_float, _c_float] + [_c_vp] * 3 + [_c_float]
-                        + [_c_vp] * 6 + [_c_int, _c_int, _c_vp, _c_sz]),
-    "cgcn_debug_head_train_phases": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 6 + [_c_float, _c_float] + [_c_vp] * 3 + [_c_float]
-                                     + [_c_vp] * 6 + [_c_int, _c_int, _c_vp, _c_sz, _c_int]),
-    "cgcn_head_bwd": (_c_int, [_c_vp] + [_c_int] * 4 + [_c_vp] * 8 + [_c_float] + [_c_vp] * 6 + [_c_int, _c_vp, _c_sz]),
-    "cgcn_sddmm": (_c_int, [_c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 5 + [_c_int]),
-    "cgcn_saliency_normalize": (_c_int, [_c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
-    "cgcn_graph_count": (_c_int, [_c_vp, _c_int, _c_int] + [_c_vp] * 5),
-    "cgcn_graph_fill": (_c_int, [_c_vp, _c_int, _c_int] + [_c_vp] * 8),
-    "cgcn_metrics_workspace_bytes": (_c_sz, [ctypes.c_longlong, _c_int]),
-    "cgcn_multilabel_metrics": (_c_int, [_c_vp, ctypes.c_longlong, _c_int, _c_vp, _c_vp, _c_float, _c_vp, _c_vp, _c_sz]),
-    "cgcn_multilabel_metrics_nonneg": (_c_int, [_c_vp, ctypes.c_longlong, _c_int, _c_vp, _c_vp, _c_float, _c_vp, _c_vp, _c_vp, _c_sz]),
-    "cgcn_sgd_step": (_c_int, [_c_vp, ctypes.c_longlong, _c_vp, _c_vp, _c_vp, _c_float, _c_float, _c_float, _c_int, _c_float, _c_vp]),
-    "cgcn_adam_step": (_c_int, [_c_vp, ctypes.c_longlong] + [_c_vp] * 5 + [_c_int, _c_vp] + [_c_float] * 6 + [_c_vp]),
+# Every function of include/chromegcn.h: (return type, its parameters in header order, by their header names).  A bare
+# name is a pointer (c_void_p); "name:t" has the type t of _TYPES ("zp": the size_t * results of
+# cgcn_head_workspace_layout).  tests/test_lib_table.py checks this table against the header.
+_TYPES = {"i": _c_int, "u": _c_uint, "ll": ctypes.c_longlong, "z": _c_sz, "f": _c_float, "zp": ctypes.POINTER(_c_sz)}
+_HEADER = {
+    "cgcn_abi_version": (_c_int, ""),
+    "cgcn_strerror": (ctypes.c_char_p, "code:i"),
+    "cgcn_spmm": (_c_int, "stream n_rows:i n_cols:i S:i d:i rowptr col val row_scale X Y aux"),
+    "cgcn_layer_fwd": (_c_int, "stream n:i S:i d:i rowptr col val row_scale X W b wg cg Xn Z H gate dropout_p:f rng_state "
+                               "stream_id:u H_in colstats colstats_rows:i aux"),
+    "cgcn_layer_fwd_colstats_plan": (_c_int, "n:i S:i d:i mode:i rows_per_tile"),
+    "cgcn_debug_set_fwd_split_bytes": (None, "bytes:ll"),
+    "cgcn_debug_set_products": (None, "mode:i"),
+    "cgcn_debug_get_products": (_c_int, ""),
+    "cgcn_debug_layer_fwd_route": (_c_int, "n:i S:i d:i aux colstats_rows:i"),
+    "cgcn_debug_layer_bwd_route": (_c_int, "n:i S:i d:i"),
+    "cgcn_layer_bwd_workspace_bytes": (_c_sz, "n:i S:i d:i"),
+    "cgcn_layer_bwd": (_c_int, "stream n:i S:i d:i rowptr_t col_t val_t row_scale X Z H gate W wg dXn dgate dX dHs dW db dwg "
+                               "dcg accumulate:i in_dropout_p:f rng_state in_stream_id:u head workspace workspace_bytes:z "
+                               "aux_stream sgd aux_t"),
+    "cgcn_debug_layer_bwd_phases": (_c_int, "stream n:i S:i d:i rowptr_t col_t val_t row_scale X Z H gate W wg dXn dgate dX dHs "
+                                            "dW db dwg dcg accumulate:i in_dropout_p:f rng_state in_stream_id:u head workspace "
+                                            "workspace_bytes:z phases:i aux_t"),
+    "cgcn_head_workspace_bytes": (_c_sz, "n:i S:i d:i C:i"),
+    "cgcn_head_workspace_layout": (_c_int, "n:i S:i d:i C:i dym_offset:zp bnc_offset:zp part_offset:zp"),
+    "cgcn_head_bwd_partials": (_c_int, "n:i"),
+    "cgcn_head_fwd": (_c_int, "stream n:i S:i d:i C:i X bn_w bn_b run_mean run_var num_batches_tracked momentum:f eps:f "
+                              "training:i W_out b_out target dropout_p:f rng_state probs loss dpred save_mean save_invstd "
+                              "workspace workspace_bytes:z"),
+    "cgcn_head_logits": (_c_int, "stream n:i S:i d:i C:i X bn_w bn_b run_mean run_var eps:f W_out b_out logits"),
+    "cgcn_head_train": (_c_int, "stream n:i S:i d:i C:i X bn_w bn_b run_mean run_var num_batches_tracked momentum:f eps:f "
+                                "W_out b_out target dropout_p:f rng_state probs loss save_mean save_invstd col_stats "
+                                "col_stats_tiles:i col_stats_rows:i workspace workspace_bytes:z"),
+    "cgcn_debug_head_train_phases": (_c_int, "stream n:i S:i d:i C:i X bn_w bn_b run_mean run_var num_batches_tracked "
+                                             "momentum:f eps:f W_out b_out target dropout_p:f rng_state probs loss save_mean "
+                                             "save_invstd col_stats col_stats_tiles:i col_stats_rows:i workspace "
+                                             "workspace_bytes:z phases:i"),
+    "cgcn_head_bwd": (_c_int, "stream n:i S:i d:i C:i X bn_w bn_b save_mean save_invstd W_out dpred dloss dropout_p:f "
+                              "rng_state dX dW_out db_out dbn_w dbn_b accumulate:i workspace workspace_bytes:z"),
+    "cgcn_sddmm": (_c_int, "stream n:i S:i d:i rowptr col A B out accumulate:i"),
+    "cgcn_saliency_normalize": (_c_int, "stream n:i rowptr val raw out"),
+    "cgcn_graph_count": (_c_int, "stream n:i adj_type:i rowptr_in col_in val_in row_counts rowptr_out"),
+    "cgcn_graph_fill": (_c_int, "stream n:i adj_type:i rowptr_in col_in val_in rowptr_out col_out val_out row_scale "
+                                "symmetric_flag"),
+    "cgcn_metrics_workspace_bytes": (_c_sz, "n:ll C:i"),
+    "cgcn_multilabel_metrics": (_c_int, "stream n:ll C:i probs targets fdr_cutoff:f out workspace workspace_bytes:z"),
+    "cgcn_multilabel_metrics_nonneg": (_c_int, "stream n:ll C:i probs targets fdr_cutoff:f out bad workspace "
+                                               "workspace_bytes:z"),
+    "cgcn_sgd_step": (_c_int, "stream count:ll param grad momentum_buf lr:f momentum:f weight_decay:f nesterov:i "
+                              "grad_scale:f rng_state"),
+    "cgcn_adam_step": (_c_int, "stream count:ll param grad exp_avg exp_avg_sq step n_step:i ticket lr:f beta1:f beta2:f "
+                               "eps:f weight_decay:f grad_scale:f rng_state"),
 }
+_ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
+        for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))
+_SIGNATURES = {fn: (res, [t for _, t in params]) for fn, (res, params) in _ABI.items()}   # name: (restype, argtypes)
+# what query() needs per function, worked out once: the parameter names in order, the positions of the pointers and
+# whether it takes a stream
+_PLANS = {fn: (tuple(p for p, _ in params), tuple(i for i, (_, t) in enumerate(params) if t in (_c_vp, _TYPES["zp"])),
+               any(p == "stream" for p, _ in params))
+          for fn, (_, params) in _ABI.items()}
 ABI_VERSION = 26
 COLSTATS_RECORDS, COLSTATS_ACCUMULATE = 0, 1   # include/chromegcn.h: CGCN_COLSTATS_*
 COLSTATS_ROWS_ACCUMULATE, COLSTATS_ROWS_ZERO_ONLY, COLSTATS_ROWS_ACCUMULATE_ZEROED = -1, -2, -3   # CGCN_COLSTATS_ROWS_*
@@ -109,6 +134,51 @@ def check(rc, what):
     if rc != 0:
         msg = load().cgcn_strerror(rc).decode()
         raise RuntimeError("chromegcn_amd: %s failed: %s (code %d)" % (what, msg, rc))
+
+
+def query(fn, **args):
+    """Call the entry point `fn` with every parameter given by its header name; returns what it returns.  A pointer
+    parameter takes a tensor (its data pointer), None (NULL), an int (an address), or a ctypes Structure or out-parameter
+    (passed by reference).  `stream` defaults to torch's current stream."""
+    names, pointers, has_stream = _PLANS[fn]
+    if has_stream and "stream" not in args:
+        args["stream"] = stream_ptr()
+    try:
+        vals = list(map(args.__getitem__, names))
+    except KeyError as e:
+        raise TypeError("%s: missing argument %s" % (fn, e.args[0])) from None
+    if len(args) != len(names):
+        raise TypeError("%s: unknown argument(s) %s" % (fn, ", ".join(sorted(set(args) - set(names)))))
+    for i in pointers:   # the eager path makes ~8 of these calls per chromosome step: plain tensors take the short way
+        v = vals[i]
+        if v.__class__ is torch.Tensor:
+            vals[i] = v.data_ptr()
+        elif v is not None and v.__class__ is not int:
+            vals[i] = v.data_ptr() if isinstance(v, torch.Tensor) else ctypes.byref(v)
+    return getattr(load(), fn)(*vals)   # `args` keeps every tensor and struct alive until the call has returned
+
+
+def call(fn, **args):
+    """query() for an entry point that returns a status: raises unless it is CGCN_OK"""
+    check(query(fn, **args), fn)
+
+
+def _workspace(nbytes, device, what):
+    if nbytes == 0:
+        raise RuntimeError("chromegcn_amd: %s: unsupported shape" % what)
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
+def head_workspace(n, S, d, C, device):
+    """the uint8 workspace of cgcn_head_fwd / cgcn_head_train / cgcn_head_bwd"""
+    return _workspace(query("cgcn_head_workspace_bytes", n=n, S=S, d=d, C=C), device,
+                      "fused head, S=%d n=%d d=%d C=%d" % (S, n, d, C))
+
+
+def layer_bwd_workspace(n, S, d, device):
+    """the uint8 workspace of cgcn_layer_bwd"""
+    return _workspace(query("cgcn_layer_bwd_workspace_bytes", n=n, S=S, d=d), device,
+                      "layer backward, S=%d n=%d d=%d" % (S, n, d))
 
 
 class HeadGrad(ctypes.Structure):

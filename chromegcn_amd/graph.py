@@ -375,20 +375,18 @@ def normalize_graph_device(adj_type: str, hic: Optional[sp.spmatrix], n: int, de
         ci = torch.from_numpy(a.indices.astype(np.int32)).to(dev)
         if not np.all(a.data == 1.0):
             va = torch.from_numpy(a.data.astype(np.float32)).to(dev)
-    lib = _lib.load()
     with torch.cuda.device(dev):
         counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
-        _lib.check(lib.cgcn_graph_count(_lib.stream_ptr(), n, code, _lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va),
-                                        counts.data_ptr(), rowptr.data_ptr()), "cgcn_graph_count")
+        _lib.call("cgcn_graph_count", n=n, adj_type=code, rowptr_in=rp, col_in=ci, val_in=va, row_counts=counts,
+                  rowptr_out=rowptr)
         nnz = int(rowptr[n].item())  # the one host sync of the build (sizes col[])
         col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
         val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)[:nnz] if adj_type == "both" else None
         rs = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n]
         flag = torch.ones(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.cgcn_graph_fill(_lib.stream_ptr(), n, code, _lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va),
-                                       rowptr.data_ptr(), col.data_ptr(), _lib.ptr(val), rs.data_ptr(), flag.data_ptr()),
-                   "cgcn_graph_fill")
+        _lib.call("cgcn_graph_fill", n=n, adj_type=code, rowptr_in=rp, col_in=ci, val_in=va, rowptr_out=rowptr, col_out=col,
+                  val_out=val, row_scale=rs, symmetric_flag=flag)
         symmetric = bool(flag.item())
     if val is not None and bool((val == 1).all().item()):
         val = None  # a 'both' graph whose entries are all ones can use the implicit-value kernels
@@ -545,20 +543,18 @@ def _graph_from_coo_device(adj: torch.Tensor, dev) -> ChromGraph:
     ar = torch.arange(n + 1, device=dev, dtype=row.dtype)
     rowptr = torch.searchsorted(row.contiguous(), ar).to(torch.int32)
     col = colx.to(torch.int32).contiguous()
-    lib = _lib.load()
     with torch.cuda.device(dev):
         if n > 0 and nnz > 0:
             counts = torch.empty(n, dtype=torch.int32, device=dev)
             rowptr2 = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            _lib.check(lib.cgcn_graph_count(_lib.stream_ptr(), n, ADJ_CODES["hic"], rowptr.data_ptr(), col.data_ptr(), None,
-                                            counts.data_ptr(), rowptr2.data_ptr()), "cgcn_graph_count")
+            _lib.call("cgcn_graph_count", n=n, adj_type=ADJ_CODES["hic"], rowptr_in=rowptr, col_in=col, val_in=None,
+                      row_counts=counts, rowptr_out=rowptr2)
             if bool(torch.equal(rowptr2, rowptr)):   # binarise(pattern + I) == pattern: the diagonal is already there
                 col2 = torch.empty(nnz, dtype=torch.int32, device=dev)
                 rs = torch.empty(n, dtype=torch.float32, device=dev)
                 flag = torch.ones(1, dtype=torch.int32, device=dev)
-                _lib.check(lib.cgcn_graph_fill(_lib.stream_ptr(), n, ADJ_CODES["hic"], rowptr.data_ptr(), col.data_ptr(), None,
-                                               rowptr2.data_ptr(), col2.data_ptr(), None, rs.data_ptr(), flag.data_ptr()),
-                           "cgcn_graph_fill")
+                _lib.call("cgcn_graph_fill", n=n, adj_type=ADJ_CODES["hic"], rowptr_in=rowptr, col_in=col, val_in=None,
+                          rowptr_out=rowptr2, col_out=col2, val_out=None, row_scale=rs, symmetric_flag=flag)
                 if bool(flag.item()) and bool(torch.equal(v, rs[row])):
                     return ChromGraph(n=n, nnz=nnz, rowptr=rowptr, col=col, val=None, row_scale=rs, rowptr_t=rowptr, col_t=col,
                                       val_t=None, symmetric=True, host=None)

@@ -23,19 +23,17 @@ def _metrics_raw(probs: torch.Tensor, targets: torch.Tensor, fdr_cutoff: float, 
     n, C = probs.shape
     if tuple(targets.shape) != (n, C):
         raise RuntimeError("probs and targets must both be [n, C]")
-    lib = _lib.load()
-    ws_bytes = lib.cgcn_metrics_workspace_bytes(n, C)
+    ws_bytes = _lib.query("cgcn_metrics_workspace_bytes", n=n, C=C)
     if ws_bytes == 0:
         raise RuntimeError("chromegcn_amd.metrics: unsupported size n=%d C=%d" % (n, C))
     ws = torch.empty(ws_bytes, device=probs.device, dtype=torch.uint8)
     out = torch.empty(4 * C + 1, device=probs.device, dtype=torch.float32)
+    args = dict(n=n, C=C, probs=probs, targets=targets, fdr_cutoff=float(fdr_cutoff), out=out, workspace=ws,
+                workspace_bytes=ws_bytes)
     if nonneg:
-        _lib.check(lib.cgcn_multilabel_metrics_nonneg(_lib.stream_ptr(), n, C, probs.data_ptr(), targets.data_ptr(), float(fdr_cutoff),
-                                                      out.data_ptr(), out.data_ptr() + 16 * C, ws.data_ptr(), ws_bytes),
-                   "cgcn_multilabel_metrics_nonneg")
+        _lib.call("cgcn_multilabel_metrics_nonneg", bad=out.data_ptr() + 16 * C, **args)
     else:
-        _lib.check(lib.cgcn_multilabel_metrics(_lib.stream_ptr(), n, C, probs.data_ptr(), targets.data_ptr(), float(fdr_cutoff),
-                                               out.data_ptr(), ws.data_ptr(), ws_bytes), "cgcn_multilabel_metrics")
+        _lib.call("cgcn_multilabel_metrics", **args)
     return out
 
 

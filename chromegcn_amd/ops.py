@@ -30,6 +30,16 @@ def _dense(t: torch.Tensor) -> torch.Tensor:
     return t.clone() if t.data_ptr() % 16 else t
 
 
+def _check_rng(rng_state, dropout: bool):
+    if dropout and rng_state is None:
+        raise RuntimeError("chromegcn_amd: fused dropout needs the model's rng_state tensor")
+
+
+def _check_momentum(momentum):
+    if momentum is None:
+        raise RuntimeError("chromegcn_amd: BatchNorm momentum=None (cumulative average) is not supported by the fused head")
+
+
 def _check_feat(x: torch.Tensor, g: ChromGraph, name="x", any_width=False):
     _require_cuda(x, name)
     ok_d = (x.dim() == 3 and x.shape[2] % 4 == 0 and 4 <= x.shape[2] <= 4096) if any_width else (x.dim() == 3 and x.shape[2] in SUPPORTED_D)
@@ -62,9 +72,7 @@ def sddmm(a, b, graph: ChromGraph, transposed=False, out=None):
             raise RuntimeError("chromegcn_amd: sddmm accumulates into a contiguous fp32 [nnz] tensor on the features' device")
     else:
         out = torch.empty(col.shape[0], device=a.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.cgcn_sddmm(_lib.stream_ptr(), n, S, d, rowptr.data_ptr(), col.data_ptr(), a.data_ptr(), b.data_ptr(),
-                              out.data_ptr(), 1 if acc else 0), "cgcn_sddmm")
+    _lib.call("cgcn_sddmm", n=n, S=S, d=d, rowptr=rowptr, col=col, A=a, B=b, out=out, accumulate=1 if acc else 0)
     return out
 
 
@@ -74,9 +82,7 @@ def saliency_normalize(raw, graph: ChromGraph):
     _require_cuda(raw, "raw")
     raw = raw.contiguous()
     out = torch.empty_like(raw)
-    lib = _lib.load()
-    _lib.check(lib.cgcn_saliency_normalize(_lib.stream_ptr(), graph.n, graph.rowptr.data_ptr(), _lib.ptr(graph.val), raw.data_ptr(),
-                                           out.data_ptr()), "cgcn_saliency_normalize")
+    _lib.call("cgcn_saliency_normalize", n=graph.n, rowptr=graph.rowptr, val=graph.val, raw=raw, out=out)
     return out
 
 
@@ -93,19 +99,99 @@ _saliency_tap = None  # set by chromegcn_amd.saliency while it collects per-laye
 _sgd_fuse = None
 
 
-def _sgd_fuse_arg(layer_id, dx, sink):
-    """ctypes reference to a cgcn_sgd_fuse for this cgcn_layer_bwd call, or None (plus the struct to keep alive)"""
+def _sgd_fuse_arg(layer_id, sink):
+    """the cgcn_sgd_fuse for this cgcn_layer_bwd call (of a layer whose gradients go into `sink`), or None"""
     rq = _sgd_fuse
-    if rq is None or rq.get("done") or layer_id != 1 or sink is None or _lib.aux_stream_ptr() is not None:
-        return None, None
+    if rq is None or rq.get("done") or layer_id != 1 or sink is None:
+        return None
     fg = rq["grad"]
     lo, hi = fg.data_ptr(), fg.data_ptr() + 4 * fg.numel()
     if not all(lo <= t.data_ptr() and t.data_ptr() + 4 * t.numel() <= hi for t in sink):
-        return None, None
-    sg = _lib.SgdFuse(rq["param"].data_ptr(), fg.data_ptr(), _lib.ptr(rq["mom"]), fg.numel(), float(rq["lr"]),
-                      float(rq["momentum"]), float(rq["weight_decay"]), float(rq["grad_scale"]), 1 if rq["nesterov"] else 0,
-                      _lib.ptr(rq["rng_state"]))
-    return ctypes.byref(sg), sg
+        return None
+    return _lib.SgdFuse(rq["param"].data_ptr(), fg.data_ptr(), _lib.ptr(rq["mom"]), fg.numel(), float(rq["lr"]),
+                        float(rq["momentum"]), float(rq["weight_decay"]), float(rq["grad_scale"]), 1 if rq["nesterov"] else 0,
+                        _lib.ptr(rq["rng_state"]))
+
+
+# The one call site of each launch, shared with torch_ops.py.  Inputs arrive dense (_dense, _layer_params, _head_params);
+# csr / csr_t: (rowptr, col, val, row_scale) of the graph and (rowptr_t, col_t, val_t, row_scale) of its transpose.
+def _layer_params(weight, bias, gate_w, gate_b):
+    return _dense(weight), bias.contiguous(), gate_w.contiguous().view(-1), gate_b.contiguous().view(-1)
+
+
+def _head_params(bn_w, bn_b, w_out, b_out):
+    return _dense(bn_w), _dense(bn_b), _dense(w_out), b_out.contiguous()
+
+
+def layer_fwd(x, params, csr, z, h, dropout_p=0.0, rng_state=None, layer_id=0, h_in=None, colstats=None, colstats_rows=0):
+    """cgcn_layer_fwd -> (X', gate); z / h: the Z and H buffers to fill, or None"""
+    S, n, d = x.shape
+    weight, bias, wg, cg = params
+    rowptr, col, val, row_scale = csr
+    xn, gate = torch.empty_like(x), torch.empty((S, n), device=x.device, dtype=torch.float32)
+    _lib.call("cgcn_layer_fwd", n=n, S=S, d=d, rowptr=rowptr, col=col, val=val, row_scale=row_scale, X=x, W=weight, b=bias,
+              wg=wg, cg=cg, Xn=xn, Z=z, H=h, gate=gate, dropout_p=float(dropout_p),
+              rng_state=rng_state if dropout_p > 0 else None, stream_id=int(layer_id), H_in=h_in, colstats=colstats,
+              colstats_rows=colstats_rows, aux=G.aux_ptr(col))
+    return xn, gate
+
+
+def layer_bwd(x, z, h, gate, weight, wg, csr_t, dx, dhs, dropout_in, rng_state, layer_id, dxn=None, dgate=None, head=None,
+              sink=None, fuse_sink=None, aux_stream=None):
+    """cgcn_layer_bwd -> (dW, db, dwg, dcg), written into `sink` when one is given.  dL/dX' comes as dxn (+ dgate) or from
+    the fused head (head: a _lib.HeadGrad).  fuse_sink: the engine's gradient sink of this layer, which lets the call carry
+    the step's SGD update (_sgd_fuse) when there is no aux_stream (_lib.aux_stream_ptr)."""
+    S, n, d = x.shape
+    f32 = dict(device=x.device, dtype=torch.float32)
+    if sink is not None:
+        dw, db, dwg, dcg = sink
+    else:
+        dw, db, dwg, dcg = torch.empty_like(weight), torch.empty(d, **f32), torch.empty(d, **f32), torch.empty(1, **f32)
+    ws = _lib.layer_bwd_workspace(n, S, d, x.device)
+    sgd = _sgd_fuse_arg(layer_id, fuse_sink) if aux_stream is None else None
+    rowptr_t, col_t, val_t, row_scale = csr_t
+    _lib.call("cgcn_layer_bwd", n=n, S=S, d=d, rowptr_t=rowptr_t, col_t=col_t, val_t=val_t, row_scale=row_scale, X=x, Z=z,
+              H=h, gate=gate, W=weight, wg=wg, dXn=dxn, dgate=dgate, dX=dx, dHs=dhs, dW=dw, db=db, dwg=dwg, dcg=dcg,
+              accumulate=0, in_dropout_p=float(dropout_in), rng_state=rng_state, in_stream_id=max(layer_id - 1, 0),
+              head=head, workspace=ws, workspace_bytes=ws.numel(), aux_stream=aux_stream, sgd=sgd, aux_t=G.aux_ptr(col_t))
+    if sgd is not None:
+        _sgd_fuse["done"] = True
+    return dw, db, dwg, dcg
+
+
+def head_fwd(x, params, target, run_mean, run_var, nbt, momentum, eps, training, dropout_p, rng_state, probs, loss, dpred,
+             save_mean, save_invstd):
+    """cgcn_head_fwd; dpred / save_mean / save_invstd: buffers to fill, or None"""
+    S, n, d = x.shape
+    bn_w, bn_b, w_out, b_out = params
+    ws = _lib.head_workspace(n, S, d, w_out.shape[0], x.device)
+    _lib.call("cgcn_head_fwd", n=n, S=S, d=d, C=w_out.shape[0], X=x, bn_w=bn_w, bn_b=bn_b, run_mean=run_mean, run_var=run_var,
+              num_batches_tracked=nbt, momentum=float(momentum), eps=float(eps), training=1 if training else 0, W_out=w_out,
+              b_out=b_out, target=target, dropout_p=float(dropout_p),
+              rng_state=rng_state if training and dropout_p > 0 else None, probs=probs, loss=loss, dpred=dpred,
+              save_mean=save_mean, save_invstd=save_invstd, workspace=ws, workspace_bytes=ws.numel())
+
+
+def _head_grad_bufs(sink, d, w_out):
+    """(dbn_w, dbn_b, dW_out, db_out): the gradient sink, or new buffers"""
+    if sink is not None:
+        return sink
+    f32 = dict(device=w_out.device, dtype=torch.float32)
+    return torch.empty(d, **f32), torch.empty(d, **f32), torch.empty_like(w_out), torch.empty(w_out.shape[0], **f32)
+
+
+def head_bwd(dloss, x, bn_w, bn_b, w_out, dpred, save_mean, save_invstd, dropout_p, rng_state, sink=None):
+    """cgcn_head_bwd -> (dX, dbn_w, dbn_b, dW_out, db_out); the parameter gradients go into `sink` when one is given"""
+    S, n, d = x.shape
+    C = w_out.shape[0]
+    ws = _lib.head_workspace(n, S, d, C, x.device)
+    dx = torch.empty_like(x)
+    dbn_w, dbn_b, dw_out, db_out = _head_grad_bufs(sink, d, w_out)
+    _lib.call("cgcn_head_bwd", n=n, S=S, d=d, C=C, X=x, bn_w=bn_w, bn_b=bn_b, save_mean=save_mean, save_invstd=save_invstd,
+              W_out=w_out, dpred=dpred.contiguous(), dloss=dloss.contiguous().view(1), dropout_p=float(dropout_p),
+              rng_state=rng_state if dropout_p > 0 else None, dX=dx, dW_out=dw_out, db_out=db_out, dbn_w=dbn_w, dbn_b=dbn_b,
+              accumulate=0, workspace=ws, workspace_bytes=ws.numel())
+    return dx, dbn_w, dbn_b, dw_out, db_out
 
 
 # feature tables from this size on do not fit the L2s: cgcn_layer_fwd's split route (FWD_SPLIT_TABLE_BYTES in csrc)
@@ -171,30 +257,17 @@ class GatedLayerFn(torch.autograd.Function):
         S, n, d = x.shape
         if tuple(weight.shape) != (d, d):
             raise RuntimeError("chromegcn_amd: fused layer needs a square [d,d] weight, got %s" % (tuple(weight.shape),))
-        weight = _dense(weight)
-        bias = bias.contiguous()
-        wg = gate_w.contiguous().view(-1)
-        cg = gate_b.contiguous().view(-1)
+        params = _layer_params(weight, bias, gate_w, gate_b)
         need_bwd = any(ctx.needs_input_grad[:5])
-        xn = torch.empty_like(x)
-        gate = torch.empty((S, n), device=x.device, dtype=torch.float32)
         z = torch.empty_like(x) if need_bwd else None
         h_in, h = _resolve_h_cache(h_cache, x, need_bwd)
-        if (dropout_out > 0 or dropout_in > 0) and rng_state is None:
-            raise RuntimeError("chromegcn_amd: fused dropout needs the model's rng_state tensor")
-        lib = _lib.load()
-        _lib.check(lib.cgcn_layer_fwd(_lib.stream_ptr(), n, S, d, _lib.ptr(graph.rowptr), _lib.ptr(graph.col),
-                                      _lib.ptr(graph.val), _lib.ptr(graph.row_scale), x.data_ptr(), weight.data_ptr(),
-                                      bias.data_ptr(), wg.data_ptr(), cg.data_ptr(), xn.data_ptr(), _lib.ptr(z),
-                                      _lib.ptr(h), gate.data_ptr(), float(dropout_out),
-                                      _lib.ptr(rng_state) if dropout_out > 0 else None, int(layer_id), _lib.ptr(h_in),
-                                      # zero_stat: the NEXT (last) layer's statistics totals, zeroed by this call's first launch
-                                      _lib.ptr(zero_stat), _lib.COLSTATS_ROWS_ZERO_ONLY if zero_stat is not None else 0,
-                                      G.aux_ptr(graph.col)),
-                   "cgcn_layer_fwd")
+        _check_rng(rng_state, dropout_out > 0 or dropout_in > 0)
+        # zero_stat: the NEXT (last) layer's statistics totals, zeroed by this call's first launch
+        xn, gate = layer_fwd(x, params, (graph.rowptr, graph.col, graph.val, graph.row_scale), z, h, dropout_out, rng_state,
+                             layer_id, h_in, zero_stat, _lib.COLSTATS_ROWS_ZERO_ONLY if zero_stat is not None else 0)
         h = _store_h_cache(h_cache, h_in, h)
         if need_bwd:
-            ctx.save_for_backward(x, z, h, gate, weight, wg, rng_state if dropout_in > 0 else None)
+            ctx.save_for_backward(x, z, h, gate, params[0], params[2], rng_state if dropout_in > 0 else None)
         ctx.graph = graph
         ctx.gate_w_shape = gate_w.shape
         ctx.gate_b_shape = gate_b.shape
@@ -208,7 +281,6 @@ class GatedLayerFn(torch.autograd.Function):
     def backward(ctx, dxn, dgate):
         x, z, h, gate, weight, wg, rng_state = ctx.saved_tensors
         g = ctx.graph
-        S, n, d = x.shape
         if dxn is None and dgate is None:
             return (None,) * 13
         dxn = torch.zeros_like(x) if dxn is None else _dense(dxn)
@@ -216,27 +288,9 @@ class GatedLayerFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None  # None: skip the gather over Ahat^T
         # dHs = diag(row_scale) dL/dU W^T: the gather's operand (and the saliency SDDMM's); not computed when unused
         dhs = torch.empty_like(x) if (dx is not None or _saliency_tap is not None) else None
-        if ctx.sink is not None:
-            dw, db, dwg, dcg = ctx.sink
-        else:
-            dw = torch.empty_like(weight)
-            db = torch.empty(d, device=x.device, dtype=torch.float32)
-            dwg = torch.empty(d, device=x.device, dtype=torch.float32)
-            dcg = torch.empty(1, device=x.device, dtype=torch.float32)
-        lib = _lib.load()
-        ws_bytes = lib.cgcn_layer_bwd_workspace_bytes(n, S, d)
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-        sg_ref, sg_keep = _sgd_fuse_arg(ctx.layer_id, dx, ctx.sink)
-        _lib.check(lib.cgcn_layer_bwd(_lib.stream_ptr(), n, S, d, _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t),
-                                      _lib.ptr(g.val_t), _lib.ptr(g.row_scale), x.data_ptr(), z.data_ptr(),
-                                      h.data_ptr(), gate.data_ptr(), weight.data_ptr(), wg.data_ptr(),
-                                      dxn.data_ptr(), _lib.ptr(dgate), _lib.ptr(dx), _lib.ptr(dhs), dw.data_ptr(),
-                                      db.data_ptr(), dwg.data_ptr(), dcg.data_ptr(), 0, ctx.dropout_in,
-                                      _lib.ptr(rng_state), max(ctx.layer_id - 1, 0), None, ws.data_ptr(), ws_bytes,
-                                      _lib.aux_stream_ptr(), sg_ref, G.aux_ptr(g.col_t)),
-                   "cgcn_layer_bwd")
-        if sg_ref is not None:
-            _sgd_fuse["done"] = True
+        dw, db, dwg, dcg = layer_bwd(x, z, h, gate, weight, wg, (g.rowptr_t, g.col_t, g.val_t, g.row_scale), dx, dhs,
+                                     ctx.dropout_in, rng_state, ctx.layer_id, dxn, dgate, sink=ctx.sink, fuse_sink=ctx.sink,
+                                     aux_stream=_lib.aux_stream_ptr())
         if _saliency_tap is not None:
             _saliency_tap.append((x, dhs, g))
         if ctx.sink is not None:
@@ -267,7 +321,7 @@ def stat_buffer(x):
     CGCN_COLSTATS_ACCUMULATE), or None when the shape has none (n < 2).  Uninitialised: a launch of the step zeroes it."""
     S, n, d = x.shape
     rows = ctypes.c_int(0)
-    tiles = _lib.load().cgcn_layer_fwd_colstats_plan(n, S, d, _lib.COLSTATS_ACCUMULATE, ctypes.byref(rows))
+    tiles = _lib.query("cgcn_layer_fwd_colstats_plan", n=n, S=S, d=d, mode=_lib.COLSTATS_ACCUMULATE, rows_per_tile=rows)
     if tiles <= 0 or rows.value != -1:
         return None
     return torch.empty((tiles, S, d, 2), device=x.device, dtype=torch.float32)
@@ -285,20 +339,14 @@ class HeadLossFn(torch.autograd.Function):
         _require_cuda(x, "x")
         for t, nm in ((bn_w, "bn weight"), (bn_b, "bn bias"), (w_out, "out.weight"), (b_out, "out.bias"), (target, "target")):
             _require_cuda(t, nm)
-        if momentum is None:
-            raise RuntimeError("chromegcn_amd: BatchNorm momentum=None (cumulative average) is not supported by the fused head")
+        _check_momentum(momentum)
         x = _dense(x)
         S, n, d = x.shape
         C = w_out.shape[0]
         target = target.contiguous()
         if tuple(target.shape) != (n, C):
             raise RuntimeError("chromegcn_amd: target must be [n, C] = [%d, %d], got %s" % (n, C, tuple(target.shape)))
-        bn_w, bn_b, w_out, b_out = _dense(bn_w), _dense(bn_b), _dense(w_out), b_out.contiguous()
-        lib = _lib.load()
-        ws_bytes = lib.cgcn_head_workspace_bytes(n, S, d, C)
-        if ws_bytes == 0:
-            raise RuntimeError("chromegcn_amd: fused head does not support S=%d n=%d d=%d C=%d" % (S, n, d, C))
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+        params = _head_params(bn_w, bn_b, w_out, b_out)
         need_bwd = training and any(ctx.needs_input_grad[:5])
         ctx.eval_grad = (not training) and any(ctx.needs_input_grad[:5])
         probs, loss = _out_slots(out_slots, n, C, x.device)
@@ -306,16 +354,11 @@ class HeadLossFn(torch.autograd.Function):
         save_mean = torch.empty((S, d), device=x.device, dtype=torch.float32) if training else None
         save_invstd = torch.empty((S, d), device=x.device, dtype=torch.float32) if training else None
         drop = bool(training) and dropout_p > 0
-        if drop and rng_state is None:
-            raise RuntimeError("chromegcn_amd: fused dropout needs the model's rng_state tensor")
-        _lib.check(lib.cgcn_head_fwd(_lib.stream_ptr(), n, S, d, C, x.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                     run_mean.data_ptr(), run_var.data_ptr(), _lib.ptr(nbt), float(momentum), float(eps),
-                                     1 if training else 0, w_out.data_ptr(), b_out.data_ptr(), target.data_ptr(),
-                                     float(dropout_p), _lib.ptr(rng_state) if drop else None,
-                                     probs.data_ptr(), loss.data_ptr(), _lib.ptr(dpred), _lib.ptr(save_mean),
-                                     _lib.ptr(save_invstd), ws.data_ptr(), ws_bytes), "cgcn_head_fwd")
+        _check_rng(rng_state, drop)
+        head_fwd(x, params, target, run_mean, run_var, nbt, momentum, eps, training, dropout_p, rng_state, probs, loss, dpred,
+                 save_mean, save_invstd)
         if need_bwd:
-            ctx.save_for_backward(x, bn_w, bn_b, w_out, dpred, save_mean, save_invstd, rng_state if drop else None)
+            ctx.save_for_backward(x, *params[:3], dpred, save_mean, save_invstd, rng_state if drop else None)
             ctx.dropout_p = float(dropout_p) if drop else 0.0
             ctx.sink = grad_sink if _sink_ok(grad_sink, ((d,), (d,), (C, d), (C,))) else None
         ctx.mark_non_differentiable(probs)
@@ -326,25 +369,8 @@ class HeadLossFn(torch.autograd.Function):
         if ctx.eval_grad:
             raise RuntimeError(_EVAL_BWD_MSG)
         x, bn_w, bn_b, w_out, dpred, save_mean, save_invstd, rng_state = ctx.saved_tensors
-        S, n, d = x.shape
-        C = w_out.shape[0]
-        lib = _lib.load()
-        ws_bytes = lib.cgcn_head_workspace_bytes(n, S, d, C)
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-        dx = torch.empty_like(x)
-        if ctx.sink is not None:
-            dbn_w, dbn_b, dw_out, db_out = ctx.sink
-        else:
-            dw_out = torch.empty_like(w_out)
-            db_out = torch.empty(C, device=x.device, dtype=torch.float32)
-            dbn_w = torch.empty(d, device=x.device, dtype=torch.float32)
-            dbn_b = torch.empty(d, device=x.device, dtype=torch.float32)
-        dloss = dloss.contiguous().view(1)
-        _lib.check(lib.cgcn_head_bwd(_lib.stream_ptr(), n, S, d, C, x.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                     save_mean.data_ptr(), save_invstd.data_ptr(), w_out.data_ptr(), dpred.data_ptr(),
-                                     dloss.data_ptr(), ctx.dropout_p, _lib.ptr(rng_state), dx.data_ptr(),
-                                     dw_out.data_ptr(), db_out.data_ptr(), dbn_w.data_ptr(), dbn_b.data_ptr(), 0,
-                                     ws.data_ptr(), ws_bytes), "cgcn_head_bwd")
+        dx, dbn_w, dbn_b, dw_out, db_out = head_bwd(dloss, x, bn_w, bn_b, w_out, dpred, save_mean, save_invstd, ctx.dropout_p,
+                                                    rng_state, ctx.sink)
         if ctx.sink is not None:
             return (dx,) + (None,) * 15
         return (dx, dbn_w, dbn_b, dw_out, db_out) + (None,) * 11
@@ -364,25 +390,20 @@ class LastLayerHeadLossFn(torch.autograd.Function):
         for t, nm in ((weight, "weight"), (bias, "bias"), (gate_w, "gate weight"), (gate_b, "gate bias"),
                       (bn_w, "bn weight"), (bn_b, "bn bias"), (w_out, "out.weight"), (b_out, "out.bias"), (target, "target")):
             _require_cuda(t, nm)
-        if momentum is None:
-            raise RuntimeError("chromegcn_amd: BatchNorm momentum=None (cumulative average) is not supported by the fused head")
+        _check_momentum(momentum)
         x = _dense(x)
         S, n, d = x.shape
         C = w_out.shape[0]
         target = target.contiguous()
         if tuple(weight.shape) != (d, d) or tuple(target.shape) != (n, C):
             raise RuntimeError("chromegcn_amd: bad shapes for the fused last layer + head")
-        weight, bias = _dense(weight), bias.contiguous()
-        wg, cg = gate_w.contiguous().view(-1), gate_b.contiguous().view(-1)
-        bn_w, bn_b, w_out, b_out = _dense(bn_w), _dense(bn_b), _dense(w_out), b_out.contiguous()
+        weight, bias, wg, cg = _layer_params(weight, bias, gate_w, gate_b)
+        bn_w, bn_b, w_out, b_out = _head_params(bn_w, bn_b, w_out, b_out)
         need_bwd = training and any(ctx.needs_input_grad[:9])
         ctx.eval_grad = (not training) and any(ctx.needs_input_grad[:9])
-        lib = _lib.load()
-        xn = torch.empty_like(x)
-        gate = torch.empty((S, n), device=x.device, dtype=torch.float32)
         z = torch.empty_like(x) if need_bwd else None
         h_in, h = _resolve_h_cache(h_cache, x, need_bwd)
-        colstats, cs_tiles, cs_rows = None, 0, 0
+        colstats, cs_tiles, cs_rows, fwd_rows = None, 0, 0, 0
         if need_bwd:
             # the layer kernel also emits the first stage of the head's BatchNorm statistics (tile still on chip)
             # stat_acc: the caller vouches for the range of the fixed-point totals (include/chromegcn.h,
@@ -390,48 +411,35 @@ class LastLayerHeadLossFn(torch.autograd.Function):
             # otherwise per-workgroup records.  Accumulate mode needs the two-launch route, i.e. an H buffer of this call.
             # stat_buf: totals an EARLIER launch of this step has zeroed (the previous layer's forward: gated_layer(zero_stat=...));
             # this layer then accumulates on whatever route its table size gives it -- the fused kernel for small tables.
-            rows = ctypes.c_int(0)
-            fwd_rows = None
             if stat_acc and stat_buf is not None:
                 colstats, cs_tiles, cs_rows = stat_buf, stat_buf.shape[0], -1
                 fwd_rows = _lib.COLSTATS_ROWS_ACCUMULATE_ZEROED
             else:
                 mode = _lib.COLSTATS_ACCUMULATE if (stat_acc and (h is not None or h_in is not None)) else _lib.COLSTATS_RECORDS
-                cs_tiles = lib.cgcn_layer_fwd_colstats_plan(n, S, d, mode, ctypes.byref(rows))
-                cs_rows = rows.value
+                rows = ctypes.c_int(0)
+                cs_tiles = _lib.query("cgcn_layer_fwd_colstats_plan", n=n, S=S, d=d, mode=mode, rows_per_tile=rows)
+                cs_rows = fwd_rows = rows.value
                 colstats = torch.empty((cs_tiles, S, d, 2), device=x.device, dtype=torch.float32)
-        _lib.check(lib.cgcn_layer_fwd(_lib.stream_ptr(), n, S, d, _lib.ptr(graph.rowptr), _lib.ptr(graph.col),
-                                      _lib.ptr(graph.val), _lib.ptr(graph.row_scale), x.data_ptr(), weight.data_ptr(),
-                                      bias.data_ptr(), wg.data_ptr(), cg.data_ptr(), xn.data_ptr(), _lib.ptr(z),
-                                      _lib.ptr(h), gate.data_ptr(), 0.0, None, int(layer_id), _lib.ptr(h_in), _lib.ptr(colstats),
-                                      cs_rows if (not need_bwd or fwd_rows is None) else fwd_rows, G.aux_ptr(graph.col)), "cgcn_layer_fwd")
+        xn, gate = layer_fwd(x, (weight, bias, wg, cg), (graph.rowptr, graph.col, graph.val, graph.row_scale), z, h,
+                             layer_id=layer_id, h_in=h_in, colstats=colstats, colstats_rows=fwd_rows)
         h = _store_h_cache(h_cache, h_in, h)
-        ws_bytes = lib.cgcn_head_workspace_bytes(n, S, d, C)
-        if ws_bytes == 0:
-            raise RuntimeError("chromegcn_amd: fused head does not support S=%d n=%d d=%d C=%d" % (S, n, d, C))
-        ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
         probs, loss = _out_slots(out_slots, n, C, x.device)
         save_mean = torch.empty((S, d), device=x.device, dtype=torch.float32) if training else None
         save_invstd = torch.empty((S, d), device=x.device, dtype=torch.float32) if training else None
         drop = bool(training) and dropout_p > 0
-        if (drop or dropout_in > 0) and rng_state is None:
-            raise RuntimeError("chromegcn_amd: fused dropout needs the model's rng_state tensor")
+        _check_rng(rng_state, drop or dropout_in > 0)
         if need_bwd:
             # forward of the head + the tile-local half of its backward in one pass (cgcn_head_train); the workspace
             # carries dym and the partial sums to backward()
-            _lib.check(lib.cgcn_head_train(_lib.stream_ptr(), n, S, d, C, xn.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                           run_mean.data_ptr(), run_var.data_ptr(), _lib.ptr(nbt), float(momentum), float(eps),
-                                           w_out.data_ptr(), b_out.data_ptr(), target.data_ptr(), float(dropout_p) if drop else 0.0,
-                                           _lib.ptr(rng_state) if drop else None, probs.data_ptr(), loss.data_ptr(),
-                                           save_mean.data_ptr(), save_invstd.data_ptr(), _lib.ptr(colstats), cs_tiles, cs_rows,
-                                           ws.data_ptr(), ws_bytes), "cgcn_head_train")
+            ws = _lib.head_workspace(n, S, d, C, x.device)
+            _lib.call("cgcn_head_train", n=n, S=S, d=d, C=C, X=xn, bn_w=bn_w, bn_b=bn_b, run_mean=run_mean, run_var=run_var,
+                      num_batches_tracked=nbt, momentum=float(momentum), eps=float(eps), W_out=w_out, b_out=b_out,
+                      target=target, dropout_p=float(dropout_p) if drop else 0.0, rng_state=rng_state if drop else None,
+                      probs=probs, loss=loss, save_mean=save_mean, save_invstd=save_invstd, col_stats=colstats,
+                      col_stats_tiles=cs_tiles, col_stats_rows=cs_rows, workspace=ws, workspace_bytes=ws.numel())
         else:
-            _lib.check(lib.cgcn_head_fwd(_lib.stream_ptr(), n, S, d, C, xn.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                         run_mean.data_ptr(), run_var.data_ptr(), _lib.ptr(nbt), float(momentum), float(eps),
-                                         1 if training else 0, w_out.data_ptr(), b_out.data_ptr(), target.data_ptr(),
-                                         float(dropout_p), _lib.ptr(rng_state) if drop else None, probs.data_ptr(),
-                                         loss.data_ptr(), None, _lib.ptr(save_mean), _lib.ptr(save_invstd),
-                                         ws.data_ptr(), ws_bytes), "cgcn_head_fwd")
+            head_fwd(xn, (bn_w, bn_b, w_out, b_out), target, run_mean, run_var, nbt, momentum, eps, training, dropout_p,
+                     rng_state, probs, loss, None, save_mean, save_invstd)
         if need_bwd:
             ctx.save_for_backward(x, z, h, gate, weight, wg, xn, bn_w, bn_b, w_out, ws, save_mean, save_invstd,
                                   rng_state if (drop or dropout_in > 0) else None,
@@ -453,50 +461,29 @@ class LastLayerHeadLossFn(torch.autograd.Function):
     def backward(ctx, dloss, _dprobs, _dgate):
         if ctx.eval_grad:
             raise RuntimeError(_EVAL_BWD_MSG)
+        if dloss is None:
+            return (None,) * 27
         (x, z, h, gate, weight, wg, xn, bn_w, bn_b, w_out, hws, save_mean, save_invstd, rng_state, stat_acc) = ctx.saved_tensors
         g = ctx.graph
         S, n, d = x.shape
         C = w_out.shape[0]
-        dev = x.device
-        lib = _lib.load()
-        f32 = dict(device=dev, dtype=torch.float32)
-        if ctx.head_sink is not None:
-            dbn_w, dbn_b, dw_out, db_out = ctx.head_sink
-        else:
-            dw_out, db_out = torch.empty_like(w_out), torch.empty(C, **f32)
-            dbn_w, dbn_b = torch.empty(d, **f32), torch.empty(d, **f32)
-        if ctx.layer_sink is not None:
-            dw, db, dwg, dcg = ctx.layer_sink
-        else:
-            dw, db, dwg, dcg = torch.empty_like(weight), torch.empty(d, **f32), torch.empty(d, **f32), torch.empty(1, **f32)
-        hws_bytes = hws.numel()
-        if dloss is None:
-            return (None,) * 27
+        dbn_w, dbn_b, dw_out, db_out = _head_grad_bufs(ctx.head_sink, d, w_out)
         dloss = dloss.contiguous().view(1)
         # dym, bnc and the partials are already in the workspace cgcn_head_train filled (for d loss = 1); every head
         # gradient is finished inside cgcn_layer_bwd (cgcn_head_grad.dloss / dbn_w / dbn_b), so no head launch here
         o_dym, o_bnc, o_part = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(lib.cgcn_head_workspace_layout(n, S, d, C, ctypes.byref(o_dym), ctypes.byref(o_bnc), ctypes.byref(o_part)),
-                   "cgcn_head_workspace_layout")
+        _lib.call("cgcn_head_workspace_layout", n=n, S=S, d=d, C=C, dym_offset=o_dym, bnc_offset=o_bnc, part_offset=o_part)
         hg = _lib.HeadGrad(hws.data_ptr() + o_dym.value, hws.data_ptr() + o_bnc.value, save_mean.data_ptr(),
                            save_invstd.data_ptr(), bn_w.data_ptr(), ctx.dropout_p, _lib.ptr(rng_state),
-                           hws.data_ptr() + o_part.value, lib.cgcn_head_bwd_partials(n), C, dw_out.data_ptr(),
+                           hws.data_ptr() + o_part.value, _lib.query("cgcn_head_bwd_partials", n=n), C, dw_out.data_ptr(),
                            db_out.data_ptr(), 0, dloss.data_ptr(), dbn_w.data_ptr(), dbn_b.data_ptr(), _lib.ptr(stat_acc))
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dhs = torch.empty_like(x) if dx is not None else None
-        ws_bytes = lib.cgcn_layer_bwd_workspace_bytes(n, S, d)
-        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
         # a one-layer model: this IS the first layer's backward, i.e. the last launch of the step
-        sg_ref, sg_keep = _sgd_fuse_arg(ctx.layer_id, dx, ctx.layer_sink if ctx.head_sink is not None else None)
-        _lib.check(lib.cgcn_layer_bwd(_lib.stream_ptr(), n, S, d, _lib.ptr(g.rowptr_t), _lib.ptr(g.col_t),
-                                      _lib.ptr(g.val_t), _lib.ptr(g.row_scale), x.data_ptr(), z.data_ptr(),
-                                      h.data_ptr(), gate.data_ptr(), weight.data_ptr(), wg.data_ptr(),
-                                      None, None, _lib.ptr(dx), _lib.ptr(dhs), dw.data_ptr(), db.data_ptr(),
-                                      dwg.data_ptr(), dcg.data_ptr(), 0, ctx.dropout_in, _lib.ptr(rng_state),
-                                      max(ctx.layer_id - 1, 0), ctypes.byref(hg), ws.data_ptr(), ws_bytes,
-                                      _lib.aux_stream_ptr(), sg_ref, G.aux_ptr(g.col_t)), "cgcn_layer_bwd")
-        if sg_ref is not None:
-            _sgd_fuse["done"] = True
+        dw, db, dwg, dcg = layer_bwd(x, z, h, gate, weight, wg, (g.rowptr_t, g.col_t, g.val_t, g.row_scale), dx, dhs,
+                                     ctx.dropout_in, rng_state, ctx.layer_id, head=hg, sink=ctx.layer_sink,
+                                     fuse_sink=ctx.layer_sink if ctx.head_sink is not None else None,
+                                     aux_stream=_lib.aux_stream_ptr())
         gl = (None,) * 4 if ctx.layer_sink is not None else (dw, db, dwg.view(ctx.shapes[0]), dcg.view(ctx.shapes[1]))
         gh = (None,) * 4 if ctx.head_sink is not None else (dbn_w, dbn_b, dw_out, db_out)
         return (dx,) + gl + gh + (None,) * 18
@@ -538,10 +525,11 @@ def head_logits(x, bn: torch.nn.BatchNorm1d, out: torch.nn.Linear):
 
 def sgd_step(flat_param, flat_grad, flat_mom, lr, momentum, weight_decay, nesterov, rng_state=None, grad_scale=1.0):
     """torch.optim.SGD step on flat buffers in one launch (cgcn_sgd_step); also advances the dropout counter."""
-    lib = _lib.load()
-    _lib.check(lib.cgcn_sgd_step(_lib.stream_ptr(), flat_param.numel(), flat_param.data_ptr(), flat_grad.data_ptr(),
-                                 _lib.ptr(flat_mom), float(lr), float(momentum), float(weight_decay),
-                                 1 if nesterov else 0, float(grad_scale), _lib.ptr(rng_state)), "cgcn_sgd_step")
+    if not (flat_param.is_contiguous() and flat_grad.is_contiguous() and flat_param.numel() == flat_grad.numel()):
+        raise RuntimeError("chromegcn_amd: sgd_step: param and grad must be contiguous and of equal size")
+    _lib.call("cgcn_sgd_step", count=flat_param.numel(), param=flat_param, grad=flat_grad, momentum_buf=flat_mom, lr=float(lr),
+              momentum=float(momentum), weight_decay=float(weight_decay), nesterov=1 if nesterov else 0,
+              grad_scale=float(grad_scale), rng_state=rng_state)
 
 
 def adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq, step, ticket, lr, beta1, beta2, eps, weight_decay,
@@ -549,8 +537,11 @@ def adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq, step, ticket, lr, beta
     """torch.optim.Adam step on flat buffers in one launch (cgcn_adam_step): `step` is a float32 device tensor of
     per-parameter counts (all advanced by one), `ticket` an int32 device word that stays 0 between launches; also
     advances the dropout counter."""
-    lib = _lib.load()
-    _lib.check(lib.cgcn_adam_step(_lib.stream_ptr(), flat_param.numel(), flat_param.data_ptr(), flat_grad.data_ptr(),
-                                  exp_avg.data_ptr(), exp_avg_sq.data_ptr(), step.data_ptr(), step.numel(),
-                                  ticket.data_ptr(), float(lr), float(beta1), float(beta2), float(eps),
-                                  float(weight_decay), float(grad_scale), _lib.ptr(rng_state)), "cgcn_adam_step")
+    n = flat_param.numel()
+    if not all(t.is_contiguous() and t.numel() == n for t in (flat_param, flat_grad, exp_avg, exp_avg_sq)):
+        raise RuntimeError("chromegcn_amd: adam_step: param, grad, exp_avg and exp_avg_sq must be contiguous and of equal size")
+    if step.dtype != torch.float32 or not step.is_contiguous() or ticket.dtype != torch.int32 or ticket.numel() < 1:
+        raise RuntimeError("chromegcn_amd: adam_step: step must be contiguous float32, ticket int32 with one element")
+    _lib.call("cgcn_adam_step", count=n, param=flat_param, grad=flat_grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, step=step,
+              n_step=step.numel(), ticket=ticket, lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps),
+              weight_decay=float(weight_decay), grad_scale=float(grad_scale), rng_state=rng_state)

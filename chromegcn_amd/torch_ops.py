@@ -25,22 +25,9 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, ops
 from .graph import aux_ptr
-
-_P = _lib.ptr
-
-
-def _cuda_f32(t: Tensor, name: str):
-    if not t.is_cuda:
-        raise RuntimeError("chromegcn_amd: %s is on %s; the path only exists as HIP kernels (no CPU fallback)" % (name, t.device))
-    if t.dtype != torch.float32:
-        raise RuntimeError("chromegcn_amd: %s must be float32, got %s" % (name, t.dtype))
-
-
-def _dense(t: Tensor) -> Tensor:
-    t = t.contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
+from .ops import _dense, _require_cuda
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -51,16 +38,15 @@ def spmm(x: Tensor, rowptr: Tensor, col: Tensor, val: Optional[Tensor], row_scal
          rowptr_t: Tensor, col_t: Tensor, val_t: Optional[Tensor]) -> Tensor:
     """Y[s] = diag(row_scale) Ahat X[s];  x: [S, n_cols, d] (S in {1,2}, d % 4 == 0).  rowptr_t / col_t / val_t: CSR of
     Ahat^T for the backward (the same tensors for the symmetric graphs the reference writes)."""
-    _cuda_f32(x, "x")
+    _require_cuda(x, "x")
     if x.dim() != 3:
         raise RuntimeError("chromegcn::spmm: x must be [S, n, d], got %s" % (tuple(x.shape),))
     x = _dense(x)
     S, n_cols, d = x.shape
     n_rows = rowptr.numel() - 1
     y = torch.empty((S, n_rows, d), device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.cgcn_spmm(_lib.stream_ptr(), n_rows, n_cols, S, d, _P(rowptr), _P(col), _P(val), _P(row_scale),
-                             x.data_ptr(), y.data_ptr(), aux_ptr(col)), "cgcn_spmm")
+    _lib.call("cgcn_spmm", n_rows=n_rows, n_cols=n_cols, S=S, d=d, rowptr=rowptr, col=col, val=val, row_scale=row_scale, X=x,
+              Y=y, aux=aux_ptr(col))
     return y
 
 
@@ -96,24 +82,17 @@ def gated_layer(x: Tensor, weight: Tensor, bias: Tensor, gate_w: Tensor, gate_b:
     """(X', gate, Z, H) of one gated layer: H = diag(row_scale) Ahat X, Z = tanh(H W + b), g = sigmoid(Z w + c),
     X' = dropout_out((1 - g) X + g Z).  Z and H are what the backward needs.  x: [S, n, d], d in {128, 256}."""
     for t, nm in ((x, "x"), (weight, "weight"), (bias, "bias"), (gate_w, "gate weight"), (gate_b, "gate bias")):
-        _cuda_f32(t, nm)
+        _require_cuda(t, nm)
     if x.dim() != 3 or x.shape[0] not in (1, 2) or x.shape[2] not in (128, 256):
         raise RuntimeError("chromegcn::gated_layer: x must be [S in {1,2}, n, d in {128,256}], got %s" % (tuple(x.shape),))
     x = _dense(x)
     S, n, d = x.shape
     if tuple(weight.shape) != (d, d) or rowptr.numel() != n + 1:
         raise RuntimeError("chromegcn::gated_layer: weight must be [d, d] and the graph must have n nodes")
-    if (dropout_out > 0 or dropout_in > 0) and rng_state is None:
-        raise RuntimeError("chromegcn::gated_layer: dropout needs the rng_state tensor")
-    weight, bias = _dense(weight), bias.contiguous()
-    wg, cg = gate_w.contiguous().view(-1), gate_b.contiguous().view(-1)
-    xn, z, h = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-    gate = torch.empty((S, n), device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    _lib.check(lib.cgcn_layer_fwd(_lib.stream_ptr(), n, S, d, _P(rowptr), _P(col), _P(val), _P(row_scale), x.data_ptr(),
-                                  weight.data_ptr(), bias.data_ptr(), wg.data_ptr(), cg.data_ptr(), xn.data_ptr(),
-                                  z.data_ptr(), h.data_ptr(), gate.data_ptr(), float(dropout_out),
-                                  _P(rng_state) if dropout_out > 0 else None, int(layer_id), None, None, 0, aux_ptr(col)), "cgcn_layer_fwd")
+    ops._check_rng(rng_state, dropout_out > 0 or dropout_in > 0)
+    z, h = torch.empty_like(x), torch.empty_like(x)
+    xn, gate = ops.layer_fwd(x, ops._layer_params(weight, bias, gate_w, gate_b), (rowptr, col, val, row_scale), z, h,
+                             dropout_out, rng_state, layer_id)
     return xn, gate, z, h
 
 
@@ -132,22 +111,12 @@ def gated_layer_backward(dxn: Tensor, dgate: Optional[Tensor], x: Tensor, z: Ten
     over Ahat^T (dX comes back empty).  dHs = diag(row_scale) dL/dU W^T (the gather's and the saliency SDDMM's operand)."""
     dxn = _dense(dxn)
     x, z, h, weight = _dense(x), _dense(z), _dense(h), _dense(weight)
-    S, n, d = x.shape
-    dev = x.device
-    f32 = dict(device=dev, dtype=torch.float32)
-    dx = torch.empty_like(x) if need_dx else torch.empty(0, **f32)
+    dx = torch.empty_like(x) if need_dx else x.new_empty(0)
     dhs = torch.empty_like(x)
-    dw, db, dwg, dcg = torch.empty_like(weight), torch.empty(d, **f32), torch.empty(d, **f32), torch.empty(1, **f32)
-    lib = _lib.load()
-    ws_bytes = lib.cgcn_layer_bwd_workspace_bytes(n, S, d)
-    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
-    wg = gate_w.contiguous().view(-1)
-    _lib.check(lib.cgcn_layer_bwd(_lib.stream_ptr(), n, S, d, _P(rowptr_t), _P(col_t), _P(val_t), _P(row_scale),
-                                  x.data_ptr(), z.data_ptr(), h.data_ptr(), gate.contiguous().data_ptr(), weight.data_ptr(),
-                                  wg.data_ptr(), dxn.data_ptr(), _P(None if dgate is None else dgate.contiguous()),
-                                  dx.data_ptr() if need_dx else None, dhs.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                  dwg.data_ptr(), dcg.data_ptr(), 0, float(dropout_in), _P(rng_state) if dropout_in > 0 else None,
-                                  max(int(layer_id) - 1, 0), None, ws.data_ptr(), ws_bytes, None, None, aux_ptr(col_t)), "cgcn_layer_bwd")
+    dw, db, dwg, dcg = ops.layer_bwd(x, z, h, gate.contiguous(), weight, gate_w.contiguous().view(-1),
+                                     (rowptr_t, col_t, val_t, row_scale), dx if need_dx else None, dhs, dropout_in,
+                                     rng_state if dropout_in > 0 else None, int(layer_id), dxn,
+                                     None if dgate is None else dgate.contiguous())
     return dx, dw, db, dwg, dcg, dhs
 
 
@@ -198,34 +167,22 @@ def head_loss(x: Tensor, bn_w: Tensor, bn_b: Tensor, w_out: Tensor, b_out: Tenso
     update them -- are RETURNED; `head_loss_module` copies them into the BatchNorm module and bumps
     num_batches_tracked.  dpred = d loss / d pred for the backward (empty in eval mode)."""
     for t, nm in ((x, "x"), (bn_w, "bn weight"), (bn_b, "bn bias"), (w_out, "out.weight"), (b_out, "out.bias"), (target, "target")):
-        _cuda_f32(t, nm)
+        _require_cuda(t, nm)
     x = _dense(x)
     S, n, d = x.shape
     C = w_out.shape[0]
     target = target.contiguous()
     if tuple(target.shape) != (n, C):
         raise RuntimeError("chromegcn::head_loss: target must be [n, C] = [%d, %d], got %s" % (n, C, tuple(target.shape)))
-    bn_w, bn_b, w_out, b_out = _dense(bn_w), _dense(bn_b), _dense(w_out), b_out.contiguous()
-    lib = _lib.load()
-    ws_bytes = lib.cgcn_head_workspace_bytes(n, S, d, C)
-    if ws_bytes == 0:
-        raise RuntimeError("chromegcn::head_loss: unsupported shape S=%d n=%d d=%d C=%d" % (S, n, d, C))
     f32 = dict(device=x.device, dtype=torch.float32)
-    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
     probs, loss = torch.empty((n, C), **f32), torch.empty(1, **f32)
     dpred = torch.empty((n, C), **f32) if training else torch.empty(0, **f32)
     save_mean = torch.empty((S, d), **f32) if training else torch.empty(0, **f32)
     save_invstd = torch.empty((S, d), **f32) if training else torch.empty(0, **f32)
-    drop = bool(training) and dropout_p > 0
-    if drop and rng_state is None:
-        raise RuntimeError("chromegcn::head_loss: dropout needs the rng_state tensor")
+    ops._check_rng(rng_state, bool(training) and dropout_p > 0)
     new_rm, new_rv = run_mean.detach().clone().contiguous(), run_var.detach().clone().contiguous()  # the kernel updates these copies
-    _lib.check(lib.cgcn_head_fwd(_lib.stream_ptr(), n, S, d, C, x.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                 new_rm.data_ptr(), new_rv.data_ptr(), None, float(momentum), float(eps),
-                                 1 if training else 0, w_out.data_ptr(), b_out.data_ptr(), target.data_ptr(),
-                                 float(dropout_p), _P(rng_state) if drop else None, probs.data_ptr(), loss.data_ptr(),
-                                 dpred.data_ptr() if training else None, save_mean.data_ptr() if training else None,
-                                 save_invstd.data_ptr() if training else None, ws.data_ptr(), ws_bytes), "cgcn_head_fwd")
+    ops.head_fwd(x, ops._head_params(bn_w, bn_b, w_out, b_out), target, new_rm, new_rv, None, momentum, eps, training,
+                 dropout_p, rng_state, probs, loss, *((dpred, save_mean, save_invstd) if training else (None,) * 3))
     return loss.view(()), probs, save_mean, save_invstd, dpred, new_rm, new_rv
 
 
@@ -243,22 +200,8 @@ def head_loss_backward(dloss: Tensor, x: Tensor, bn_w: Tensor, bn_b: Tensor, w_o
                        save_mean: Tensor, save_invstd: Tensor, dropout_p: float,
                        rng_state: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """(dX, dbn_w, dbn_b, dW_out, db_out) of head_loss for the upstream d loss (a scalar tensor)."""
-    x, bn_w, bn_b, w_out = _dense(x), _dense(bn_w), _dense(bn_b), _dense(w_out)
-    S, n, d = x.shape
-    C = w_out.shape[0]
-    f32 = dict(device=x.device, dtype=torch.float32)
-    lib = _lib.load()
-    ws_bytes = lib.cgcn_head_workspace_bytes(n, S, d, C)
-    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
-    dx, dw_out = torch.empty_like(x), torch.empty_like(w_out)
-    db_out, dbn_w, dbn_b = torch.empty(C, **f32), torch.empty(d, **f32), torch.empty(d, **f32)
-    dl = dloss.contiguous().view(1)
-    _lib.check(lib.cgcn_head_bwd(_lib.stream_ptr(), n, S, d, C, x.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                 save_mean.data_ptr(), save_invstd.data_ptr(), w_out.data_ptr(), dpred.contiguous().data_ptr(),
-                                 dl.data_ptr(), float(dropout_p), _P(rng_state) if dropout_p > 0 else None, dx.data_ptr(),
-                                 dw_out.data_ptr(), db_out.data_ptr(), dbn_w.data_ptr(), dbn_b.data_ptr(), 0,
-                                 ws.data_ptr(), ws_bytes), "cgcn_head_bwd")
-    return dx, dbn_w, dbn_b, dw_out, db_out
+    return ops.head_bwd(dloss, _dense(x), _dense(bn_w), _dense(bn_b), _dense(w_out), dpred, save_mean, save_invstd, dropout_p,
+                        rng_state)
 
 
 @head_loss_backward.register_fake
@@ -278,9 +221,8 @@ def _head_setup(ctx, inputs, output):
 
 
 def _head_backward(ctx, dloss, dprobs, dsm, dsi, ddpred, drm, drv):
-    from .ops import _EVAL_BWD_MSG
     if not ctx.training:
-        raise RuntimeError(_EVAL_BWD_MSG)
+        raise RuntimeError(ops._EVAL_BWD_MSG)
     if dloss is None:
         return (None,) * 13
     x, bn_w, bn_b, w_out, dpred, save_mean, save_invstd, rng_state = ctx.saved_tensors
@@ -300,7 +242,7 @@ def head_logits(x: Tensor, bn_w: Tensor, bn_b: Tensor, run_mean: Tensor, run_var
     layers.ChromeGCN._head takes it only when nothing needs a gradient."""
     for t, nm in ((x, "x"), (bn_w, "bn weight"), (bn_b, "bn bias"), (run_mean, "running_mean"), (run_var, "running_var"),
                   (w_out, "out.weight"), (b_out, "out.bias")):
-        _cuda_f32(t, nm)
+        _require_cuda(t, nm)
     if x.dim() != 3:
         raise RuntimeError("chromegcn::head_logits: x must be [S, n, d], got %s" % (tuple(x.shape),))
     x = _dense(x)
@@ -310,9 +252,8 @@ def head_logits(x: Tensor, bn_w: Tensor, bn_b: Tensor, run_mean: Tensor, run_var
     # the dense copies (if any were needed) stay bound to names until the launch is enqueued: a temporary dropped
     # earlier hands its block back to the caching allocator, and the next copy of the same size would alias it
     bn_w, bn_b, run_mean, run_var, w_out, b_out = map(_dense, (bn_w, bn_b, run_mean, run_var, w_out, b_out))
-    _lib.check(_lib.load().cgcn_head_logits(_lib.stream_ptr(), n, S, d, C, x.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(),
-                                            run_mean.data_ptr(), run_var.data_ptr(), float(eps), w_out.data_ptr(),
-                                            b_out.data_ptr(), logits.data_ptr()), "cgcn_head_logits")
+    _lib.call("cgcn_head_logits", n=n, S=S, d=d, C=C, X=x, bn_w=bn_w, bn_b=bn_b, run_mean=run_mean, run_var=run_var,
+              eps=float(eps), W_out=w_out, b_out=b_out, logits=logits)
     return logits
 
 
@@ -325,8 +266,7 @@ def head_loss_module(x: Tensor, bn: torch.nn.BatchNorm1d, out: torch.nn.Linear, 
                      dropout_p: float, rng_state: Optional[Tensor]):
     """nn.Module-level wrapper of chromegcn::head_loss: applies the returned running statistics to `bn` and counts the
     BatchNorm calls (one per strand) like the reference's two forward calls.  Returns (loss [], probs [n,C])."""
-    if bn.momentum is None:
-        raise RuntimeError("chromegcn_amd: BatchNorm momentum=None (cumulative average) is not supported by the fused head")
+    ops._check_momentum(bn.momentum)
     loss, probs, _sm, _si, _dp, rm, rv = torch.ops.chromegcn.head_loss(
         x, bn.weight, bn.bias, out.weight, out.bias, target, bn.running_mean, bn.running_var, float(bn.momentum),
         float(bn.eps), bool(training), float(dropout_p), rng_state)
@@ -347,12 +287,7 @@ def sgd_step(param: Tensor, grad: Tensor, momentum_buf: Optional[Tensor], lr: fl
              nesterov: bool, grad_scale: float, rng_state: Optional[Tensor]) -> None:
     """torch.optim.SGD semantics on flat fp32 buffers in one launch: d = grad_scale g + wd p; m = mu m + d;
     p -= lr (nesterov ? d + mu m : m).  rng_state (optional): the dropout step counter, advanced by one."""
-    if not (param.is_contiguous() and grad.is_contiguous() and param.numel() == grad.numel()):
-        raise RuntimeError("chromegcn::sgd_step: param and grad must be contiguous and of equal size")
-    lib = _lib.load()
-    _lib.check(lib.cgcn_sgd_step(_lib.stream_ptr(), param.numel(), param.data_ptr(), grad.data_ptr(), _P(momentum_buf),
-                                 float(lr), float(momentum), float(weight_decay), 1 if nesterov else 0, float(grad_scale),
-                                 _P(rng_state)), "cgcn_sgd_step")
+    ops.sgd_step(param, grad, momentum_buf, lr, momentum, weight_decay, nesterov, rng_state, grad_scale)
 
 
 @sgd_step.register_fake
@@ -369,16 +304,7 @@ def adam_step_(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor,
     m += (1 - b1)(d - m); v = b2 v + (1 - b2) d^2; p -= lr / (1 - b1^t) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
     step: float32 per-parameter counts, all advanced by one; ticket: int32 [1], 0 between launches;
     rng_state (optional): the dropout step counter, advanced by one."""
-    n = param.numel()
-    if not all(t.is_contiguous() and t.numel() == n for t in (grad, exp_avg, exp_avg_sq)) or not param.is_contiguous():
-        raise RuntimeError("chromegcn::adam_step_: param, grad, exp_avg and exp_avg_sq must be contiguous and of equal size")
-    if step.dtype != torch.float32 or not step.is_contiguous() or ticket.dtype != torch.int32 or ticket.numel() < 1:
-        raise RuntimeError("chromegcn::adam_step_: step must be contiguous float32, ticket int32 with one element")
-    lib = _lib.load()
-    _lib.check(lib.cgcn_adam_step(_lib.stream_ptr(), n, param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(),
-                                  exp_avg_sq.data_ptr(), step.data_ptr(), step.numel(), ticket.data_ptr(), float(lr),
-                                  float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale),
-                                  _P(rng_state)), "cgcn_adam_step")
+    ops.adam_step(param, grad, exp_avg, exp_avg_sq, step, ticket, lr, beta1, beta2, eps, weight_decay, rng_state, grad_scale)
 
 
 @adam_step_.register_fake
