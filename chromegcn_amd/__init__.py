@@ -1,9 +1,10 @@
 """chromegcn_amd -- MI355X-native gated graph-convolution hot path of ChromeGCN.
 
 Public surface mirrors the reference modules it replaces (see layers.py / graph.py / finetune.py)."""
+from .ablation import label_pair_ablation  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 
 __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_graph", "process_graph",
-           "upload", "as_graph", "FeatureCollector"]
+           "upload", "as_graph", "FeatureCollector", "label_pair_ablation"]

@@ -68,6 +68,15 @@ _HEADER = {
                               "grad_scale:f rng_state"),
     "cgcn_adam_step": (_c_int, "stream count:ll param grad exp_avg exp_avg_sq step n_step:i ticket lr:f beta1:f beta2:f "
                                "eps:f weight_decay:f grad_scale:f rng_state"),
+    "cgcn_ablation_prepare": (_c_int, "stream n:i C:i targets label_bits pos_lists pos_ranks pos_counts"),
+    "cgcn_ablation_workspace_bytes": (_c_sz, "n_inst:i S:i d:i layers:i"),
+    "cgcn_ablation_layer": (_c_int, "stream n:i S:i d:i rowptr col val row_scale X X_inst W b wg cg label_bits C:i pos_list "
+                                    "pos_rank n_pos:i cols n_cols:i X_out removed"),
+    "cgcn_ablation_head": (_c_int, "stream n:i S:i d:i C:i X X_inst bn_w bn_b run_mean run_var eps:f W_out b_out pos_lists "
+                                   "pos_counts label:i n_pos:i cols n_cols:i removed base M"),
+    "cgcn_ablation_mask": (_c_int, "stream n:i C:i rowptr col val row_scale label_bits label_i:i label_j:i val_out "
+                                   "row_scale_out removed"),
+    "cgcn_ablation_reduce": (_c_int, "stream n:i S:i C:i logits pos_lists pos_counts label:i col_label:i removed base M"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

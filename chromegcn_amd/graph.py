@@ -600,3 +600,28 @@ def as_graph(adj, device, n: Optional[int] = None) -> ChromGraph:
     if isinstance(adj, torch.Tensor) and adj.layout == torch.sparse_coo:
         return graph_from_torch_sparse(adj, device)
     raise TypeError("adj must be a ChromGraph, a torch sparse COO tensor or None, got %r" % type(adj))
+
+
+class _MaskedGraph(ChromGraph):
+    """A graph that shares rowptr and the pattern of another (masked_graph): its cgcn_graph_aux is derived from the
+    base graph's, so the host-side detection of _register_aux (band, band plus: host syncs) does not run again."""
+
+    def __post_init__(self):
+        pass
+
+
+def masked_graph(base: ChromGraph, val: torch.Tensor, row_scale: torch.Tensor) -> ChromGraph:
+    """The base graph's pattern with explicit values `val` [nnz] and row scales `row_scale` [n] (the label-pair ablation's
+    composed route rewrites both in place between forwards).  For the EVAL forward only: no transpose is built.  The
+    column array is a copy so that the graph gets an aux record of its own: the base graph's 16-bit index copy, row order
+    and longest row are reused, the band and band-plus routes are off (explicit values that may be zero)."""
+    import weakref
+    col = base.col.clone()
+    ent = _aux_entry(base.col)
+    if ent is not None:
+        c16, order = ent[1][0], ent[1][1]
+        _AUX[col.data_ptr()] = (weakref.ref(col), (c16, order),
+                                GraphAux(None if c16 is None else c16.data_ptr(), None if order is None else order.data_ptr(),
+                                         int(ent[2].max_row_len), 0, None, None, None, None))
+    return _MaskedGraph(n=base.n, nnz=base.nnz, rowptr=base.rowptr, col=col, val=val, row_scale=row_scale,
+                        rowptr_t=base.rowptr, col_t=col, val_t=val, symmetric=False, host=None)

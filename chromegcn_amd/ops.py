@@ -545,3 +545,57 @@ def adam_step(flat_param, flat_grad, exp_avg, exp_avg_sq, step, ticket, lr, beta
     _lib.call("cgcn_adam_step", count=n, param=flat_param, grad=flat_grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq, step=step,
               n_step=step.numel(), ticket=ticket, lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps),
               weight_decay=float(weight_decay), grad_scale=float(grad_scale), rng_state=rng_state)
+
+
+# -- label-pair edge ablation (chromegcn_amd/ablation.py; cgcn_ablation_* in include/chromegcn.h) ----------------------
+def ablation_workspace_bytes(n_inst, S, d, layers):
+    """bytes of the restricted route's workspace for n_inst row instances (0: unsupported shape)"""
+    return _lib.query("cgcn_ablation_workspace_bytes", n_inst=int(n_inst), S=int(S), d=int(d), layers=int(layers))
+
+
+def ablation_prepare(targets):
+    """targets [n, C] (nonzero = positive) -> (label_bits uint32 [n, ceil(C/32)] as int32, pos_lists [C, n],
+    pos_ranks [C, n], pos_counts [C]), all on targets' device"""
+    _require_cuda(targets, "targets")
+    t = targets.contiguous()
+    n, C = t.shape
+    bits = torch.empty((max(n, 1), (C + 31) // 32), device=t.device, dtype=torch.int32)
+    lists = torch.empty((C, max(n, 1)), device=t.device, dtype=torch.int32)
+    ranks = torch.empty_like(lists)
+    counts = torch.empty(C, device=t.device, dtype=torch.int32)
+    _lib.call("cgcn_ablation_prepare", n=n, C=C, targets=t, label_bits=bits, pos_lists=lists, pos_ranks=ranks,
+              pos_counts=counts)
+    return bits, lists, ranks, counts
+
+
+def ablation_layer(graph: ChromGraph, x, x_inst, params, bits, C, pos_list, pos_rank, n_pos, cols, n_cols, x_out, removed):
+    """cgcn_ablation_layer: one gated layer for the (column label, row of P_i) instances; params = _layer_params(...)"""
+    S, n, d = x.shape
+    weight, bias, wg, cg = params
+    _lib.call("cgcn_ablation_layer", n=n, S=S, d=d, rowptr=graph.rowptr, col=graph.col, val=graph.val,
+              row_scale=graph.row_scale, X=x, X_inst=x_inst, W=weight, b=bias, wg=wg, cg=cg, label_bits=bits, C=C,
+              pos_list=pos_list, pos_rank=pos_rank, n_pos=n_pos, cols=cols, n_cols=n_cols, X_out=x_out, removed=removed)
+
+
+def ablation_head(x, x_inst, bn: torch.nn.BatchNorm1d, out: torch.nn.Linear, pos_lists, pos_counts, label, n_pos, cols, n_cols,
+                  removed, base, M, d):
+    """cgcn_ablation_head: label < 0 fills base[C] from x [S, n, d]; label = i fills row i of M from the instances"""
+    S, n = (x.shape[0], x.shape[1]) if x is not None else (2, pos_lists.shape[1])
+    _lib.call("cgcn_ablation_head", n=n, S=S, d=d, C=out.weight.shape[0], X=x, X_inst=x_inst, bn_w=bn.weight, bn_b=bn.bias,
+              run_mean=bn.running_mean, run_var=bn.running_var, eps=float(bn.eps), W_out=out.weight, b_out=out.bias,
+              pos_lists=pos_lists, pos_counts=pos_counts, label=int(label), n_pos=int(n_pos), cols=cols, n_cols=int(n_cols),
+              removed=removed, base=base, M=M)
+
+
+def ablation_mask(graph: ChromGraph, bits, C, label_i, label_j, val_out, rs_out, removed):
+    """cgcn_ablation_mask: the masked values and row scales of pair (label_i, label_j) on graph's pattern"""
+    _lib.call("cgcn_ablation_mask", n=graph.n, C=C, rowptr=graph.rowptr, col=graph.col, val=graph.val,
+              row_scale=graph.row_scale, label_bits=bits, label_i=int(label_i), label_j=int(label_j), val_out=val_out,
+              row_scale_out=rs_out, removed=removed)
+
+
+def ablation_reduce(logits, pos_lists, pos_counts, label, col_label, removed, base, M):
+    """cgcn_ablation_reduce: label < 0 fills base[C] from logits [S, n, C]; label = i writes M[i, col_label]"""
+    S, n, C = logits.shape
+    _lib.call("cgcn_ablation_reduce", n=n, S=S, C=C, logits=logits, pos_lists=pos_lists, pos_counts=pos_counts,
+              label=int(label), col_label=int(col_label), removed=removed, base=base, M=M)

@@ -512,6 +512,75 @@ int cgcn_adam_step(cgcn_stream_t stream, long long count, float *param, const fl
                    float *exp_avg_sq, float *step, int n_step, int32_t *ticket, float lr, float beta1, float beta2,
                    float eps, float weight_decay, float grad_scale, unsigned long long *rng_state);
 
+/*
+ * Label-pair Hi-C edge ablation (scripts/visualize.py:79-119, the TF-TF interaction map; chromegcn_amd/ablation.py).
+ * These six functions are additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing above changes.
+ * For labels (i, j) with positive rows P_c = {u : targets[u, c] != 0}: every stored entry (u, v) with u in P_i and
+ * v in P_j is removed from A-hat (the self loop too), the touched rows renormalised (a row left empty stays zero), and
+ *     M[i * C + j] = (base_i - abl_ij) / base_i,
+ * base_i / abl_ij = mean over P_i of sigmoid((logit_fwd(u, i) + logit_rev(u, i)) / 2) on the full / ablated graph;
+ * exactly 0 when the pair removes no stored entry.  S must be 2 (both strands), d 128 or 256, else
+ * CGCN_ERR_UNSUPPORTED; NULL buffers and negative sizes are CGCN_ERR_BAD_ARG.  Every sum is in a fixed order.
+ *
+ * Set-up, once per call: label_bits uint32 [n][(C + 31) / 32] (bit c of row u: u in P_c); pos_lists int32 [C][n]
+ * (pos_lists[c * n + k]: the k-th row of P_c, ascending); pos_ranks int32 [C][n] (k, or -1 outside P_c);
+ * pos_counts int32 [C] (|P_c|).
+ */
+int cgcn_ablation_prepare(cgcn_stream_t stream, int n, int C, const float *targets, uint32_t *label_bits,
+                          int32_t *pos_lists, int32_t *pos_ranks, int32_t *pos_counts);
+
+/*
+ * Bytes of the restricted route's workspace for n_inst = (column labels of a batch) x |P_i| row instances and
+ * layers in {1, 2}, or 0 when unsupported: [X1: n_inst * S * d fp32][X2: the same, layers == 2][removed: n_inst int32],
+ * each part starting at a 256-byte boundary.
+ */
+size_t cgcn_ablation_workspace_bytes(int n_inst, int S, int d, int layers);
+
+/*
+ * Restricted route, one gated layer for the instances (b, k) of row label i, b < n_cols, k < n_pos = |P_i|: row
+ * u = pos_list[k] under the mask of column label cols[b].  X [S, n, d] is the unablated input of the layer; X_inst
+ * (NULL for layer 1) the instances' ablated input [n_cols][n_pos][S][d], read for the neighbours v in P_i (pos_rank:
+ * the [n] ranks of P_i) and for the row itself.  Kept neighbours only are gathered; then U = H W + b, Z = tanh U,
+ * g = sigmoid(Z . wg + cg), X_out = (1 - g) X_u + g Z in fp32, [n_cols][n_pos][S][d].  removed (may be NULL):
+ * int32 [n_cols][n_pos], the entries each instance's row lost.
+ */
+int cgcn_ablation_layer(cgcn_stream_t stream, int n, int S, int d, const int32_t *rowptr, const int32_t *col,
+                        const float *val, const float *row_scale, const float *X, const float *X_inst, const float *W,
+                        const float *b, const float *wg, const float *cg, const uint32_t *label_bits, int C,
+                        const int32_t *pos_list, const int32_t *pos_rank, int n_pos, const int32_t *cols, int n_cols,
+                        float *X_out, int32_t *removed);
+
+/*
+ * Restricted route, label i's eval head (ReLU, BatchNorm from the running statistics, W_out[i] . y + b_out[i] per
+ * strand, strand mean, sigmoid) and the fixed-order mean over P_i.
+ *   label < 0: base_c for every label c from the unablated last-layer output X [S, n, d] (pos_lists, pos_counts);
+ *              NaN for an empty P_c.
+ *   label = i: M[i * C + cols[b]] for b < n_cols from the instance rows X_inst [n_cols][n_pos][S][d], with base and
+ *              the removed counts of cgcn_ablation_layer.
+ */
+int cgcn_ablation_head(cgcn_stream_t stream, int n, int S, int d, int C, const float *X, const float *X_inst,
+                       const float *bn_w, const float *bn_b, const float *run_mean, const float *run_var, float eps,
+                       const float *W_out, const float *b_out, const int32_t *pos_lists, const int32_t *pos_counts,
+                       int label, int n_pos, const int32_t *cols, int n_cols, const int32_t *removed, float *base,
+                       float *M);
+
+/*
+ * Composed route, the masked graph of pair (label_i, label_j) on the unchanged pattern: val_out[nnz] (val, or 1 when
+ * NULL, with the removed entries 0), row_scale_out[n] (row_scale, or 1 when NULL, for untouched rows; 1 / kept sum for
+ * touched ones, 0 when nothing is kept) and removed (int32 [1]): the number of removed entries.
+ */
+int cgcn_ablation_mask(cgcn_stream_t stream, int n, int C, const int32_t *rowptr, const int32_t *col, const float *val,
+                       const float *row_scale, const uint32_t *label_bits, int label_i, int label_j, float *val_out,
+                       float *row_scale_out, int32_t *removed);
+
+/*
+ * Composed route, mean over P_i of sigmoid of the strand-mean logits [S, n, C]: label < 0 writes base_c for every c;
+ * label = i writes M[i * C + col_label] from base[i] and removed[0] (exactly 0 when it is 0).
+ */
+int cgcn_ablation_reduce(cgcn_stream_t stream, int n, int S, int C, const float *logits, const int32_t *pos_lists,
+                         const int32_t *pos_counts, int label, int col_label, const int32_t *removed, float *base,
+                         float *M);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,274 @@
+"""Label-pair Hi-C edge ablation (chromegcn_amd.ablation, scripts/visualize.py:79-119) against the reference's own method:
+a dense adjacency per pair, masked_fill, row sums with 0 -> 1, and the forwards of both strands, here driven through the
+oracle model in float64."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import chromegcn_amd as C
+from chromegcn_amd import _lib, ops, synth
+from chromegcn_amd.ablation import RestrictedAblation, label_pair_ablation
+from oracle import chromegcn_oracle as O
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+BAD_ARG, UNSUPPORTED = -1, -2
+
+
+def _models(d, c, layers, seed, scale=1.5):
+    torch.manual_seed(seed)
+    orc = O.GatedGCNOracle(d, c, 0.0, layers)
+    with torch.no_grad():
+        for k, p in orc.named_parameters():
+            if "GC" in k and k.endswith("weight"):
+                p.copy_(torch.randn_like(p) / np.sqrt(d) * scale)
+        orc.out.weight.mul_(40.0)
+        orc.batch_norm.running_mean.copy_(torch.randn(d) * 0.1)
+        orc.batch_norm.running_var.copy_(torch.rand(d) + 0.5)
+        orc.batch_norm.weight.copy_(torch.rand(d) + 0.5)
+        orc.batch_norm.bias.copy_(torch.randn(d) * 0.1)
+    model = C.ChromeGCN(d, d, c, 0.0, True, layers)
+    model.load_state_dict(orc.state_dict())
+    return orc.double().eval(), model.to(DEV).eval()
+
+
+def _dense_forward(orc, adj, x):
+    h = x
+    for k in range(1, orc.n_layers + 1):
+        gc, wk = getattr(orc, "GC%d" % k), getattr(orc, "W%d" % k)
+        z = torch.tanh(adj @ (h @ gc.weight) + gc.bias)
+        g = torch.sigmoid(wk(z))
+        h = (1 - g) * h + g * z
+    return orc.out(orc.batch_norm(torch.relu(h)))
+
+
+def reference_matrix(orc, adj, x_f, x_r, targets, rows=None, cols=None):
+    """scripts/visualize.py:79-119 restated in float64 (adj: the dense normalised adjacency)"""
+    c = targets.shape[1]
+    rows = range(c) if rows is None else rows
+    cols = range(c) if cols is None else cols
+    x_f, x_r = x_f.double(), x_r.double()
+    with torch.no_grad():
+        pred = (_dense_forward(orc, adj, x_f) + _dense_forward(orc, adj, x_r)) / 2
+        mat = torch.zeros(c, c, dtype=torch.float64)
+        zero_mat = torch.zeros(adj.shape, dtype=torch.bool)
+        for i in rows:
+            pi = targets[:, i].nonzero().view(-1)
+            base = pred[pi, i].sigmoid().mean()
+            pi_mat = zero_mat.index_fill(0, pi, True)
+            for j in cols:
+                pj = targets[:, j].nonzero().view(-1)
+                if len(pj) > 0 and i != j:
+                    adj2 = adj.masked_fill(pi_mat & zero_mat.index_fill(1, pj, True), 0)
+                    s = adj2.sum(1).view(-1, 1)
+                    s[s == 0] = 1
+                    adj2 = adj2 / s
+                    p = (_dense_forward(orc, adj2, x_f) + _dense_forward(orc, adj2, x_r)) / 2
+                    mat[i, j] = (base - p[pi, i].sigmoid().mean()) / base
+    return mat.numpy()
+
+
+def _dense_adj(adj_type, a, n):
+    return torch.from_numpy(O.normalized_adjacency(adj_type, a, n).toarray()).double()
+
+
+def _case(n, pairs, c, layers, d=128, seed=0, rate=0.2, adj_type="hic", a=None):
+    a = O.random_symmetric_graph(n, pairs, seed) if a is None else a
+    orc, model = _models(d, c, layers, seed)
+    g = torch.Generator().manual_seed(seed)
+    x_f, x_r = torch.randn(n, d, generator=g), torch.randn(n, d, generator=g)
+    targets = (torch.rand(n, c, generator=g) < rate).float()
+    return orc, model, a, x_f, x_r, targets
+
+
+def _run(model, a, x_f, x_r, targets, adj_type="hic", **kw):
+    n = x_f.shape[0]
+    graph = C.process_graph(adj_type, {"c": a}, n, "c", device=DEV)
+    return label_pair_ablation(model, x_f.to(DEV), x_r.to(DEV), graph, targets.to(DEV), **kw).cpu().numpy()
+
+
+def _check(got, want):
+    np.testing.assert_allclose(got, want, atol=1e-5, rtol=1e-4)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+
+
+@pytest.mark.parametrize("n,pairs,c,layers", [(120, 500, 7, 1), (120, 500, 9, 2), (300, 2000, 12, 2), (300, 2000, 10, 1)])
+def test_both_routes_match_float64(n, pairs, c, layers):
+    orc, model, a, x_f, x_r, targets = _case(n, pairs, c, layers, seed=n + c)
+    want = reference_matrix(orc, _dense_adj("hic", a, n), x_f, x_r, targets)
+    assert np.nanmax(np.abs(want)) > 1e-3
+    for route in ("restricted", "composed"):
+        _check(_run(model, a, x_f, x_r, targets, route=route), want)
+
+
+@pytest.mark.parametrize("adj_type", ["hic", "both", "constant", "none"])
+def test_adjacency_types(adj_type):
+    n, c = 120, 8
+    orc, model, a, x_f, x_r, targets = _case(n, 400, c, 2, seed=5, rate=0.25)
+    want = reference_matrix(orc, _dense_adj(adj_type, a, n), x_f, x_r, targets)
+    assert np.nanmax(np.abs(want)) > 1e-3
+    for route in ("restricted", "composed"):
+        _check(_run(model, a, x_f, x_r, targets, adj_type=adj_type, route=route), want)
+
+
+def _special_case():
+    n, c = 200, 10
+    a = O.random_symmetric_graph(n, 600, 11).tolil()
+    hub = 5
+    for v in range(100, 160):                 # a row of many neighbours
+        a[hub, v] = a[v, hub] = 1.0
+    a = a.tocsr()
+    orc, model, _, x_f, x_r, targets = _case(n, 0, c, 2, seed=11, rate=0.3, a=a)
+    nb = set(a[hub].indices.tolist()) | {hub}
+    u0 = 3
+    v0 = next(v for v in range(n) if v != u0 and a[u0, v] == 0 and v not in nb and u0 not in nb)
+    targets[:, 0] = 0                         # empty P_i: NaN row
+    targets[:, 1] = 0                         # empty P_j: zero column
+    targets[:, 2] = 1                         # positive on every row
+    targets[:, 3] = 0
+    targets[hub, 3] = 1                       # P_3 = {hub}
+    keep_one = sorted(nb - {hub})[0]
+    targets[:, 4] = 0
+    targets[sorted(nb - {keep_one}), 4] = 1   # (3, 4): the hub row keeps exactly one of 62 entries (self loop removed)
+    targets[:, 5] = 0
+    targets[sorted(nb), 5] = 1                # (3, 5): the hub row loses every entry (a zero row)
+    targets[:, 6] = 0
+    targets[u0, 6] = 1
+    targets[:, 7] = 0
+    targets[v0, 7] = 1                        # (6, 7) and (7, 6): nothing removed
+    return orc, model, a, x_f, x_r, targets
+
+
+def test_special_cases():
+    orc, model, a, x_f, x_r, targets = _special_case()
+    n, c = targets.shape
+    want = reference_matrix(orc, _dense_adj("hic", a, n), x_f, x_r, targets)
+    for route in ("restricted", "composed"):
+        got = _run(model, a, x_f, x_r, targets, route=route)
+        _check(got, want)
+        assert np.all(np.diag(got) == 0.0)
+        assert np.all(got[:, 1] == 0.0)
+        assert np.all(np.isnan(got[0, [j for j in range(c) if j not in (0, 1)]])) and got[0, 0] == 0 and got[0, 1] == 0
+        assert got[6, 7] == 0.0 and got[7, 6] == 0.0
+        assert abs(got[3, 4]) > 1e-4 and abs(got[3, 5]) > 1e-4
+        assert np.all(np.isfinite(got[2]))
+
+
+def test_rows_and_cols_subsets():
+    n, c = 300, 103
+    _orc, model, a, x_f, x_r, targets = _case(n, 2000, c, 2, seed=3, rate=0.05)
+    full = _run(model, a, x_f, x_r, targets)
+    sub = _run(model, a, x_f, x_r, targets, rows=range(10, 80), cols=range(10, 80))
+    block = np.zeros_like(full)
+    block[10:80, 10:80] = full[10:80, 10:80]
+    assert np.array_equal(np.nan_to_num(sub, nan=7.0), np.nan_to_num(block, nan=7.0))
+    small = _run(model, a, x_f, x_r, targets, rows=[3, 17], cols=[17, 1, 50], route="composed")
+    want = reference_matrix(_orc, _dense_adj("hic", a, n), x_f, x_r, targets, rows=[3, 17], cols=[17, 1, 50])
+    _check(small, want)
+    assert np.all(small[[r for r in range(c) if r not in (3, 17)]] == 0)
+
+
+def test_small_workspace_batches_give_the_same_bits():
+    _orc, model, a, x_f, x_r, targets = _case(300, 2000, 12, 2, seed=8)
+    big = _run(model, a, x_f, x_r, targets)
+    tiny = _run(model, a, x_f, x_r, targets, max_workspace_bytes=1)   # one column label per batch
+    assert np.array_equal(np.nan_to_num(big, nan=7.0), np.nan_to_num(tiny, nan=7.0))
+
+
+def test_chr21_size_routes_agree_and_are_deterministic():
+    feats, hic = synth.synthetic_chromosome("chr21")
+    n, d, c = feats["forward"].shape[0], 128, feats["target"].shape[1]
+    _orc, model = _models(d, c, 2, 21)
+    graph = C.process_graph("hic", {"chr21": hic}, n, "chr21", device=DEV)
+    x_f, x_r, tg = feats["forward"].to(DEV), feats["backward"].to(DEV), feats["target"].to(DEV)
+    full = label_pair_ablation(model, x_f, x_r, graph, tg)
+    again = label_pair_ablation(model, x_f, x_r, graph, tg)
+    assert torch.equal(torch.nan_to_num(full, nan=7.0), torch.nan_to_num(again, nan=7.0))
+    counts = (tg != 0).sum(0).cpu()
+    defined = (counts > 0).view(-1, 1) & (counts > 0).view(1, -1) & ~torch.eye(c, dtype=torch.bool)
+    assert bool(torch.isfinite(full.cpu()[defined]).all())
+    blk = range(16)
+    comp = label_pair_ablation(model, x_f, x_r, graph, tg, rows=blk, cols=blk, route="composed").cpu().numpy()
+    np.testing.assert_allclose(full.cpu().numpy()[:16, :16], comp[:16, :16], atol=1e-5, rtol=0)
+    assert np.abs(comp).max() > 0
+
+
+@pytest.mark.parametrize("d,layers,route", [(128, 3, "auto"), (256, 4, "auto"), (256, 2, "restricted"), (256, 2, "composed")])
+def test_other_model_shapes(d, layers, route):
+    n, c = 120, 7
+    orc, model, a, x_f, x_r, targets = _case(n, 500, c, layers, d=d, seed=d + layers, rate=0.25)
+    want = reference_matrix(orc, _dense_adj("hic", a, n), x_f, x_r, targets)
+    assert np.nanmax(np.abs(want)) > 1e-3
+    _check(_run(model, a, x_f, x_r, targets, route=route), want)
+
+
+def test_hub_graph():
+    n, c = 300, 8
+    a = synth.contact_graph(n, 2000, 4, "hub")
+    orc, model, _, x_f, x_r, targets = _case(n, 0, c, 2, seed=4, rate=0.2, a=a)
+    want = reference_matrix(orc, _dense_adj("hic", a, n), x_f, x_r, targets)
+    for route in ("restricted", "composed"):
+        _check(_run(model, a, x_f, x_r, targets, route=route), want)
+
+
+def test_one_row_label_captured_and_replayed():
+    n, c = 300, 9
+    _orc, model, a, x_f, x_r, targets = _case(n, 2000, c, 2, seed=6, rate=0.2)
+    graph = C.process_graph("hic", {"c": a}, n, "c", device=DEV)
+    x = torch.stack([x_f, x_r]).to(DEV)
+    tg = targets.to(DEV)
+    with torch.no_grad():
+        bits, lists, ranks, counts = ops.ablation_prepare(tg)
+        ra = RestrictedAblation(model, x, graph, bits, lists, ranks, counts)
+        i = 2
+        n_pos = int(counts[i].item())
+        cols = torch.tensor([j for j in range(c) if j != i], dtype=torch.int32, device=DEV)
+        ws = ra.workspace(n_pos * cols.numel())
+        eager = torch.zeros(c, c, device=DEV)
+        ra.run_row(i, n_pos, cols, cols.numel(), ws, eager)
+        M = torch.zeros(c, c, device=DEV)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                ra.run_row(i, n_pos, cols, cols.numel(), ws, M)
+        torch.cuda.current_stream().wait_stream(s)
+        for _ in range(2):
+            M.zero_()
+            g.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(M, eager)
+    assert eager.abs().max() > 0
+    want = torch.from_numpy(_run(model, a, x_f, x_r, targets, rows=[i])).to(DEV)
+    assert torch.equal(eager, want)
+
+
+def test_errors():
+    _orc, model, a, x_f, x_r, targets = _case(120, 500, 7, 2, seed=1)
+    graph = C.process_graph("hic", {"c": a}, 120, "c", device=DEV)
+    xf, xr, tg = x_f.to(DEV), x_r.to(DEV), targets.to(DEV)
+    model.train()
+    with pytest.raises(RuntimeError, match="eval"):
+        label_pair_ablation(model, xf, xr, graph, tg)
+    model.eval()
+    with pytest.raises(ValueError, match="graph"):
+        label_pair_ablation(model, xf, xr, None, tg)
+    _o3, m3 = _models(128, 7, 3, 1)
+    with pytest.raises(ValueError, match="restricted"):
+        label_pair_ablation(m3, xf, xr, graph, tg, route="restricted")
+    t = torch.zeros(4096, device=DEV)
+    args = dict(n=120, S=2, d=128, rowptr=graph.rowptr, col=graph.col, val=None, row_scale=graph.row_scale, X=t, X_inst=None,
+                W=t, b=t, wg=t, cg=t, label_bits=t, C=7, pos_list=t, pos_rank=t, n_pos=4, cols=t, n_cols=3, X_out=t,
+                removed=None)
+    assert _lib.query("cgcn_ablation_layer", **dict(args, W=None)) == BAD_ARG
+    assert _lib.query("cgcn_ablation_layer", **dict(args, d=64)) == UNSUPPORTED
+    assert _lib.query("cgcn_ablation_layer", **dict(args, S=1)) == UNSUPPORTED
+    assert _lib.query("cgcn_ablation_head", n=120, S=2, d=200, C=7, X=t, X_inst=None, bn_w=t, bn_b=t, run_mean=t, run_var=t,
+                      eps=1e-5, W_out=t, b_out=t, pos_lists=t, pos_counts=t, label=-1, n_pos=0, cols=None, n_cols=0,
+                      removed=None, base=t, M=None) == UNSUPPORTED
+    assert _lib.query("cgcn_ablation_mask", n=120, C=7, rowptr=graph.rowptr, col=graph.col, val=None, row_scale=None,
+                      label_bits=t, label_i=0, label_j=1, val_out=None, row_scale_out=t, removed=t) == BAD_ARG
+    assert ctypes.c_size_t(_lib.query("cgcn_ablation_workspace_bytes", n_inst=10, S=2, d=64, layers=2)).value == 0
