@@ -77,6 +77,10 @@ _HEADER = {
     "cgcn_ablation_mask": (_c_int, "stream n:i C:i rowptr col val row_scale label_bits label_i:i label_j:i val_out "
                                    "row_scale_out removed"),
     "cgcn_ablation_reduce": (_c_int, "stream n:i S:i C:i logits pos_lists pos_counts label:i col_label:i removed base M"),
+    "cgcn_hic_workspace_bytes": (_c_sz, "M:ll N:i capacity:ll K:ll"),
+    "cgcn_hic_count": (_c_int, "stream M:ll pos1 pos2 window_start N:i workspace workspace_bytes:z n_survivors"),
+    "cgcn_hic_build": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_start N:i K:ll capacity:ll "
+                               "workspace workspace_bytes:z rowptr_out col_out nnz_out n_survivors"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -1,0 +1,379 @@
+// chromegcn_amd/csrc/cgcn_hic.hip
+//
+// The top-K Hi-C contact graph from raw contact records on the device: what the reference's
+// data/7create_graph_new.py does with a Python dict and a full sorted() -- get_contact_edge_pairs (:67-91),
+// get_top_contact_locs (:93-104), create_adj_mat (:108-120) -- for any edge budget and any normalisation vector.
+//
+//   k_hic_filter<false>  one streaming pass over the M records (pos1, pos2 only): survivors per 2048-record tile
+//   k_hic_scan           exclusive scan of the tile counts (one workgroup); the survivor count S stays on the device
+//   k_hic_filter<true>   the same pass again, now writing the survivors IN FILE ORDER: the sort key of the fp64 value
+//                        count / (nv[pos1 / res] * nv[pos2 / res]) and its window ranks (i, j)
+//   rocprim::radix_sort_keys    a copy of the keys, ascending (= values descending)
+//   k_hic_threshold      t = the K-th sorted key and how many survivors with key t are taken: K - #{keys < t}
+//   k_hic_take<false> / k_hic_scan / k_hic_take<true>   a survivor is taken iff key < t, or key == t and fewer than that many
+//                        survivors with key t precede it IN FILE ORDER (an ordered prefix count): the reference's stable
+//                        sorted(reverse=True) cut at K, without ordering the survivors; the taken ones leave as edge keys
+//                        (i << b | j) and (j << b | i), b = bits of N, the others as padding
+//   rocprim::radix_sort_keys    the 2 b low bits of the edge keys (the padding sorts last)
+//   k_hic_unique<false> / k_hic_scan / k_hic_unique<true>   duplicates dropped ((a, b) and (b, a) records merge), columns,
+//                        row pointers and nnz
+// Integer keys, integer counts and ordered writes only: the result does not depend on scheduling.  Nothing is allocated,
+// nothing synchronises, nothing is retained; every size the host cannot know (S, min(K, S), nnz) is read from device
+// memory by the kernels, whose grids are sized for the caller's bounds (capacity, K).
+#include <cstring>  // rocprim 4.x headers use memset without including it
+#include <rocprim/rocprim.hpp>
+
+#include "cgcn_common.hpp"
+
+#define HIC_THREADS 256
+#define HIC_STEPS 8                                    // records per lane of the filter pass
+#define HIC_TILE (HIC_THREADS * HIC_STEPS)             // records per workgroup: 4 waves x 8 steps x 64 lanes
+#define HIC_PAD_KEY 0xFFFFFFFFFFFFFFFFull              // sorts behind every real key in both sorts
+
+typedef unsigned long long u64;
+
+// rank of x in the strictly increasing ws[0..N), or -1.  Branch-free descent to the last element <= x.
+__device__ __forceinline__ int hic_rank(const int* __restrict__ ws, int N, int x) {
+  int lo = 0, n = N;
+  while (n > 1) {
+    const int half = n >> 1;
+    lo = ws[lo + half] <= x ? lo + half : lo;
+    n -= half;
+  }
+  return (N > 0 && ws[lo] == x) ? lo : -1;
+}
+
+// The order-preserving image of an fp64 value, complemented: an ASCENDING sort of these keys lists the values in
+// descending order.  -0 is folded onto +0 (the reference compares numbers).
+__device__ __forceinline__ u64 hic_value_key(double v) {
+  u64 u = (u64)__double_as_longlong(v == 0.0 ? 0.0 : v);
+  u ^= (u >> 63) ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull;
+  return ~u;
+}
+
+// nv[] of get_normalization_values (:62-63): NaN and 0 become +inf.  A bin outside the vector (the reference raises
+// IndexError) reads as +inf too: never out of bounds.
+__device__ __forceinline__ double hic_norm_at(const double* __restrict__ norm, long long n_bins, int pos, int res) {
+  const long long b = pos / res;
+  if (b < 0 || b >= n_bins) return __longlong_as_double(0x7FF0000000000000ll);
+  const double x = norm[b];
+  return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
+}
+
+// Wave w of a workgroup owns the 512 consecutive records [tile + 512 w, tile + 512 (w + 1)) and walks them in 8 steps of
+// 64 (coalesced); a survivor's place is (tile offset) + (survivors of the waves before) + (of the steps before) + (of the
+// lanes before): file order.  WRITE = false only counts the tile's survivors.
+template <bool WRITE>
+__global__ __launch_bounds__(HIC_THREADS) void k_hic_filter(long long M, const int* __restrict__ pos1, const int* __restrict__ pos2,
+                                                            const double* __restrict__ count, const double* __restrict__ norm,
+                                                            long long n_bins, int res, const int* __restrict__ ws, int N,
+                                                            int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
+                                                            long long capacity, u64* __restrict__ keys, int2* __restrict__ ij) {
+  __shared__ int wave_tot[HIC_THREADS / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const long long base = (long long)blockIdx.x * HIC_TILE + (long long)w * (HIC_STEPS * WAVE);
+  int ri[HIC_STEPS], rj[HIC_STEPS];
+  int before[HIC_STEPS];   // survivors of this wave in earlier steps and earlier lanes of the step
+  int run = 0;
+#pragma unroll
+  for (int s = 0; s < HIC_STEPS; ++s) {
+    const long long r = base + s * WAVE + lane;
+    int i = -1, j = -1;
+    if (r < M) {
+      const int a = pos1[r], b = pos2[r];
+      if (a != b) {
+        i = hic_rank(ws, N, a);
+        if (i >= 0) j = hic_rank(ws, N, b);
+      }
+    }
+    const bool hit = i >= 0 && j >= 0;
+    const u64 m = __ballot(hit);
+    before[s] = run + __popcll(m & ((1ull << lane) - 1ull));
+    run += __popcll(m);
+    ri[s] = hit ? i : -1;
+    rj[s] = j;
+  }
+  if (lane == 0) wave_tot[w] = run;
+  __syncthreads();
+  if (!WRITE) {
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    return;
+  }
+  long long off = tile_off[blockIdx.x];
+  for (int k = 0; k < w; ++k) off += wave_tot[k];
+#pragma unroll
+  for (int s = 0; s < HIC_STEPS; ++s) {
+    if (ri[s] < 0) continue;
+    const long long o = off + before[s];
+    if (o >= capacity) continue;   // the caller's capacity is below the survivor count: the build reports it, nothing is overrun
+    const long long r = base + s * WAVE + lane;
+    double v = count[r];
+    if (norm) {
+      const double d = hic_norm_at(norm, n_bins, pos1[r], res) * hic_norm_at(norm, n_bins, pos2[r], res);
+      v = v / d;   // one multiply, one divide, both correctly rounded (:84)
+    }
+    keys[o] = hic_value_key(v);
+    ij[o] = make_int2(ri[s], rj[s]);
+  }
+}
+
+// exclusive scan of counts[0..nb) into off[0..nb); the total goes to total64[0] and, clamped to `clamp`, to total32[0]
+// (either may be NULL).  One workgroup of 1024 threads.
+__global__ __launch_bounds__(1024) void k_hic_scan(int nb, const int* __restrict__ counts, long long* __restrict__ off,
+                                                   long long* __restrict__ total64, int* __restrict__ total32, long long clamp) {
+  __shared__ long long part[1024];
+  const int t = threadIdx.x;
+  const int per = (nb + 1023) / 1024;
+  const int i0 = min(nb, t * per), i1 = min(nb, i0 + per);
+  long long s = 0;
+  for (int i = i0; i < i1; ++i) s += counts[i];
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const long long v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  long long run = t ? part[t - 1] : 0;
+  for (int i = i0; i < i1; ++i) {
+    off[i] = run;
+    run += counts[i];
+  }
+  if (t == 1023) {
+    const long long tot = part[1023];
+    if (total64) total64[0] = tot;
+    if (total32) total32[0] = (int)(tot < clamp ? tot : clamp);
+  }
+}
+
+// slots [S, capacity) of the sort input, when the caller's capacity exceeds the survivor count
+__global__ __launch_bounds__(256) void k_hic_pad(const long long* __restrict__ n_surv, long long capacity, u64* __restrict__ keys) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o < capacity && o >= n_surv[0]) keys[o] = HIC_PAD_KEY;
+}
+
+// From the sorted keys: taken[0] = kt = min(K, S, capacity); thr[0] = t, the kt-th key (the K-th largest value);
+// thr[1] = kt - #{keys < t}, the number of survivors with value == t that are taken (the first ones in file order).
+// kt = 0: t = 0 and nothing is below it.  One thread; the count is a binary search.
+__global__ void k_hic_threshold(long long K, long long capacity, const long long* __restrict__ n_surv, const u64* __restrict__ sorted,
+                                long long* __restrict__ taken, u64* __restrict__ thr) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const long long S = min(n_surv[0], capacity);
+  const long long kt = min(K, S);
+  taken[0] = kt;
+  if (kt == 0) { thr[0] = 0; thr[1] = 0; return; }
+  const u64 t = sorted[kt - 1];
+  long long lo = 0, hi = kt - 1;   // first index with sorted[index] == t
+  while (lo < hi) {
+    const long long mid = (lo + hi) >> 1;
+    if (sorted[mid] < t) lo = mid + 1; else hi = mid;
+  }
+  thr[0] = t;
+  thr[1] = (u64)(kt - lo);
+}
+
+// Survivor o (file order) is taken iff its key is below t (its value above the threshold) or equals t and fewer than thr[1]
+// survivors with key t precede it.  WRITE = false counts the keys equal to t per 256-survivor tile; WRITE = true writes the
+// two edge keys of every taken survivor at slots 2 o and 2 o + 1 and pads the others (the edge sort moves the pads behind).
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_hic_take(const long long* __restrict__ n_surv, long long capacity, const u64* __restrict__ keys,
+                                                  const u64* __restrict__ thr, int* __restrict__ tile_counts,
+                                                  const long long* __restrict__ tile_off, const int2* __restrict__ ij, int b,
+                                                  u64* __restrict__ edges) {
+  __shared__ int wave_tot[4];
+  const long long S = min(n_surv[0], capacity);
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const u64 t = thr[0];
+  const u64 key = o < S ? keys[o] : HIC_PAD_KEY;
+  const bool eq = o < S && key == t;
+  const u64 m = __ballot(eq);
+  if (lane == 0) wave_tot[w] = __popcll(m);
+  __syncthreads();
+  if (!WRITE) {
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    return;
+  }
+  if (o >= capacity) return;
+  long long rank = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+  for (int k = 0; k < w; ++k) rank += wave_tot[k];
+  u64 e0 = HIC_PAD_KEY, e1 = HIC_PAD_KEY;
+  if (o < S && (key < t || (eq && (u64)rank < thr[1]))) {
+    const int2 p = ij[o];
+    e0 = ((u64)(unsigned)p.x << b) | (u64)(unsigned)p.y;
+    e1 = ((u64)(unsigned)p.y << b) | (u64)(unsigned)p.x;
+  }
+  edges[2 * o] = e0;
+  edges[2 * o + 1] = e1;
+}
+
+// sorted edge keys [0, 2 taken): element p starts a new (row, column) pair iff it differs from p - 1.  WRITE = false counts
+// the starts per 256-element tile; WRITE = true writes the columns and the row pointers: the start at output place q of
+// row i closes every row after the previous pair's up to i (rowptr[r] = q), the last element closes the rest with nnz.
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_hic_unique(const long long* __restrict__ taken, const u64* __restrict__ edges, int b, int N,
+                                                    int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
+                                                    const int* __restrict__ nnz, int* __restrict__ rowptr, int* __restrict__ col) {
+  __shared__ int wave_tot[4];
+  const long long n = 2 * taken[0];
+  const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  u64 e = 0, prev = 0;
+  bool head = false;
+  if (p < n) {
+    e = edges[p];
+    prev = p > 0 ? edges[p - 1] : 0;
+    head = p == 0 || e != prev;
+  }
+  const u64 m = __ballot(head);
+  if (lane == 0) wave_tot[w] = __popcll(m);
+  __syncthreads();
+  if (!WRITE) {
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    return;
+  }
+  if (p >= n) return;
+  const int row = (int)(e >> b);
+  if (head) {
+    long long q = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < w; ++k) q += wave_tot[k];
+    col[q] = (int)(e & ((1ull << b) - 1ull));
+    const int prow = p > 0 ? (int)(prev >> b) : -1;
+    for (int r = prow + 1; r <= row; ++r) rowptr[r] = (int)q;
+  }
+  if (p == n - 1) {
+    const int total = nnz[0];
+    for (int r = row + 1; r <= N; ++r) rowptr[r] = total;
+  }
+}
+
+static inline size_t hic_al(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int hic_bits(int N) {
+  int b = 1;
+  while (b < 31 && (1ll << b) < (long long)N) ++b;
+  return b;
+}
+static inline long long hic_tiles(long long n, int tile) { const long long k = (n + tile - 1) / tile; return k < 1 ? 1 : k; }
+
+struct HicPlan {
+  long long cap, half, E;      // survivor slots, the most records taken = min(K, capacity), edge slots = 2 cap
+  long long tilesM, tilesS, tilesE;
+  int b;
+  size_t temp, o_counts, o_off, o_taken, o_thr, o_keyA, o_keyB, o_ij, o_edgeA, o_edgeB, o_temp, total;
+};
+
+static bool hic_plan(long long M, int N, long long capacity, long long K, HicPlan* p) {
+  if (M < 0 || N < 0 || capacity < 0 || K < 0) return false;
+  if (capacity >= 2147483647ll || 2 * K >= 2147483648ll || M / HIC_TILE >= 2147483647ll) return false;
+  p->cap = capacity < 1 ? 1 : capacity;
+  p->half = K < capacity ? K : capacity;
+  p->E = 2 * p->cap;
+  p->tilesM = hic_tiles(M, HIC_TILE);
+  p->tilesS = hic_tiles(p->cap, 256);
+  p->tilesE = hic_tiles(p->E, 256);
+  p->b = hic_bits(N);
+  size_t t1 = 0, t2 = 0;
+  (void)rocprim::radix_sort_keys(nullptr, t1, (const u64*)nullptr, (u64*)nullptr, (size_t)p->cap, 0u, 64u);
+  (void)rocprim::radix_sort_keys(nullptr, t2, (const u64*)nullptr, (u64*)nullptr, (size_t)p->E, 0u, (unsigned)(2 * p->b));
+  p->temp = t1 > t2 ? t1 : t2;
+  const long long tiles = p->tilesM > p->tilesE ? p->tilesM : p->tilesE;
+  const size_t e = (size_t)p->E;
+  size_t o = 0;
+  p->o_counts = o; o += hic_al((size_t)tiles * 4);
+  p->o_off = o; o += hic_al((size_t)tiles * 8);
+  p->o_taken = o; o += 256;
+  p->o_thr = o; o += 256;
+  p->o_keyA = o; o += hic_al((size_t)p->cap * 8);
+  p->o_keyB = o; o += hic_al((size_t)p->cap * 8);
+  p->o_ij = o; o += hic_al((size_t)p->cap * 8);
+  p->o_edgeA = o; o += hic_al(e * 8);
+  p->o_edgeB = o; o += hic_al(e * 8);
+  p->o_temp = o; o += hic_al(p->temp);
+  p->total = o + 256;   // the base is rounded up to 256 bytes
+  return true;
+}
+
+extern "C" {
+
+size_t cgcn_hic_workspace_bytes(long long M, int N, long long capacity, long long K) {
+  HicPlan p;
+  return hic_plan(M, N, capacity, K, &p) ? p.total : 0;
+}
+
+int cgcn_hic_count(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                   int N, void* workspace, size_t workspace_bytes, long long* n_survivors) {
+  if (M < 0 || N < 0 || !n_survivors) return CGCN_ERR_BAD_ARG;
+  if (M > 0 && (!pos1 || !pos2 || !workspace)) return CGCN_ERR_BAD_ARG;
+  if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
+  HicPlan p;
+  if (!hic_plan(M, N, 0, 0, &p)) return CGCN_ERR_UNSUPPORTED;
+  if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
+  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  int* counts = (int*)(w + p.o_counts);
+  long long* off = (long long*)(w + p.o_off);
+  hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, (const double*)nullptr,
+                     (const double*)nullptr, 0ll, 1, window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr,
+                     (int2*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
+  return launch_status();
+}
+
+int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                   const double* norm, long long n_bins, int resolution_bp, const int32_t* window_start, int N, long long K,
+                   long long capacity, void* workspace, size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out,
+                   int32_t* nnz_out, long long* n_survivors) {
+  if (M < 0 || N < 0 || K < 0 || capacity < 0 || n_bins < 0 || !rowptr_out || !nnz_out || !n_survivors || !workspace)
+    return CGCN_ERR_BAD_ARG;
+  if (M > 0 && (!pos1 || !pos2 || !count)) return CGCN_ERR_BAD_ARG;
+  if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
+  if (norm && (resolution_bp < 1 || n_bins < 1)) return CGCN_ERR_BAD_ARG;
+  HicPlan p;
+  if (!hic_plan(M, N, capacity, K, &p)) return CGCN_ERR_UNSUPPORTED;
+  if (p.half > 0 && !col_out) return CGCN_ERR_BAD_ARG;
+  if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  int* counts = (int*)(w + p.o_counts);
+  long long* off = (long long*)(w + p.o_off);
+  long long* taken = (long long*)(w + p.o_taken);
+  u64* thr = (u64*)(w + p.o_thr);
+  u64* keyA = (u64*)(w + p.o_keyA);
+  u64* keyB = (u64*)(w + p.o_keyB);
+  int2* ij = (int2*)(w + p.o_ij);
+  u64* edgeA = (u64*)(w + p.o_edgeA);
+  u64* edgeB = (u64*)(w + p.o_edgeB);
+  if (hipMemsetAsync(rowptr_out, 0, ((size_t)N + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  if (hipMemsetAsync(nnz_out, 0, 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
+  const int res = norm ? resolution_bp : 1;
+  hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
+                     window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr, (int2*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
+  if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
+  hipLaunchKernelGGL(k_hic_filter<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
+                     window_start, N, (int*)nullptr, (const long long*)off, capacity, keyA, ij);
+  hipLaunchKernelGGL(k_hic_pad, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity, keyA);
+  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), p.temp, (const u64*)keyA, keyB, (size_t)capacity, 0u, 64u, st) != hipSuccess)
+    return CGCN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_hic_threshold, dim3(1), dim3(64), 0, st, K, capacity, (const long long*)n_survivors, (const u64*)keyB, taken, thr);
+  hipLaunchKernelGGL(k_hic_take<false>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
+                     (const u64*)keyA, (const u64*)thr, counts, (const long long*)nullptr, (const int2*)nullptr, p.b, (u64*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesS, (const int*)counts, off, (long long*)nullptr, (int*)nullptr, 0ll);
+  hipLaunchKernelGGL(k_hic_take<true>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
+                     (const u64*)keyA, (const u64*)thr, (int*)nullptr, (const long long*)off, (const int2*)ij, p.b, edgeA);
+  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), p.temp, (const u64*)edgeA, edgeB, (size_t)p.E, 0u, (unsigned)(2 * p.b), st) !=
+      hipSuccess)
+    return CGCN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_hic_unique<false>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
+                     counts, (const long long*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesE, (const int*)counts, off, (long long*)nullptr, nnz_out,
+                     2147483647ll);
+  hipLaunchKernelGGL(k_hic_unique<true>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
+                     (int*)nullptr, (const long long*)off, (const int*)nnz_out, rowptr_out, col_out);
+  return launch_status();
+}
+
+}  // extern "C"

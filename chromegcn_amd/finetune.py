@@ -266,8 +266,13 @@ class GCNStage:
             return
         pend = self._pending.pop(name, None)
         materialising = pend is not None and pend[0] is feats and pend[1] is hic   # same data as registered
-        h = G.normalize_graph(self.adj_type, hic, n)
-        g = G.upload(h, self.device)
+        if isinstance(hic, G.ChromGraph):   # already normalised for this stage's adj_type on the device (chromegcn_amd.hic)
+            if hic.n != n or hic.device.type != self.device.type:
+                raise ValueError("graph of %s has %d windows on %s; the features have %d rows on %s"
+                                 % (name, hic.n, hic.device, n, self.device))
+            g = hic
+        else:
+            g = G.upload(G.normalize_graph(self.adj_type, hic, n), self.device)
         x = torch.stack([feats["forward"], feats["backward"]]).to(self.device, torch.float32).contiguous()
         t = feats["target"].to(self.device, torch.float32).contiguous()
         known = self._meta.get(name)

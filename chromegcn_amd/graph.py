@@ -353,13 +353,11 @@ def normalize_graph_device(adj_type: str, hic: Optional[sp.spmatrix], n: int, de
     """process_graph on the GPU (cgcn_graph_count / cgcn_graph_fill): the raw Hi-C CSR is uploaded once
     (int32 + fp32, canonical form) and A-hat, 1/rowsum and the symmetry flag are produced on the device.
     Same result as upload(normalize_graph(...)) -- tests/test_gpu_graph.py."""
-    from . import _lib
     if adj_type not in ADJ_CODES:
         raise ValueError("unsupported adj_type %r (reference: UnboundLocalError)" % (adj_type,))
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("normalize_graph_device needs a GPU; use normalize_graph + upload on the host")
-    code = ADJ_CODES[adj_type]
     rp = ci = va = None
     if adj_type in ("hic", "both"):
         if hic is None:
@@ -375,6 +373,24 @@ def normalize_graph_device(adj_type: str, hic: Optional[sp.spmatrix], n: int, de
         ci = torch.from_numpy(a.indices.astype(np.int32)).to(dev)
         if not np.all(a.data == 1.0):
             va = torch.from_numpy(a.data.astype(np.float32)).to(dev)
+    return normalize_device_csr(adj_type, n, rp, ci, va, dev)
+
+
+def normalize_device_csr(adj_type: str, n: int, rp: Optional[torch.Tensor], ci: Optional[torch.Tensor],
+                         va: Optional[torch.Tensor], device="cuda") -> ChromGraph:
+    """The device half of normalize_graph_device for a raw Hi-C matrix that is ALREADY a canonical CSR on the device
+    (int32 rowptr [n + 1] and sorted columns, fp32 values or None = ones; col may be longer than rowptr[n]): what
+    chromegcn_amd.hic builds, so that no matrix visits the host.  rp / ci / va are ignored for 'constant' and 'none'."""
+    from . import _lib
+    if adj_type not in ADJ_CODES:
+        raise ValueError("unsupported adj_type %r (reference: UnboundLocalError)" % (adj_type,))
+    dev = torch.device(device)
+    code = ADJ_CODES[adj_type]
+    if adj_type in ("hic", "both"):
+        if rp is None or rp.numel() != n + 1:
+            raise ValueError("adj_type %r needs a Hi-C CSR of %d rows" % (adj_type, n))
+    else:
+        rp = ci = va = None
     with torch.cuda.device(dev):
         counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)

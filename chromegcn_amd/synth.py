@@ -94,6 +94,47 @@ def contact_graph(n: int, pairs: int, seed: int, hic_like=False) -> sp.csr_matri
     return sp.csr_matrix(a, dtype=np.float64)
 
 
+def raw_contacts(chrom: str, seed: int = None, resolution_bp: int = 1000, background_per_bin: float = 80.0,
+                 peak_pairs_per_window: float = 120.0) -> dict:
+    """Seeded synthetic contact records at a real chromosome's shape, in the form chromegcn_amd.hic consumes: what a
+    `RAWobserved` file plus a norm file plus the window list of data/7create_graph_new.py hold.
+      * every `resolution_bp` bin of the chromosome exists; a PEAK_FRACTION share of them (chrom_nodes) are windows with
+        peaks: `window_start`, strictly increasing;
+      * records sorted by (pos1, pos2), pos1 <= pos2, each ordered pair once, like the real files; the distance of a pair
+        follows the truncated 1/k law of contact_graph(hic_like=True);
+      * `background_per_bin` x bins records between any two bins (1.4 % of them survive the window filter) and
+        `peak_pairs_per_window` x windows drawn with BOTH ends on windows, so that the survivors outnumber the 250 000
+        pairs of the default budget and the top-K cut binds;
+      * integer counts that fall with distance (1 + Poisson: heavy ties, as in raw counts); a norm vector around 1 with
+        2 % NaN and 1 % zero entries.
+    Returns {'pos1', 'pos2' int32 [M], 'count' float64 [M], 'norm' float64 [n_bins], 'window_start' int32 [N],
+    'resolution_bp'}."""
+    rng = np.random.RandomState(chrom_seed(chrom) + 7000 if seed is None else seed)
+    n_bins = -(-HG19_LEN[chrom] // resolution_bp)
+    n = min(chrom_nodes(chrom), n_bins)
+    windows = np.sort(rng.choice(n_bins, n, replace=False)).astype(np.int64)
+
+    def pairs(count, size):   # (a, b), a < b < size, b - a from the truncated 1/k law
+        dist = np.clip(np.floor(np.exp(rng.random_sample(count) * math.log(max(2, size - 1)))).astype(np.int64), 1, size - 1)
+        a = (rng.random_sample(count) * (size - dist)).astype(np.int64)
+        return a, a + dist
+
+    a0, b0 = pairs(int(background_per_bin * n_bins), n_bins)
+    a1, b1 = pairs(int(peak_pairs_per_window * n), n)
+    diag = rng.randint(0, n_bins, n_bins // 8)   # pos1 == pos2 records: real files have the diagonal, the rule drops it
+    b1p = np.concatenate([a0, windows[a1], diag])
+    b2p = np.concatenate([b0, windows[b1], diag])
+    key = np.unique(b1p * n_bins + b2p)   # each ordered pair once, sorted by (pos1, pos2)
+    bin1, bin2 = key // n_bins, key % n_bins
+    count = 1.0 + rng.poisson(40.0 / (1.0 + (bin2 - bin1)) ** 0.8)
+    norm = 0.5 + rng.random_sample(n_bins)
+    norm[rng.random_sample(n_bins) < 0.02] = np.nan
+    norm[rng.random_sample(n_bins) < 0.01] = 0.0
+    return {"pos1": (bin1 * resolution_bp).astype(np.int32), "pos2": (bin2 * resolution_bp).astype(np.int32),
+            "count": count.astype(np.float64), "norm": norm, "window_start": (windows * resolution_bp).astype(np.int32),
+            "resolution_bp": int(resolution_bp)}
+
+
 def chrom_features(n: int, d: int, n_labels: int, seed: int, positive_rate: float = 0.05) -> Dict[str, torch.Tensor]:
     g = torch.Generator().manual_seed(seed)
     return {"forward": torch.randn(n, d, generator=g), "backward": torch.randn(n, d, generator=g),

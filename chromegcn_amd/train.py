@@ -8,7 +8,8 @@ optimizer (utils/util_methods.py:14-19) and run the epoch loop (runner.py:25-62)
 
 Inputs are the reference's own files: `<feat_dir>/chrom_feature_dict_{train,valid,test}.pt`
 (utils/util_methods.py:183-199) and `<graph_root>/{split}_graphs_{hicsize}_{hicnorm}norm.pkl`
-(data/7create_graph_new.py:197-202).  `-synthetic` replaces them by the seeded GM12878-shaped stand-in."""
+(data/7create_graph_new.py:197-202), or with `-hic_contacts DIR` the contact caches `DIR/<chrom>.cghic` from which the graphs
+are built on the GPU for any `-hicsize` / `-hicnorm` (chromegcn_amd/hic.py).  `-synthetic` replaces them by the seeded GM12878-shaped stand-in."""
 from __future__ import annotations
 
 import argparse
@@ -28,6 +29,9 @@ def parse(argv=None):
     ap.add_argument("-graph_root", type=str, default=None)
     ap.add_argument("-hicsize", type=str, default="500000")          # config_args.py:47
     ap.add_argument("-hicnorm", type=str, default="SQRTVC")          # config_args.py:46
+    ap.add_argument("-hic_contacts", type=str, default=None, metavar="DIR",
+                    help="build every chromosome's graph on the GPU from DIR/<chrom>.cghic (chromegcn_amd.hic contact caches) "
+                         "for the given -hicsize / -hicnorm, instead of opening a pickle under -graph_root")
     ap.add_argument("-adj_type", type=str, default="hic", choices=["constant", "hic", "both", "none"])
     ap.add_argument("-gcn_layers", type=int, default=2)              # config_args.py:40
     ap.add_argument("-gcn_dropout", type=float, default=0.2)         # config_args.py:24
@@ -63,7 +67,12 @@ def load_inputs(opt):
     for sp in ("train", "valid", "test"):
         data[sp] = torch.load(os.path.join(opt.feat_dir, "chrom_feature_dict_%s.pt" % sp), map_location="cpu")   # main.py:30-32
         graphs[sp] = None
-        if opt.adj_type in ("hic", "both"):
+        if opt.adj_type in ("hic", "both") and opt.hic_contacts:
+            from . import hic
+            graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
+                                                        torch.device("cuda", opt.gpu_id),
+                                                        {c: f["forward"].shape[0] for c, f in data[sp].items()})
+        elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:
                 graphs[sp] = pickle.load(f)

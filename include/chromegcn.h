@@ -581,6 +581,39 @@ int cgcn_ablation_reduce(cgcn_stream_t stream, int n, int S, int C, const float 
                          const int32_t *pos_counts, int label, int col_label, const int32_t *removed, float *base,
                          float *M);
 
+/*
+ * The top-K Hi-C contact graph of one chromosome from its raw contact records (data/7create_graph_new.py:51-120, :168;
+ * chromegcn_amd/hic.py).  These three functions are additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing above changes.
+ *   pos1, pos2 int32 [M]: the two start positions of every record, in file order; count fp64 [M]: the observed value;
+ *   norm fp64 [n_bins] or NULL: the normalisation vector, indexed by pos / resolution_bp (NaN and 0 read as +inf, and so
+ *       does a bin outside the vector); window_start int32 [N], strictly increasing: the windows with peaks (a window's
+ *       node index is its rank).
+ * Rule: a record survives iff pos1 != pos2 and both occur in window_start; its value is count / (nv[b1] * nv[b2]) in fp64
+ * (one multiply, one divide; count itself when norm is NULL); the K = hic_edges / 2 survivors that come first in a STABLE
+ * descending sort by value are taken (ties at the threshold: file order; fewer than K survivors: all of them); every taken
+ * record sets A[i, j] = A[j, i] = 1.  Result: canonical {0,1} CSR (sorted columns, no values, symmetric, no diagonal):
+ * rowptr_out int32 [N + 1], col_out int32 [2 min(K, capacity)] of which the first nnz_out[0] (device int32 [1]) are written.
+ * Not defined: two records with the same ordered (pos1, pos2), NaN values, 2 K >= 2^31.
+ *
+ * Two calls, because the buffers are sized by the survivor count S, which only the device knows: cgcn_hic_count leaves S
+ * in n_survivors (device int64 [1]; it depends on the records and the windows only, not on norm or K); the caller reads it
+ * once and hands it to cgcn_hic_build as `capacity` (any bound >= S is as good).  cgcn_hic_build writes S again; when it
+ * exceeds `capacity` nothing is overrun and the graph is that of the first `capacity` survivors: repeat with a larger one.
+ * All of it is enqueued on `stream`: no allocation, no synchronisation, nothing retained between calls.
+ * CGCN_ERR_BAD_ARG: a negative size, a NULL buffer that would be read or written, norm with resolution_bp < 1;
+ * CGCN_ERR_UNSUPPORTED: capacity or 2 K >= 2^31; CGCN_ERR_WORKSPACE: workspace_bytes below
+ * cgcn_hic_workspace_bytes(M, N, capacity, K) (cgcn_hic_count: capacity = K = 0), which is 0 for unsupported sizes.
+ */
+size_t cgcn_hic_workspace_bytes(long long M, int N, long long capacity, long long K);
+
+int cgcn_hic_count(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2,
+                   const int32_t *window_start, int N, void *workspace, size_t workspace_bytes, long long *n_survivors);
+
+int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                   const double *norm, long long n_bins, int resolution_bp, const int32_t *window_start, int N,
+                   long long K, long long capacity, void *workspace, size_t workspace_bytes, int32_t *rowptr_out,
+                   int32_t *col_out, int32_t *nnz_out, long long *n_survivors);
+
 #ifdef __cplusplus
 }
 #endif
