@@ -4,9 +4,9 @@ Public surface mirrors the reference modules it replaces (see layers.py / graph.
 from .ablation import label_pair_ablation  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
-from .hic import HicContacts, build_hic_graph, build_hic_graph_host  # noqa: F401
+from .hic import HicContacts, build_hic_graph, build_hic_graph_host, expand_contacts_host  # noqa: F401
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 
 __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_graph", "process_graph",
            "upload", "as_graph", "FeatureCollector", "label_pair_ablation", "HicContacts",
-           "build_hic_graph", "build_hic_graph_host"]
+           "build_hic_graph", "build_hic_graph_host", "expand_contacts_host"]

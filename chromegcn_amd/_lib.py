@@ -81,6 +81,12 @@ _HEADER = {
     "cgcn_hic_count": (_c_int, "stream M:ll pos1 pos2 window_start N:i workspace workspace_bytes:z n_survivors"),
     "cgcn_hic_build": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_start N:i K:ll capacity:ll "
                                "workspace workspace_bytes:z rowptr_out col_out nnz_out n_survivors"),
+    "cgcn_hic_up_workspace_bytes": (_c_sz, "M:ll N:i capacity:ll K:ll resolution_bp:i window_bp:i n_window_bins:ll"),
+    "cgcn_hic_count_up": (_c_int, "stream M:ll pos1 pos2 window_start N:i resolution_bp:i window_bp:i n_window_bins:ll workspace "
+                                  "workspace_bytes:z n_survivors"),
+    "cgcn_hic_build_up": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_bp:i n_window_bins:ll "
+                                  "window_start N:i K:ll capacity:ll workspace workspace_bytes:z rowptr_out col_out nnz_out "
+                                  "n_survivors"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

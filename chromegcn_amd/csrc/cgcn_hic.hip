@@ -248,6 +248,184 @@ __global__ __launch_bounds__(256) void k_hic_unique(const long long* __restrict_
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Records coarser than the windows (K562: 5 kb records, 1 kb windows).  up = resolution_bp /
+// window_bp; a record stands for its up x up children (pos1 + a window_bp, pos2 + b window_bp), a outer, b inner, and the
+// rule above applies to that expanded file.  Nothing is expanded in memory: the filter reads the 16 B of a source record and
+// writes only the surviving children, at their places in the expanded file's survivor order.
+//
+//   k_hic_up_bits / k_hic_up_rank   once per call: a bitmap with one bit per window_bp bin and, per 32-bit word, the number
+//                        of windows before it.  A window start that is negative or no multiple of window_bp raises a flag
+//                        instead: the passes then find every child by binary search (the rule, for any window set).
+//   k_hic_filter_up<false>  per record the two up-bit masks m1, m2 of its children that are windows (one two-word table
+//                        read each); it has popc(m1) popc(m2) - (pos1 == pos2 ? popc(m1 & m2) : 0) survivors.  A wave owns
+//                        512 consecutive records and walks them in 8 steps of 64; the counts are scanned across the wave
+//                        with DPP row shifts.  One count per 512-record wave tile: no barrier between the waves.
+//   k_hic_scan           as above, over the wave tiles
+//   k_hic_filter_up<true>   the same pass, writing: the value key once per record, (i, j) from the rank table
+// The workgroups are persistent (a wave strides over the wave tiles) so that the copy of the tables into LDS -- up to
+// 2 x 32 KB -- is paid once per workgroup; larger tables are read from global memory (L2) by the same code.
+#define HIC_UP_THREADS 1024
+#define HIC_UP_WAVES (HIC_UP_THREADS / WAVE)
+#define HIC_UP_WTILE (HIC_STEPS * WAVE)                // records per wave tile
+#define HIC_UP_MAX 8
+#define HIC_UP_LDS_WORDS 8192                          // bitmap words (and rank words) that the LDS route holds
+
+__global__ __launch_bounds__(256) void k_hic_up_bits(const int* __restrict__ ws, int N, int wbp, long long nbits,
+                                                     unsigned* __restrict__ bitmap, int* __restrict__ offgrid) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int s = ws[i];
+  if (s < 0 || s % wbp != 0) { atomicOr(offgrid, 1); return; }
+  const long long q = s / wbp;
+  if (q < nbits) atomicOr(&bitmap[q >> 5], 1u << (q & 31));   // a start beyond the caller's extent is ignored
+}
+
+// rank[w] = set bits of bitmap[0..w).  One workgroup of 1024 threads.
+__global__ __launch_bounds__(1024) void k_hic_up_rank(int nwords, const unsigned* __restrict__ bitmap, int* __restrict__ rank) {
+  __shared__ int part[1024];
+  const int t = threadIdx.x;
+  const int per = (nwords + 1023) / 1024;
+  const int i0 = min(nwords, t * per), i1 = min(nwords, i0 + per);
+  int s = 0;
+  for (int i = i0; i < i1; ++i) s += __popc(bitmap[i]);
+  part[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int v = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = t ? part[t - 1] : 0;
+  for (int i = i0; i < i1; ++i) {
+    rank[i] = run;
+    run += __popc(bitmap[i]);
+  }
+}
+
+// inclusive sum over the 64 lanes of a wave (every lane active): 4 row shifts inside the rows of 16, then the two row
+// broadcasts.  A lane without a source keeps the 0 of `old`.
+__device__ __forceinline__ int hic_wave_scan(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+// which of the children pos + a window_bp, a < up, are windows: bit a.  Bitmap route (every window start is a non-negative
+// multiple of window_bp): bits [q, q + up) of the bitmap, q = pos / window_bp; the bitmap ends with a zero word, so the
+// second word of the read exists.  Search route: the rule, child by child.
+__device__ __forceinline__ unsigned hic_up_mask(bool search, const unsigned* bm, long long nbits, int wbp, int up, int pos,
+                                                const int* __restrict__ ws, int N) {
+  const unsigned all = (1u << up) - 1u;
+  if (search) {
+    unsigned m = 0;
+    for (int a = 0; a < up; ++a) {
+      const long long c = (long long)pos + (long long)a * wbp;
+      if (c <= 2147483647ll && (c < 0 || c / wbp < nbits) && hic_rank(ws, N, (int)c) >= 0) m |= 1u << a;
+    }
+    return m;
+  }
+  const long long q = pos / wbp;
+  if (q * wbp != pos || q >= nbits || q <= -(long long)up) return 0;
+  if (q < 0) return (bm[0] << (unsigned)(-q)) & all;
+  const unsigned w = (unsigned)(q >> 5);
+  const u64 two = (u64)bm[w] | ((u64)bm[w + 1] << 32);
+  return (unsigned)(two >> (q & 31)) & all;
+}
+
+// windows before bin q >= 0 (bitmap route)
+__device__ __forceinline__ int hic_up_rank_of(const unsigned* bm, const int* rk, long long q) {
+  const unsigned w = (unsigned)(q >> 5);
+  return rk[w] + __popc(bm[w] & ((1u << (q & 31)) - 1u));
+}
+
+template <bool WRITE, bool LDS>
+__global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
+    long long M, const int* __restrict__ pos1, const int* __restrict__ pos2, const double* __restrict__ count,
+    const double* __restrict__ norm, long long n_bins, int res, int wbp, int up, const int* __restrict__ ws, int N,
+    const unsigned* __restrict__ tab, int nwords, long long nbits, const int* __restrict__ offgrid, long long wtiles,
+    int* __restrict__ tile_counts, const long long* __restrict__ tile_off, long long capacity, u64* __restrict__ keys,
+    int2* __restrict__ ij) {
+  extern __shared__ unsigned hic_up_lds[];
+  const bool search = offgrid[0] != 0;
+  const unsigned* bm = tab;
+  if (LDS) {
+    if (!search)
+      for (int k = threadIdx.x; k < 2 * nwords; k += HIC_UP_THREADS) hic_up_lds[k] = tab[k];
+    __syncthreads();
+    bm = hic_up_lds;
+  }
+  const int* rk = (const int*)(bm + nwords);
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long long wave0 = (long long)blockIdx.x * HIC_UP_WAVES + threadIdx.x / WAVE, waves = (long long)gridDim.x * HIC_UP_WAVES;
+  for (long long t = wave0; t < wtiles; t += waves) {
+    const long long base = t * HIC_UP_WTILE;
+    unsigned pk[HIC_STEPS];   // m1 | m2 << 8 | (pos1 == pos2) << 16; 0 = no survivor
+    int before[HIC_STEPS];    // survivors of this wave tile in earlier steps and earlier lanes of the step
+    int run = 0;
+#pragma unroll
+    for (int s = 0; s < HIC_STEPS; ++s) {
+      const long long r = base + s * WAVE + lane;
+      unsigned m1 = 0, m2 = 0, diag = 0;
+      if (r < M) {
+        const int a = pos1[r], b = pos2[r];
+        m1 = hic_up_mask(search, bm, nbits, wbp, up, a, ws, N);
+        if (m1) m2 = hic_up_mask(search, bm, nbits, wbp, up, b, ws, N);
+        diag = a == b;
+      }
+      const int cnt = __popc(m1) * __popc(m2) - (diag ? __popc(m1 & m2) : 0);
+      const int inc = hic_wave_scan(cnt);
+      before[s] = run + inc - cnt;
+      run += __builtin_amdgcn_readlane(inc, WAVE - 1);
+      pk[s] = cnt > 0 ? (m1 | (m2 << 8) | (diag << 16)) : 0u;
+    }
+    if (!WRITE) {
+      if (lane == 0) tile_counts[t] = run;
+      continue;
+    }
+    const long long off = tile_off[t];
+#pragma unroll
+    for (int s = 0; s < HIC_STEPS; ++s) {
+      if (pk[s] == 0) continue;
+      long long o = off + before[s];
+      if (o >= capacity) continue;   // the caller's capacity is below the survivor count: the build reports it, nothing is overrun
+      const long long r = base + s * WAVE + lane;
+      const int p1 = pos1[r], p2 = pos2[r];
+      double v = count[r];
+      if (norm) {
+        const double d = hic_norm_at(norm, n_bins, p1, res) * hic_norm_at(norm, n_bins, p2, res);
+        v = v / d;   // one multiply, one divide: every child of the record has the record's two norm bins
+      }
+      const u64 key = hic_value_key(v);
+      const unsigned m1 = pk[s] & 0xFFu, m2 = (pk[s] >> 8) & 0xFFu;
+      const bool diag = (pk[s] >> 16) != 0;
+      int ibase = 0, jbase = 0;
+      if (!search) {   // m1, m2 != 0; a set bit is a bin >= 0
+        ibase = hic_up_rank_of(bm, rk, p1 / wbp + (__ffs(m1) - 1));
+        jbase = hic_up_rank_of(bm, rk, p2 / wbp + (__ffs(m2) - 1));
+      }
+      for (unsigned ma = m1; ma; ma &= ma - 1u) {
+        const int a = __ffs(ma) - 1;
+        const int i = search ? hic_rank(ws, N, p1 + a * wbp) : ibase + __popc(m1 & ((1u << a) - 1u));
+        for (unsigned mb = m2; mb; mb &= mb - 1u) {
+          const int b = __ffs(mb) - 1;
+          if (diag && a == b) continue;
+          if (o >= capacity) break;
+          const int j = search ? hic_rank(ws, N, p2 + b * wbp) : jbase + __popc(m2 & ((1u << b) - 1u));
+          keys[o] = key;
+          ij[o] = make_int2(i, j);
+          ++o;
+        }
+      }
+    }
+  }
+}
+
 static inline size_t hic_al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int hic_bits(int N) {
   int b = 1;
@@ -294,6 +472,105 @@ static bool hic_plan(long long M, int N, long long capacity, long long K, HicPla
   return true;
 }
 
+
+// everything behind the filter: survivors [0, min(S, capacity)) of keyA / ij -> the CSR
+static int hic_select_and_csr(hipStream_t st, const HicPlan& p, char* w, int N, long long K, long long capacity, int32_t* rowptr_out,
+                              int32_t* col_out, int32_t* nnz_out, long long* n_survivors) {
+  int* counts = (int*)(w + p.o_counts);
+  long long* off = (long long*)(w + p.o_off);
+  long long* taken = (long long*)(w + p.o_taken);
+  u64* thr = (u64*)(w + p.o_thr);
+  u64* keyA = (u64*)(w + p.o_keyA);
+  u64* keyB = (u64*)(w + p.o_keyB);
+  int2* ij = (int2*)(w + p.o_ij);
+  u64* edgeA = (u64*)(w + p.o_edgeA);
+  u64* edgeB = (u64*)(w + p.o_edgeB);
+  size_t temp = p.temp;
+  hipLaunchKernelGGL(k_hic_pad, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity, keyA);
+  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), temp, (const u64*)keyA, keyB, (size_t)capacity, 0u, 64u, st) != hipSuccess)
+    return CGCN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_hic_threshold, dim3(1), dim3(64), 0, st, K, capacity, (const long long*)n_survivors, (const u64*)keyB, taken, thr);
+  hipLaunchKernelGGL(k_hic_take<false>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
+                     (const u64*)keyA, (const u64*)thr, counts, (const long long*)nullptr, (const int2*)nullptr, p.b, (u64*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesS, (const int*)counts, off, (long long*)nullptr, (int*)nullptr, 0ll);
+  hipLaunchKernelGGL(k_hic_take<true>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
+                     (const u64*)keyA, (const u64*)thr, (int*)nullptr, (const long long*)off, (const int2*)ij, p.b, edgeA);
+  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), temp, (const u64*)edgeA, edgeB, (size_t)p.E, 0u, (unsigned)(2 * p.b), st) !=
+      hipSuccess)
+    return CGCN_ERR_LAUNCH;
+  hipLaunchKernelGGL(k_hic_unique<false>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
+                     counts, (const long long*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesE, (const int*)counts, off, (long long*)nullptr, nnz_out,
+                     2147483647ll);
+  hipLaunchKernelGGL(k_hic_unique<true>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
+                     (int*)nullptr, (const long long*)off, (const int*)nnz_out, rowptr_out, col_out);
+  return launch_status();
+}
+
+struct HicUpPlan {
+  HicPlan base;
+  int up, nwords;
+  long long wtiles;
+  bool lds;
+  size_t o_wcounts, o_woff, o_tab, tab_bytes, total;
+};
+
+// CGCN_OK, or the error the entry points return for these sizes
+static int hic_up_plan(long long M, int N, long long capacity, long long K, int resolution_bp, int window_bp,
+                       long long n_window_bins, HicUpPlan* p) {
+  if (M < 0 || N < 0 || capacity < 0 || K < 0 || n_window_bins < 0) return CGCN_ERR_BAD_ARG;
+  if (resolution_bp < 1 || window_bp < 1 || resolution_bp % window_bp != 0) return CGCN_ERR_BAD_ARG;
+  p->up = resolution_bp / window_bp;
+  if (p->up > HIC_UP_MAX) return CGCN_ERR_UNSUPPORTED;
+  if (M >= (2147483648ll + p->up * p->up - 1) / (p->up * p->up)) return CGCN_ERR_UNSUPPORTED;   // M up^2 >= 2^31
+  if (n_window_bins > 2147483648ll) return CGCN_ERR_UNSUPPORTED;   // positions are int32
+  if (!hic_plan(M, N, capacity, K, &p->base)) return CGCN_ERR_UNSUPPORTED;
+  p->nwords = (int)((n_window_bins + 31) / 32) + 1;   // one zero word behind the last bit
+  p->lds = p->nwords <= HIC_UP_LDS_WORDS;
+  p->wtiles = hic_tiles(M, HIC_UP_WTILE);
+  size_t o = p->base.total - 256;   // behind the sibling's buffers
+  p->o_wcounts = o; o += hic_al((size_t)p->wtiles * 4);
+  p->o_woff = o; o += hic_al((size_t)p->wtiles * 8);
+  p->o_tab = o;
+  p->tab_bytes = hic_al((size_t)p->nwords * 8) + 256;   // bitmap, rank table, the off-grid flag
+  o += p->tab_bytes;
+  p->total = o + 256;
+  return CGCN_OK;
+}
+
+// the tables of one call, and the grid of its persistent filter passes
+static int hic_up_tables(hipStream_t st, const HicUpPlan& p, char* w, const int32_t* window_start, int N, int window_bp,
+                         long long n_window_bins, unsigned* grid) {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return CGCN_ERR_LAUNCH;
+  const long long wgs = (p.wtiles + HIC_UP_WAVES - 1) / HIC_UP_WAVES, cap = 2ll * (cus < 1 ? 1 : cus);
+  *grid = (unsigned)(wgs < cap ? wgs : cap);
+  unsigned* tab = (unsigned*)(w + p.o_tab);
+  if (hipMemsetAsync(tab, 0, p.tab_bytes, st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  if (N > 0)
+    hipLaunchKernelGGL(k_hic_up_bits, dim3((unsigned)hic_tiles(N, 256)), dim3(256), 0, st, window_start, N, window_bp, n_window_bins,
+                       tab, (int*)(w + p.o_tab + p.tab_bytes - 256));
+  hipLaunchKernelGGL(k_hic_up_rank, dim3(1), dim3(1024), 0, st, p.nwords, (const unsigned*)tab, (int*)(tab + p.nwords));
+  return CGCN_OK;
+}
+
+template <bool WRITE>
+static void hic_up_filter(hipStream_t st, const HicUpPlan& p, unsigned grid, char* w, long long M, const int32_t* pos1,
+                          const int32_t* pos2, const double* count, const double* norm, long long n_bins, int res, int wbp,
+                          const int32_t* ws, int N, long long nbits, long long capacity, u64* keys, int2* ij) {
+  const unsigned* tab = (const unsigned*)(w + p.o_tab);
+  const int* flag = (const int*)(w + p.o_tab + p.tab_bytes - 256);
+  int* counts = (int*)(w + p.o_wcounts);
+  const long long* off = (const long long*)(w + p.o_woff);
+  if (p.lds)
+    hipLaunchKernelGGL((k_hic_filter_up<WRITE, true>), dim3(grid), dim3(HIC_UP_THREADS), (size_t)p.nwords * 8, st, M, pos1, pos2, count,
+                       norm, n_bins, res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij);
+  else
+    hipLaunchKernelGGL((k_hic_filter_up<WRITE, false>), dim3(grid), dim3(HIC_UP_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins,
+                       res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij);
+}
+
 extern "C" {
 
 size_t cgcn_hic_workspace_bytes(long long M, int N, long long capacity, long long K) {
@@ -338,13 +615,8 @@ int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const
   char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   int* counts = (int*)(w + p.o_counts);
   long long* off = (long long*)(w + p.o_off);
-  long long* taken = (long long*)(w + p.o_taken);
-  u64* thr = (u64*)(w + p.o_thr);
   u64* keyA = (u64*)(w + p.o_keyA);
-  u64* keyB = (u64*)(w + p.o_keyB);
   int2* ij = (int2*)(w + p.o_ij);
-  u64* edgeA = (u64*)(w + p.o_edgeA);
-  u64* edgeB = (u64*)(w + p.o_edgeB);
   if (hipMemsetAsync(rowptr_out, 0, ((size_t)N + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (hipMemsetAsync(nnz_out, 0, 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
@@ -355,25 +627,69 @@ int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const
   if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
   hipLaunchKernelGGL(k_hic_filter<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
                      window_start, N, (int*)nullptr, (const long long*)off, capacity, keyA, ij);
-  hipLaunchKernelGGL(k_hic_pad, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity, keyA);
-  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), p.temp, (const u64*)keyA, keyB, (size_t)capacity, 0u, 64u, st) != hipSuccess)
-    return CGCN_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_hic_threshold, dim3(1), dim3(64), 0, st, K, capacity, (const long long*)n_survivors, (const u64*)keyB, taken, thr);
-  hipLaunchKernelGGL(k_hic_take<false>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
-                     (const u64*)keyA, (const u64*)thr, counts, (const long long*)nullptr, (const int2*)nullptr, p.b, (u64*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesS, (const int*)counts, off, (long long*)nullptr, (int*)nullptr, 0ll);
-  hipLaunchKernelGGL(k_hic_take<true>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
-                     (const u64*)keyA, (const u64*)thr, (int*)nullptr, (const long long*)off, (const int2*)ij, p.b, edgeA);
-  if (rocprim::radix_sort_keys((void*)(w + p.o_temp), p.temp, (const u64*)edgeA, edgeB, (size_t)p.E, 0u, (unsigned)(2 * p.b), st) !=
-      hipSuccess)
-    return CGCN_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_hic_unique<false>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
-                     counts, (const long long*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesE, (const int*)counts, off, (long long*)nullptr, nnz_out,
-                     2147483647ll);
-  hipLaunchKernelGGL(k_hic_unique<true>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
-                     (int*)nullptr, (const long long*)off, (const int*)nnz_out, rowptr_out, col_out);
+  return hic_select_and_csr(st, p, w, N, K, capacity, rowptr_out, col_out, nnz_out, n_survivors);
+}
+
+size_t cgcn_hic_up_workspace_bytes(long long M, int N, long long capacity, long long K, int resolution_bp, int window_bp,
+                                   long long n_window_bins) {
+  HicUpPlan p;
+  return hic_up_plan(M, N, capacity, K, resolution_bp, window_bp, n_window_bins, &p) == CGCN_OK ? p.total : 0;
+}
+
+int cgcn_hic_count_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                      int N, int resolution_bp, int window_bp, long long n_window_bins, void* workspace, size_t workspace_bytes,
+                      long long* n_survivors) {
+  if (M < 0 || N < 0 || !n_survivors) return CGCN_ERR_BAD_ARG;
+  if (M > 0 && (!pos1 || !pos2 || !workspace)) return CGCN_ERR_BAD_ARG;
+  if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
+  HicUpPlan p;
+  const int rc = hic_up_plan(M, N, 0, 0, resolution_bp, window_bp, n_window_bins, &p);
+  if (rc != CGCN_OK) return rc;
+  if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
+  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  unsigned grid = 1;
+  if (hic_up_tables(st, p, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
+  hic_up_filter<false>(st, p, grid, w, M, pos1, pos2, nullptr, nullptr, 0ll, resolution_bp, window_bp, window_start, N, n_window_bins,
+                       0ll, nullptr, nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.wtiles, (const int*)(w + p.o_wcounts), (long long*)(w + p.o_woff),
+                     n_survivors, (int*)nullptr, 0ll);
   return launch_status();
+}
+
+int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                      const double* norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
+                      const int32_t* window_start, int N, long long K, long long capacity, void* workspace, size_t workspace_bytes,
+                      int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out, long long* n_survivors) {
+  if (M < 0 || N < 0 || K < 0 || capacity < 0 || n_bins < 0 || !rowptr_out || !nnz_out || !n_survivors || !workspace)
+    return CGCN_ERR_BAD_ARG;
+  if (M > 0 && (!pos1 || !pos2 || !count)) return CGCN_ERR_BAD_ARG;
+  if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
+  if (norm && n_bins < 1) return CGCN_ERR_BAD_ARG;
+  HicUpPlan u;
+  const int rc = hic_up_plan(M, N, capacity, K, resolution_bp, window_bp, n_window_bins, &u);
+  if (rc != CGCN_OK) return rc;
+  const HicPlan& p = u.base;
+  if (p.half > 0 && !col_out) return CGCN_ERR_BAD_ARG;
+  if (workspace_bytes < u.total) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  u64* keyA = (u64*)(w + p.o_keyA);
+  int2* ij = (int2*)(w + p.o_ij);
+  if (hipMemsetAsync(rowptr_out, 0, ((size_t)N + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  if (hipMemsetAsync(nnz_out, 0, 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
+  unsigned grid = 1;
+  if (hic_up_tables(st, u, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
+  hic_up_filter<false>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,
+                       0ll, nullptr, nullptr);
+  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)u.wtiles, (const int*)(w + u.o_wcounts), (long long*)(w + u.o_woff),
+                     n_survivors, (int*)nullptr, 0ll);
+  if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
+  hic_up_filter<true>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,
+                      capacity, keyA, ij);
+  return hic_select_and_csr(st, p, w, N, K, capacity, rowptr_out, col_out, nnz_out, n_survivors);
 }
 
 }  // extern "C"

@@ -7,7 +7,16 @@ The rule, for one chromosome: a record (pos1, pos2, count) survives iff pos1 != 
 peaks; its value is count / (nv[pos1 // res] * nv[pos2 // res]) in float64, nv = the norm vector with NaN and 0 replaced by
 +inf (count itself without a vector); the K survivors that come first in a STABLE descending sort by value are taken;
 A[i, j] = A[j, i] = 1 for each of them, i, j the ranks of the two positions among the windows.  Outside the contract: two
-records with the same ordered (pos1, pos2), NaN counts, 2 K >= 2^31."""
+records with the same ordered (pos1, pos2), NaN counts, 2 K >= 2^31.
+
+Records coarser than the windows (K562: 5 kb records, 1 kb windows; data/extras/upsample_hic.py:36-44,
+data/create_data.py:47-55): with `window_bp` dividing `resolution_bp`, up = resolution_bp / window_bp <= 8, the graph is the
+rule above applied to the EXPANDED FILE -- for each record in file order, for a = 0 .. up - 1, for b = 0 .. up - 1, the record
+(pos1 + a window_bp, pos2 + b window_bp, count) -- with the same norm, resolution_bp, window_start and K.  All up^2 children
+of a record share its two norm bins and so its value; ties are taken in the order of the expanded file; a record (p, p)
+yields the up^2 - up ordered pairs a != b, and (p + a, p + b) and (p + b, p + a) both count against K.  Contract: pos1 and
+pos2 are multiples of resolution_bp (checked).  expand_contacts_host writes the expanded file out; nothing else here does:
+the device filter and the host restatement both read the compact records and expand only the survivors."""
 from __future__ import annotations
 
 import os
@@ -48,32 +57,99 @@ def _check_norm(norm, resolution_bp, ws):
                          % (norm.shape[0], int(ws[-1]) // int(resolution_bp)))
 
 
-def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start):
-    """(record index, i, j, value) of the surviving records in file order (rules 1 and 2)."""
+def _upsample(resolution_bp, window_bp) -> int:
+    """up = resolution_bp / window_bp (1 for window_bp = None: the records are at the windows' own resolution)"""
+    if window_bp is None:
+        return 1
+    res, wbp = int(resolution_bp), int(window_bp)
+    if res < 1 or wbp < 1 or res % wbp:
+        raise ValueError("window_bp=%r does not divide resolution_bp=%r" % (window_bp, resolution_bp))
+    if res // wbp > 8:
+        raise ValueError("resolution_bp / window_bp = %d: more than 8 is not supported" % (res // wbp))
+    return res // wbp
+
+
+def _check_grid(p1, p2, resolution_bp):
+    if np.any(p1 % int(resolution_bp)) or np.any(p2 % int(resolution_bp)):
+        raise ValueError("pos1 / pos2 hold positions that are no multiple of resolution_bp=%d" % int(resolution_bp))
+
+
+def expand_contacts_host(pos1, pos2, count, resolution_bp, window_bp):
+    """The expanded file of rule 1 as arrays (int32 [up^2 M], int32 [up^2 M], count's dtype [up^2 M]): the loop of
+    data/extras/upsample_hic.py:36-44, `a` outer and `b` inner.  up^2 times the memory: for tests and tools."""
+    up = _upsample(resolution_bp, window_bp)
+    p1, p2 = np.asarray(pos1, dtype=np.int64), np.asarray(pos2, dtype=np.int64)
+    step = np.arange(up, dtype=np.int64) * (int(resolution_bp) // up)
+    e1 = np.broadcast_to(p1[:, None, None] + step[None, :, None], (p1.size, up, up)).reshape(-1)
+    e2 = np.broadcast_to(p2[:, None, None] + step[None, None, :], (p2.size, up, up)).reshape(-1)
+    if e1.size and max(int(e1.max()), int(e2.max())) >= 2 ** 31:
+        raise ValueError("an expanded position does not fit int32")
+    return e1.astype(np.int32), e2.astype(np.int32), np.repeat(np.asarray(count), up * up)
+
+
+_POPCOUNT8 = np.array([bin(x).count("1") for x in range(256)], dtype=np.int64)
+
+
+def _survivors_up(p1, p2, ws, wbp, up):
+    """(source record, child a, child b, i, j) of the survivors of the expanded file, in its order, from the compact records:
+    per record the two up-bit masks of its children that are windows; only records with a survivor are expanded."""
+    n = ws.size
+
+    def masks(p):
+        m = np.zeros(p.size, np.uint8)
+        for a in range(up):
+            c = p + a * wbp
+            m |= (ws[np.minimum(np.searchsorted(ws, c), n - 1)] == c).astype(np.uint8) << np.uint8(a)
+        return m
+
+    m1, m2 = masks(p1), masks(p2)
+    cnt = _POPCOUNT8[m1] * _POPCOUNT8[m2] - np.where(p1 == p2, _POPCOUNT8[m1 & m2], 0)
+    rec = np.flatnonzero(cnt > 0)
+    bit = np.arange(up, dtype=np.uint8)
+    alive = (((m1[rec, None, None] >> bit[None, :, None]) & 1) & ((m2[rec, None, None] >> bit[None, None, :]) & 1)).astype(bool)
+    alive &= ~((p1[rec] == p2[rec])[:, None, None] & np.eye(up, dtype=bool)[None])
+    r, a, b = np.nonzero(alive)   # C order: record, a, b = the order of the expanded file
+    src = rec[r]
+    assert src.size == int(cnt.sum())
+    return src, a, b, np.searchsorted(ws, p1[src] + a * wbp), np.searchsorted(ws, p2[src] + b * wbp)
+
+
+def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp=None):
+    """(record index, i, j, value) of the surviving records in file order (rules 1 and 2).  With window_bp: of the surviving
+    records of the expanded file, the index being the position in it."""
+    up = _upsample(resolution_bp, window_bp)
     ws = _windows(window_start).astype(np.int64)
     p1, p2 = np.asarray(pos1, dtype=np.int64), np.asarray(pos2, dtype=np.int64)
+    if up > 1:
+        _check_grid(p1, p2, resolution_bp)
     n = ws.size
     if n == 0 or p1.size == 0:
         e = np.zeros(0, np.int64)
         return e, e, e, np.zeros(0, np.float64)
-    i = np.minimum(np.searchsorted(ws, p1), n - 1)
-    j = np.minimum(np.searchsorted(ws, p2), n - 1)
-    idx = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2))
-    v = np.asarray(count)[idx].astype(np.float64)
+    if up > 1:
+        src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up)
+        idx = src * (up * up) + a * up + b
+    else:
+        i = np.minimum(np.searchsorted(ws, p1), n - 1)
+        j = np.minimum(np.searchsorted(ws, p2), n - 1)
+        idx = src = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2))
+        i, j = i[idx], j[idx]
+    v = np.asarray(count)[src].astype(np.float64)
     if norm is not None:
         nv = np.array(norm, dtype=np.float64)
         _check_norm(nv, resolution_bp, ws)
         nv[np.isnan(nv) | (nv == 0.0)] = np.inf
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-            v = v / (nv[p1[idx] // int(resolution_bp)] * nv[p2[idx] // int(resolution_bp)])
-    return idx, i[idx], j[idx], v
+            v = v / (nv[p1[src] // int(resolution_bp)] * nv[p2[src] // int(resolution_bp)])
+    return idx, i, j, v
 
 
-def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges) -> sp.csr_matrix:
-    """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns)."""
+def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None) -> sp.csr_matrix:
+    """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns).  With window_bp: of
+    the expanded file, which is never written out (the CPU path for coarse records at full size)."""
     n = _windows(window_start).size
     k = _budget(hic_edges)
-    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start)
+    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp)
     take = np.argsort(-v, kind="stable")[:k]
     i, j = i[take], j[take]
     a = sp.coo_matrix((np.ones(2 * i.size), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(n, n)).tocsr()
@@ -179,7 +255,9 @@ class HicContacts:
             raise ValueError("pos1, pos2 and count must be vectors of one length")
         self.M = int(self.pos1.numel())
         self._ws_host = self._ws_dev = None
-        self._survivors = 0
+        self._survivors = None   # of the current window set, records at the windows' resolution
+        self._survivors_up = {}  # of the current window set, per (resolution_bp, window_bp)
+        self._on_grid = set()    # the resolutions of which every position is known to be a multiple
         self._vectors = []   # (the caller's object, its device copy): a sweep passes the same vector again
 
     @classmethod
@@ -202,49 +280,92 @@ class HicContacts:
         self._vectors = self._vectors[-7:] + [(norm, dev)]
         return dev
 
-    def survivors(self, window_start) -> int:
-        """records with pos1 != pos2 and both ends among the windows (cgcn_hic_count; one host sync per window set)"""
-        from . import _lib
+    def _set_windows(self, window_start):
         ws = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
-        if self._ws_host is not None and np.array_equal(ws, self._ws_host):
-            return self._survivors
-        ws_dev = torch.from_numpy(ws).to(self.device)
-        with torch.cuda.device(self.device):
-            need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=int(ws.size), capacity=0, K=0)
-            wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d" % self.M)
-            out = torch.zeros(1, dtype=torch.int64, device=self.device)
-            _lib.call("cgcn_hic_count", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=ws_dev, N=int(ws.size),
-                      workspace=wsp, workspace_bytes=need, n_survivors=out)
-            self._survivors = int(out.item())
-        self._ws_host, self._ws_dev = ws, ws_dev
-        return self._survivors
+        if self._ws_host is None or not np.array_equal(ws, self._ws_host):
+            self._ws_host, self._ws_dev = ws, torch.from_numpy(ws).to(self.device)
+            self._survivors, self._survivors_up = None, {}
 
-    def build_raw(self, norm, resolution_bp, window_start, hic_edges):
+    def _window_bins(self, wbp) -> int:
+        """the extent of the window bitmap (cgcn_hic_count_up's n_window_bins)"""
+        return max(0, int(self._ws_host[-1]) // wbp + 1) if self._ws_host.size else 0
+
+    def survivors(self, window_start, resolution_bp=None, window_bp=None) -> int:
+        """records with pos1 != pos2 and both ends among the windows (cgcn_hic_count; one host sync per window set).  With
+        window_bp: of the expanded file (cgcn_hic_count_up; one host sync per window set and window_bp)."""
+        from . import _lib
+        up = _upsample(resolution_bp, window_bp)
+        self._set_windows(window_start)
+        n = int(self._ws_host.size)
+        if window_bp is None or int(window_bp) == int(resolution_bp):
+            if self._survivors is None:
+                with torch.cuda.device(self.device):
+                    need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=0, K=0)
+                    wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d" % self.M)
+                    out = torch.zeros(1, dtype=torch.int64, device=self.device)
+                    _lib.call("cgcn_hic_count", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
+                              workspace=wsp, workspace_bytes=need, n_survivors=out)
+                    self._survivors = int(out.item())
+            return self._survivors
+        res, wbp = int(resolution_bp), int(window_bp)
+        if (res, wbp) not in self._survivors_up:
+            with torch.cuda.device(self.device):
+                bins = self._window_bins(wbp)
+                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=0, K=0, resolution_bp=res, window_bp=wbp,
+                                  n_window_bins=bins)
+                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d" % (self.M, up))
+                out = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: survivors, [1]: positions off the grid
+                if res not in self._on_grid:   # read back with the count: still one sync
+                    out[1] = ((self.pos1 % res) != 0).sum() + ((self.pos2 % res) != 0).sum()
+                _lib.call("cgcn_hic_count_up", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
+                          resolution_bp=res, window_bp=wbp, n_window_bins=bins, workspace=wsp, workspace_bytes=need,
+                          n_survivors=out)
+                s, off = out.tolist()
+            if off:
+                raise ValueError("pos1 / pos2 hold %d positions that are no multiple of resolution_bp=%d" % (off, res))
+            self._on_grid.add(res)
+            self._survivors_up[(res, wbp)] = int(s)
+        return self._survivors_up[(res, wbp)]
+
+    def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None):
         """(rowptr int32 [N + 1], col int32 [>= nnz], sizes int64 [2] = (nnz, survivors)), all on the device, enqueued
         on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors()."""
         from . import _lib
         k = _budget(hic_edges)
-        cap = self.survivors(window_start)
+        up = _upsample(resolution_bp, window_bp)
+        direct = window_bp is None or int(window_bp) == int(resolution_bp)
+        cap = self.survivors(window_start) if direct else self.survivors(window_start, resolution_bp, window_bp)
         ws, n = self._ws_dev, int(self._ws_host.size)
         nv = self._norm(norm)
         if nv is not None:
             _check_norm(nv, resolution_bp, self._ws_host)
         with torch.cuda.device(self.device):
-            need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=cap, K=k)
-            wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d capacity=%d K=%d" % (self.M, cap, k))
             rowptr = torch.empty(n + 1, dtype=torch.int32, device=self.device)
             col = torch.empty(max(2 * min(k, cap), 1), dtype=torch.int32, device=self.device)
             sizes = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: nnz (its low int32 half), [1]: survivors
-            _lib.call("cgcn_hic_build", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
-                      n_bins=0 if nv is None else int(nv.numel()), resolution_bp=int(resolution_bp), window_start=ws, N=n, K=k,
-                      capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr, col_out=col,
-                      nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
+            if direct:
+                need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=cap, K=k)
+                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d capacity=%d K=%d" % (self.M, cap, k))
+                _lib.call("cgcn_hic_build", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
+                          n_bins=0 if nv is None else int(nv.numel()), resolution_bp=int(resolution_bp), window_start=ws, N=n,
+                          K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr, col_out=col,
+                          nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
+            else:
+                res, wbp = int(resolution_bp), int(window_bp)
+                bins = self._window_bins(wbp)
+                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=cap, K=k, resolution_bp=res,
+                                  window_bp=wbp, n_window_bins=bins)
+                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d capacity=%d K=%d" % (self.M, up, cap, k))
+                _lib.call("cgcn_hic_build_up", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
+                          n_bins=0 if nv is None else int(nv.numel()), resolution_bp=res, window_bp=wbp, n_window_bins=bins,
+                          window_start=ws, N=n, K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr,
+                          col_out=col, nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
         return rowptr, col, sizes
 
-    def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False):
+    def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
         host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back."""
-        rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges)
+        rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp)
         n = int(rowptr.numel()) - 1
         g = G.normalize_device_csr(adj_type, n, rowptr, col, None, self.device)
         if not return_raw:
@@ -255,11 +376,13 @@ class HicContacts:
 
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
-                    return_raw=False):
+                    return_raw=False, window_bp=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
-    `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again."""
+    `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
+    coarser than the windows and stand for their expanded file (the module's docstring)."""
+    _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
-    return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw)
+    return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp)
 
 
 def contact_cache_path(root: str, chrom: str) -> str:
@@ -267,10 +390,11 @@ def contact_cache_path(root: str, chrom: str) -> str:
 
 
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",
-                               sizes: Optional[Dict[str, int]] = None) -> Dict[str, G.ChromGraph]:
+                               sizes: Optional[Dict[str, int]] = None, window_bp=None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
-    instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome."""
+    instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
+    (`-hic_upsample`): the window size; a cache whose resolution_bp is coarser is built as its expanded file."""
     out = {}
     for chrom in chroms:
         c = load_contacts_cache(contact_cache_path(root, chrom))
@@ -282,6 +406,7 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
         if sizes is not None and sizes[chrom] != c.window_start.size:
             raise ValueError("%s has %d windows but the chromosome's features have %d rows"
                              % (contact_cache_path(root, chrom), c.window_start.size, sizes[chrom]))
+        up = {"window_bp": int(window_bp)} if window_bp is not None and c.resolution_bp > int(window_bp) else {}
         out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, c.norms[hicnorm] if hicnorm else None, c.resolution_bp,
-                                     c.window_start, int(hicsize), adj_type=adj_type, device=device)
+                                     c.window_start, int(hicsize), adj_type=adj_type, device=device, **up)
     return out

@@ -135,6 +135,27 @@ def raw_contacts(chrom: str, seed: int = None, resolution_bp: int = 1000, backgr
             "resolution_bp": int(resolution_bp)}
 
 
+def raw_contacts_coarse(chrom: str, resolution_bp: int = 5000, window_bp: int = 1000, seed: int = None, **kw) -> dict:
+    """raw_contacts(chrom, resolution_bp=window_bp, ...) as a coarser experiment records it (K562: 5 kb records for 1 kb
+    windows): the same distance-decay contacts binned to `resolution_bp`, counts summed, records sorted by (pos1, pos2), upper
+    triangle, diagonal records present; a norm vector of its own at `resolution_bp`; the windows stay at `window_bp`.
+    Returns raw_contacts' dict plus 'window_bp'."""
+    if resolution_bp % window_bp:
+        raise ValueError("window_bp must divide resolution_bp")
+    r = raw_contacts(chrom, seed=seed, resolution_bp=window_bp, **kw)
+    n_bins = -(-HG19_LEN[chrom] // resolution_bp)
+    key = (r["pos1"].astype(np.int64) // resolution_bp) * n_bins + r["pos2"].astype(np.int64) // resolution_bp
+    key, inv = np.unique(key, return_inverse=True)
+    count = np.bincount(inv.reshape(-1), weights=r["count"], minlength=key.size)
+    rng = np.random.RandomState((chrom_seed(chrom) if seed is None else seed) + 9000)
+    norm = 0.5 + rng.random_sample(n_bins)
+    norm[rng.random_sample(n_bins) < 0.02] = np.nan
+    norm[rng.random_sample(n_bins) < 0.01] = 0.0
+    return {"pos1": (key // n_bins * resolution_bp).astype(np.int32), "pos2": (key % n_bins * resolution_bp).astype(np.int32),
+            "count": count.astype(np.float64), "norm": norm, "window_start": r["window_start"],
+            "resolution_bp": int(resolution_bp), "window_bp": int(window_bp)}
+
+
 def chrom_features(n: int, d: int, n_labels: int, seed: int, positive_rate: float = 0.05) -> Dict[str, torch.Tensor]:
     g = torch.Generator().manual_seed(seed)
     return {"forward": torch.randn(n, d, generator=g), "backward": torch.randn(n, d, generator=g),

@@ -32,6 +32,10 @@ def parse(argv=None):
     ap.add_argument("-hic_contacts", type=str, default=None, metavar="DIR",
                     help="build every chromosome's graph on the GPU from DIR/<chrom>.cghic (chromegcn_amd.hic contact caches) "
                          "for the given -hicsize / -hicnorm, instead of opening a pickle under -graph_root")
+    ap.add_argument("-hic_upsample", action="store_true",
+                    help="-hic_contacts: a cache whose records are coarser than -window_size (K562: 5 kb) stands for its "
+                         "expanded file, every record for the window pairs it covers (data/extras/upsample_hic.py)")
+    ap.add_argument("-window_size", type=int, default=1000)          # config_args.py:9
     ap.add_argument("-adj_type", type=str, default="hic", choices=["constant", "hic", "both", "none"])
     ap.add_argument("-gcn_layers", type=int, default=2)              # config_args.py:40
     ap.add_argument("-gcn_dropout", type=float, default=0.2)         # config_args.py:24
@@ -71,7 +75,8 @@ def load_inputs(opt):
             from . import hic
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
-                                                        {c: f["forward"].shape[0] for c, f in data[sp].items()})
+                                                        {c: f["forward"].shape[0] for c, f in data[sp].items()},
+                                                        window_bp=opt.window_size if opt.hic_upsample else None)
         elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:

@@ -614,6 +614,44 @@ int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t *pos1, const
                    long long K, long long capacity, void *workspace, size_t workspace_bytes, int32_t *rowptr_out,
                    int32_t *col_out, int32_t *nnz_out, long long *n_survivors);
 
+/*
+ * The same graph from records COARSER than the windows (K562: 5 kb records, 1 kb windows; data/extras/upsample_hic.py:36-44,
+ * data/create_data.py:47-55).  Additions to ABI 26 like the three functions above; nothing above changes.
+ * window_bp divides resolution_bp, up = resolution_bp / window_bp, 1 <= up <= 8.
+ * Rule: (1) the EXPANDED FILE of the records (pos1, pos2, count) is, for each record in file order, for a = 0 .. up - 1, for
+ * b = 0 .. up - 1, the record (pos1 + a window_bp, pos2 + b window_bp, count); (2) the graph is the rule of cgcn_hic_build
+ * applied to the expanded file with the same norm, resolution_bp, window_start and K: a child survives iff its two positions
+ * differ and both occur in window_start; its value is count / (nv[b1] * nv[b2]) with the norm bins of the SOURCE record (all
+ * up^2 children of a record share them and so its value); the stable descending top-K, ties in the order of the expanded file;
+ * A[i, j] = A[j, i] = 1.  A record (p, p) yields the up^2 - up ordered pairs a != b, (p + a, p + b) and (p + b, p + a) both
+ * counting against K.  Nothing is expanded in memory: the filter reads the 16 B of a source record and writes only the
+ * surviving children.  Contract: pos1, pos2 multiples of resolution_bp (blocks of different records cannot collide); what the
+ * rule above leaves undefined stays undefined.  up = 1 gives byte for byte what cgcn_hic_count / cgcn_hic_build give.
+ *
+ * n_window_bins: the extent of the window bitmap, (last window start) / window_bp + 1, which the host knows.  A position at or
+ * beyond n_window_bins * window_bp is no window; a window start at or beyond it is the caller's error and is ignored (never an
+ * out-of-bounds write).  window_start stays any strictly increasing vector: when a start is negative or no multiple of
+ * window_bp the passes find the children by binary search instead of the bitmap, and the graph is the rule's all the same.
+ *
+ * Calls, sizes and conventions as for cgcn_hic_count / cgcn_hic_build: n_survivors and capacity count survivors of the
+ * expanded file; on overflow the graph is that of the first `capacity` of them.  Enqueue only, no allocation, no sync.
+ * CGCN_ERR_BAD_ARG: as above, and resolution_bp < 1, window_bp < 1, window_bp not dividing resolution_bp, n_window_bins < 0;
+ * CGCN_ERR_UNSUPPORTED: as above, and up > 8, M up^2 >= 2^31; CGCN_ERR_WORKSPACE: workspace_bytes below
+ * cgcn_hic_up_workspace_bytes(...) (cgcn_hic_count_up: capacity = K = 0), which is 0 for sizes the other two reject.
+ */
+size_t cgcn_hic_up_workspace_bytes(long long M, int N, long long capacity, long long K, int resolution_bp, int window_bp,
+                                   long long n_window_bins);
+
+int cgcn_hic_count_up(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2,
+                      const int32_t *window_start, int N, int resolution_bp, int window_bp, long long n_window_bins,
+                      void *workspace, size_t workspace_bytes, long long *n_survivors);
+
+int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                      const double *norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
+                      const int32_t *window_start, int N, long long K, long long capacity, void *workspace,
+                      size_t workspace_bytes, int32_t *rowptr_out, int32_t *col_out, int32_t *nnz_out,
+                      long long *n_survivors);
+
 #ifdef __cplusplus
 }
 #endif
