@@ -4,9 +4,11 @@ Public surface mirrors the reference modules it replaces (see layers.py / graph.
 from .ablation import label_pair_ablation  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
-from .hic import HicContacts, build_hic_graph, build_hic_graph_host, expand_contacts_host  # noqa: F401
+from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
+                  parse_contacts_text_host, release_text_staging, windows_from_bed)
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 
 __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_graph", "process_graph",
            "upload", "as_graph", "FeatureCollector", "label_pair_ablation", "HicContacts",
-           "build_hic_graph", "build_hic_graph_host", "expand_contacts_host"]
+           "build_hic_graph", "build_hic_graph_host", "expand_contacts_host", "contacts_from_text",
+           "parse_contacts_text_host", "release_text_staging", "windows_from_bed"]

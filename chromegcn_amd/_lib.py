@@ -87,6 +87,10 @@ _HEADER = {
     "cgcn_hic_build_up": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_bp:i n_window_bins:ll "
                                   "window_start N:i K:ll capacity:ll workspace workspace_bytes:z rowptr_out col_out nnz_out "
                                   "n_survivors"),
+    "cgcn_text_workspace_bytes": (_c_sz, "n_bytes:ll"),
+    "cgcn_text_count": (_c_int, "stream text n_bytes:ll workspace workspace_bytes:z n_records"),
+    "cgcn_text_parse": (_c_int, "stream text n_bytes:ll M:ll pos1_out pos2_out count_out flags flag_capacity:ll flag_totals "
+                                "workspace workspace_bytes:z"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

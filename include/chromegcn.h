@@ -652,6 +652,51 @@ int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t *pos1, co
                       size_t workspace_bytes, int32_t *rowptr_out, int32_t *col_out, int32_t *nnz_out,
                       long long *n_survivors);
 
+/*
+ * Hi-C contact text (a Juicer `RAWobserved` dump: data/7create_graph_new.py:71-76 reads it with int() and float()) parsed
+ * on the device into pos1 / pos2 / count, the arrays cgcn_hic_count and cgcn_hic_build take (chromegcn_amd/hic.py,
+ * DESIGN.md section 4.6).  Additions to ABI 26 like the Hi-C functions above; nothing above changes.
+ *
+ * THE RULE.  A file is a sequence of lines.  Each line ends with LF or CR LF; the last line may have no terminator (a CR is
+ * part of the terminator only in front of an LF).  Record r is the r-th line (0-based); the empty piece behind a final
+ * terminator is no line; an empty file has no record.  A line is F1 TAB F2 TAB F3.
+ *   FAST (decided and parsed on the device): the line is at most CGCN_TEXT_LINE_MAX bytes without its terminator; F1 and
+ *     F2 are one to ten decimal digits with a value below 2^31; F3 is [+-]? digits [. digits]? ([eE] [+-]? digits)?; its
+ *     significand digits (integer part, then fraction), without leading zeros and without trailing zeros of the fraction,
+ *     are at most 15 and form the integer w < 10^15 < 2^53; e = exponent - (fraction digits that remain in w) has
+ *     |e| <= 22.  The value is (double)w * 10^e for e >= 0 and (double)w / 10^-e otherwise, negated behind '-': one
+ *     correctly rounded fp64 operation on two exact operands, hence what Python's float() returns, bit for bit.
+ *   SLOW: not fast, but float(F3), int(float(F1)) and int(float(F2)) of Python accept the fields and the two positions fit
+ *     int32: 16 or more significant digits, |e| > 22, nan / inf counts, 1e3 as a position, blanks around a field, a line
+ *     longer than the bound.  The device leaves pos1[r], pos2[r], count[r] of such a line untouched and reports it; the
+ *     caller parses exactly those lines on the host and patches them in.
+ *   MALFORMED: everything else -- an empty line, a field count other than three, a '#' comment, a field float() rejects.
+ * The device decides fast exactly.  Of the other lines it reports as CGCN_TEXT_MALFORMED the ones that are empty or (within
+ * the bound) do not hold exactly two TABs, and every remaining one as CGCN_TEXT_SLOW: whether float() accepts those is the
+ * host's to say.
+ *
+ * text: n_bytes bytes, 16-byte aligned.  cgcn_text_count leaves the record count in n_records (device int64 [1]); the caller
+ * reads it once, sizes pos1_out / pos2_out int32 [M] and count_out fp64 [M] with it and calls cgcn_text_parse (a smaller M
+ * parses the first M records; nothing is overrun).  flags: int64 [flag_capacity][3] = (record, byte offset of its line,
+ * kind), appended in any order; flag_totals (device int64 [2]): the number of slow and of malformed lines of the whole
+ * text.  When their sum exceeds flag_capacity only flag_capacity entries were written: call again with a larger one.
+ * Enqueue only, no allocation, no sync, nothing kept between calls (cgcn_text_parse counts again by itself).
+ * CGCN_ERR_BAD_ARG: a negative size, a NULL or misaligned buffer that would be read or written; CGCN_ERR_UNSUPPORTED:
+ * M >= 2^31; CGCN_ERR_WORKSPACE: workspace_bytes below cgcn_text_workspace_bytes(n_bytes).
+ */
+#define CGCN_TEXT_LINE_MAX 64
+#define CGCN_TEXT_SLOW 1
+#define CGCN_TEXT_MALFORMED 2
+
+size_t cgcn_text_workspace_bytes(long long n_bytes);
+
+int cgcn_text_count(cgcn_stream_t stream, const void *text, long long n_bytes, void *workspace, size_t workspace_bytes,
+                    long long *n_records);
+
+int cgcn_text_parse(cgcn_stream_t stream, const void *text, long long n_bytes, long long M, int32_t *pos1_out,
+                    int32_t *pos2_out, double *count_out, long long *flags, long long flag_capacity,
+                    long long *flag_totals, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,71 @@
+"""Turns a Juicer directory into the contact caches `python -m chromegcn_amd.train -hic_contacts DIR` loads; needs a GPU.
+
+Walks the reference's layout (data/7create_graph_new.py:145, :174-175):
+    <hic_root>/<cell>_combined/<res>kb_resolution_intrachromosomal/<chrom>/MAPQGE30/<chrom>_<res>kb.RAWobserved
+plus the `<chrom>_<res>kb.{KR,VC,SQRTVC}norm` files that exist beside it, and a windows bed (chrom<TAB>start<TAB>...: the
+chromosome's windows with peaks, create_bin_dict :14-47).  Per chromosome the contact text is parsed on the device
+(chromegcn_amd.hic.contacts_from_text), the norm vectors -- one value per bin -- on the host, and
+`<out>/<chrom>.cghic` is written (hic.save_contacts_cache).  Prints one JSON line per chromosome."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from chromegcn_amd import hic  # noqa: E402
+
+NORMS = ("KR", "VC", "SQRTVC")
+
+
+def chrom_dir(hic_root, cell, res_kb, chrom):
+    return os.path.join(hic_root, "%s_combined" % cell, "%skb_resolution_intrachromosomal" % res_kb, chrom, "MAPQGE30")
+
+
+def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=None):
+    """writes <out>/<chrom>.cghic for every chromosome of `chroms`; returns one dict per chromosome"""
+    windows = hic.windows_from_bed(bed, chroms)
+    os.makedirs(out, exist_ok=True)
+    kw = {} if chunk_bytes is None else {"chunk_bytes": int(chunk_bytes)}
+    lines = []
+    for chrom in chroms:
+        d = chrom_dir(hic_root, cell, res_kb, chrom)
+        raw = os.path.join(d, "%s_%skb.RAWobserved" % (chrom, res_kb))
+        if not os.path.exists(raw):
+            raise SystemExit("%s is missing" % raw)
+        t0 = time.perf_counter()
+        c = hic.contacts_from_text(raw, device=device, **kw)
+        norms = {}
+        for name in NORMS:
+            p = os.path.join(d, "%s_%skb.%snorm" % (chrom, res_kb, name))
+            if os.path.exists(p):
+                norms[name] = np.loadtxt(p, dtype=np.float64, ndmin=1)
+        path = hic.contact_cache_path(out, chrom)
+        hic.save_contacts_cache(path, c.to_host(norms=norms, resolution_bp=int(res_kb) * 1000, window_start=windows[chrom]))
+        lines.append({"chrom": chrom, "records": c.M, "text_bytes": c.text_info["n_bytes"],
+                      "host_parsed_lines": int(c.text_info["slow_lines"].size), "windows": int(windows[chrom].size),
+                      "norms": sorted(norms), "cache": path, "seconds": round(time.perf_counter() - t0, 3)})
+        print(json.dumps(lines[-1]), flush=True)
+    return lines
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--hic-root", required=True)
+    ap.add_argument("--cell", required=True, help="the cell type: <hic_root>/<cell>_combined")
+    ap.add_argument("--resolution-kb", default="1")
+    ap.add_argument("--bed", required=True, help="the windows bed (windows.bed or chipseq_windows.bed of the reference)")
+    ap.add_argument("--chroms", required=True, help="comma-separated")
+    ap.add_argument("--out", required=True, help="the directory of the caches (train's -hic_contacts)")
+    ap.add_argument("--chunk-bytes", type=int, default=None)
+    opt = ap.parse_args(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/hic_ingest.py needs a GPU")
+    return ingest(opt.hic_root, opt.cell, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, chunk_bytes=opt.chunk_bytes)
+
+
+if __name__ == "__main__":
+    main()
