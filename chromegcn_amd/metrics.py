@@ -47,7 +47,8 @@ def multilabel_metrics(probs: torch.Tensor, targets: torch.Tensor, fdr_cutoff: f
     'auroc', 'aupr', 'recall_at_fdr', 'average_precision'.
     Scores are taken for probabilities first (non-negative: 32-bit keys and the library's own segmented radix sort,
     cgcn_multilabel_metrics_nonneg); if the device reports a negative score or a NaN the general path (any float scores,
-    64-bit keys) runs instead -- same results either way where both apply."""
+    64-bit keys) runs instead -- same results either way where both apply.
+    `fdr_cutoff` is rounded to float32 on the way in (the C ABI takes a float): 0.1 means float32(0.1)."""
     C = probs.shape[1]
     flat = _metrics_raw(probs, targets, fdr_cutoff, nonneg=True)
     if int(flat[4 * C:].view(torch.int32).item()) != 0:
