@@ -199,7 +199,8 @@ __device__ __forceinline__ void chan_combine(float& nA, float& meanA, float& m2A
 // Counter-based dropout RNG: a mask bit is a pure function of (seed, step counter, stream id, element
 // index), so the backward regenerates the forward's mask instead of storing it.  rng_state lives in
 // device memory ([0] = seed, [1] = step counter) so that a captured HIP graph sees a fresh counter on
-// every replay.
+// every replay.  tests/dropout_ref.py restates mix32, dropout_key, dropout_keep, dropout_threshold and the keep scale in numpy
+// and every kernel's mask is tested against it bit for bit: the two move together.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;

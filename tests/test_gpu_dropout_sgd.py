@@ -9,6 +9,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import chromegcn_amd as C
+import dropout_ref
 from chromegcn_amd import graph as G
 from chromegcn_amd import ops
 from oracle import chromegcn_oracle as O
@@ -52,6 +53,9 @@ def test_two_layer_model_with_dropout_matches_float64_with_explicit_masks(scale)
     mask1 = _probe_layer_mask(S, n, d, p, m._rng_state, 1).double()
     maskh = _probe_mask(S * n, d, p, 77, 3).view(S, n, d).double()
     assert 0.7 < mask1.mean().item() < 0.9 and not torch.equal(mask1, maskh)
+    # the probed masks are the stated ones (tests/dropout_ref.py): stream id 1 for layer 1's output, the head's own stream
+    np.testing.assert_array_equal(mask1.numpy() != 0, dropout_ref.mask(77, 3, 1, (S, n, d), p))
+    np.testing.assert_array_equal(maskh.numpy() != 0, dropout_ref.mask(77, 3, dropout_ref.HEAD_STREAM_ID, (S, n, d), p))
 
     # float64 restatement of ChromeModels.py:34-52 + finetune.py:43-45 with the masks made explicit
     x64 = x.double().requires_grad_(True)

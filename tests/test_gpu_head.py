@@ -111,6 +111,8 @@ def test_head_dropout_forward_and_backward_use_the_same_mask():
     x, tgt, bn, out = make(S, n, d, C, 9)
     mask = _probe_mask(S * n, d, p, 1234, 5).view(S, n, d).double()
     assert 0.6 < mask.mean().item() < 0.8
+    import dropout_ref   # the probed mask is the stated one (tests/dropout_ref.py)
+    np.testing.assert_array_equal(mask.numpy() != 0, dropout_ref.mask(1234, 5, dropout_ref.HEAD_STREAM_ID, (S, n, d), p))
     bn64, out64 = copy.deepcopy(bn).double().train(), copy.deepcopy(out).double()
     x64 = x.double().requires_grad_(True)
     logits = [out64(bn64(F.relu(x64[s])) * mask[s] / (1 - p)) for s in range(S)]
