@@ -39,6 +39,10 @@ _HEADER = {
     "cgcn_debug_layer_bwd_phases": (_c_int, "stream n:i S:i d:i rowptr_t col_t val_t row_scale X Z H gate W wg dXn dgate dX dHs "
                                             "dW db dwg dcg accumulate:i in_dropout_p:f rng_state in_stream_id:u head workspace "
                                             "workspace_bytes:z phases:i aux_t"),
+    "cgcn_layer_bwd_co": (_c_int, "stream n:i S:i d:i rowptr_t col_t val_t row_scale X Z H gate W wg dXn dgate dX dHs dW db "
+                                  "dwg dcg accumulate:i in_dropout_p:f rng_state in_stream_id:u head workspace "
+                                  "workspace_bytes:z aux_stream sgd aux_t companion"),
+    "cgcn_debug_layer_bwd_co_route": (_c_int, "n:i S:i d:i rowptr_t col_t val_t have_dX:i aux_t companion"),
     "cgcn_head_workspace_bytes": (_c_sz, "n:i S:i d:i C:i"),
     "cgcn_head_workspace_layout": (_c_int, "n:i S:i d:i C:i dym_offset:zp bnc_offset:zp part_offset:zp"),
     "cgcn_head_bwd_partials": (_c_int, "n:i"),
@@ -217,6 +221,12 @@ class SgdFuse(ctypes.Structure):
     _fields_ = [("param", _c_vp), ("grad", _c_vp), ("momentum_buf", _c_vp), ("count", ctypes.c_longlong),
                 ("lr", _c_float), ("momentum", _c_float), ("weight_decay", _c_float), ("grad_scale", _c_float),
                 ("nesterov", _c_int), ("rng_state", _c_vp)]
+
+
+class SpmmJob(ctypes.Structure):
+    """mirror of cgcn_spmm_job (include/chromegcn.h)"""
+    _fields_ = [("n", _c_int), ("S", _c_int), ("d", _c_int), ("rowptr", _c_vp), ("col", _c_vp), ("val", _c_vp),
+                ("row_scale", _c_vp), ("X", _c_vp), ("H", _c_vp), ("aux", _c_vp)]
 
 
 def ptr(t):

@@ -16,7 +16,7 @@
 //   accumulators -- or the fp32 MFMA chain v_mfma_f32_16x16x4_f32 (rounds 1-5; CGCN_PRODUCTS=fp32); d = 256 runs the chain.
 //   k_bwd_rowlocal256s      the same work at d = 256: column-slab workgroups, both products per 32-row tile
 //   k_reduce_partials       deterministic second stage of the column / dW sums
-//   k_bwd_sliced<S,D>       dX = mask ((1-g) dXn + Ahat^T dHs): feature-sliced gather + element-wise epilogue
+//   k_bwd_sliced<S,D>       dX = mask ((1-g) dXn + Ahat^T dHs): feature-sliced gather + element-wise epilogue (+ a companion aggregation)
 //
 // Reference semantics: models/SubLayers.py:42-52, models/ChromeModels.py:34-46 (forward);
 // SURVEY.md Appendix A (backward).
@@ -2481,27 +2481,20 @@ __device__ __forceinline__ f32x4 bandplus_sum(const f32x4* __restrict__ bt, int 
   return a;
 }
 
-// H = diag(rs) Ahat X, [S, n, D] -> [S, n, D]  (grid: NSL * ceil(n / 64) workgroups of 512)
-template <int S, int D, bool HAS_VAL, typename IT = int, bool BP = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6 : 8))) void k_aggregate_sliced(int n, const int* __restrict__ rowptr, const IT* __restrict__ col,
-                                                          const float* __restrict__ val, const float* __restrict__ rs,
-                                                          const float* __restrict__ X, float* __restrict__ H,
-                                                          const int* __restrict__ order,
-                                                          unsigned long long* __restrict__ zero_words, int zero_count) {
-  static_assert(!(BP && HAS_VAL), "the band-plus CSR holds unit entries");
+// H = diag(rs) Ahat X, [S, n, D] -> [S, n, D]: what workgroup b of NSL * ceil(n / 64) does (512 threads).  The body of
+// k_aggregate_sliced, and of the companion range of k_bwd_sliced's grid (below).  bt: the band window's LDS (BP only).
+template <int S, int D, bool HAS_VAL, typename IT, bool BP>
+__device__ __forceinline__ void aggregate_sliced_tile(int b, int n, const int* __restrict__ rowptr, const IT* __restrict__ col,
+                                                      const float* __restrict__ val, const float* __restrict__ rs,
+                                                      const float* __restrict__ X, float* __restrict__ H,
+                                                      const int* __restrict__ order, f32x4* __restrict__ bt) {
   constexpr int NSL = S * D / 32, QPR = D / 32;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // the accumulators of the statistics the row-local launch behind this one adds to (STAT_ACC_*): zeroed here, by the launch
-  // that precedes it in the same call, so that no launch of its own is needed
-  const int zblocks = (int)gridDim.x < 8 ? (int)gridDim.x : 8;
-  if (zero_words && (int)blockIdx.x < zblocks)
-    for (int i = (int)blockIdx.x * 512 + (int)threadIdx.x; i < zero_count; i += zblocks * 512) zero_words[i] = 0ull;
   int slice, tile;
-  sliced_block<NSL>(blockIdx.x, (n + 63) / 64, slice, tile);
+  sliced_block<NSL>(b, (n + 63) / 64, slice, tile);
   const size_t slice_el = (size_t)(slice / QPR) * n * D + (slice % QPR) * 32;
   const size_t lane_el = slice_el + (lane & 7) * 4;
   const SlicedTile t = sliced_tile(rowptr, order, n, tile, wave, lane);
-  __shared__ f32x4 bt[BP ? BANDPLUS_CHUNKS : 1];
   if (BP) {
     bandplus_stage(bt, X, slice_el, n, t.g0, D);
     __syncthreads();
@@ -2516,6 +2509,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
     if (SLICED_NT & 1) __builtin_nontemporal_store(acc * sc, (f32x4*)&H[lane_el + (size_t)i * D]);
     else *(f32x4*)&H[lane_el + (size_t)i * D] = acc * sc;
   }
+}
+
+// (grid: NSL * ceil(n / 64) workgroups of 512)
+template <int S, int D, bool HAS_VAL, typename IT = int, bool BP = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6 : 8))) void k_aggregate_sliced(int n, const int* __restrict__ rowptr, const IT* __restrict__ col,
+                                                          const float* __restrict__ val, const float* __restrict__ rs,
+                                                          const float* __restrict__ X, float* __restrict__ H,
+                                                          const int* __restrict__ order,
+                                                          unsigned long long* __restrict__ zero_words, int zero_count) {
+  static_assert(!(BP && HAS_VAL), "the band-plus CSR holds unit entries");
+  // the accumulators of the statistics the row-local launch behind this one adds to (STAT_ACC_*): zeroed here, by the launch
+  // that precedes it in the same call, so that no launch of its own is needed
+  const int zblocks = (int)gridDim.x < 8 ? (int)gridDim.x : 8;
+  if (zero_words && (int)blockIdx.x < zblocks)
+    for (int i = (int)blockIdx.x * 512 + (int)threadIdx.x; i < zero_count; i += zblocks * 512) zero_words[i] = 0ull;
+  __shared__ f32x4 bt[BP ? BANDPLUS_CHUNKS : 1];
+  aggregate_sliced_tile<S, D, HAS_VAL, IT, BP>(blockIdx.x, n, rowptr, col, val, rs, X, H, order, bt);
 }
 
 // Horizontal fusion: the workgroups past the gather tiles of the layer backward's last launch (k_bwd_sliced, k_bwd_band)
@@ -2550,6 +2560,27 @@ __device__ __forceinline__ void bwd_riders(int extra, int n, int P, const float*
   sgd_other_elements(sg, extra - head_slabs, D, dW, db, dwg, dcg);
 }
 
+// The companion aggregation of a k_bwd_sliced launch (cgcn_layer_bwd_co): a second block range [start, start + blocks) of the
+// same grid whose workgroups do what k_aggregate_sliced does for ANOTHER problem (in the engine: H1 = Ahat X0 of the next
+// chromosome, which depends on nothing the step computes), so that aggregation costs no launch boundary of its own -- a launch
+// floor plus the drain of this launch's dX stores (profiles/r04_launch_floor.txt).  Same template instance as the main
+// gather; `start` is a multiple of 8, so workgroup start + e runs on XCD e mod 8 like workgroup e of k_aggregate_sliced's
+// own grid (slice <-> XCD).  Nothing in the launch waits for these workgroups and they wait for nothing.
+// riders: the workgroups [riders, riders_end) are the riders (bwd_riders).  blocks == 0: no companion.
+#ifndef CO_AGG_LAST
+#define CO_AGG_LAST 0   // 1: A/B build, the companion range behind the riders instead of in front of them (layer_bwd_impl)
+#endif
+struct CoAgg {
+  int n, start, blocks, riders, riders_end;
+  const int* rowptr;
+  const void* col;   // the main gather's index type
+  const float* val;
+  const float* rs;
+  const float* X;
+  float* H;
+  const int* order;
+};
+
 // ------------------------------------------------------------------------------------------
 // k_bwd_sliced: dX = mask * ((1-g) dXn + Ahat^T dHs), dHs = diag(rs) dU W^T from k_bwd_rowlocal: the aggregation over
 // the transposed adjacency with an element-wise epilogue, feature-sliced (above).
@@ -2565,13 +2596,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
                                                     const float* __restrict__ part, float* __restrict__ dW,
                                                     float* __restrict__ db, float* __restrict__ dwg,
                                                     float* __restrict__ dcg, int accumulate, SgdFuse sg, int reduce_slabs,
-                                                    const int* __restrict__ order, HeadApply hp, int head_slabs) {
+                                                    const int* __restrict__ order, HeadApply hp, int head_slabs, CoAgg co) {
   // BP: one LDS pool serves the band window of a gather workgroup and the staging of a rider workgroup (never both)
   constexpr int RIDER_STAGE = 4 * (512 / HEAD_STAT_COLS) * (HEAD_STAT_COLS + 1) * (int)sizeof(double) / 16;
   __shared__ f32x4 bt[BP ? (BANDPLUS_CHUNKS > RIDER_STAGE ? BANDPLUS_CHUNKS : RIDER_STAGE) : 1];
   if ((int)blockIdx.x >= gather_blocks) {
+    const int b = (int)blockIdx.x;
+    if ((unsigned)(b - co.start) < (unsigned)co.blocks) {   // the companion aggregation: independent of everything else here
+      aggregate_sliced_tile<S, D, HAS_VAL, IT, BP>(b - co.start, co.n, co.rowptr, (const IT*)co.col, co.val, co.rs, co.X, co.H, co.order, bt);
+      return;
+    }
 #ifndef BSX_NORIDERS   // (decomposition build, profiles/r06_bwd_sliced_gap.txt: the riders return at once -- gradients are garbage)
-    bwd_riders<S, D, BP>((int)blockIdx.x - gather_blocks, n, P, part, dW, db, dwg, dcg, accumulate, sg, reduce_slabs, hp, head_slabs, bt);
+    if (b >= co.riders && b < co.riders_end)   // (what is left are the workgroups that pad the companion range to a multiple of 8)
+      bwd_riders<S, D, BP>(b - co.riders, n, P, part, dW, db, dwg, dcg, accumulate, sg, reduce_slabs, hp, head_slabs, bt);
 #endif
     return;
   }
@@ -3125,8 +3162,8 @@ static void launch_band_aggregate(hipStream_t st, int n, int S, int d, const flo
   else hipLaunchKernelGGL((k_band_aggregate<2, 256, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc);
 }
 
-int cgcn_spmm(cgcn_stream_t stream, int n_rows, int n_cols, int S, int d, const int32_t* rowptr, const int32_t* col,
-              const float* val, const float* row_scale, const float* X, float* Y, const cgcn_graph_aux* aux) {
+// cgcn_spmm's argument checks (n_rows == 0: nothing to check, nothing to do)
+static int spmm_check(int n_rows, int n_cols, int S, int d, const int32_t* rowptr, const int32_t* col, const float* X, const float* Y) {
   const int nmax = n_rows > n_cols ? n_rows : n_cols;
   if (nmax < 0) return CGCN_ERR_BAD_ARG;
   // the bare aggregation takes any width that is a multiple of 4 (k_spmm_any); S*D in {128, 256, 512} has tuned kernels
@@ -3135,6 +3172,18 @@ int cgcn_spmm(cgcn_stream_t stream, int n_rows, int n_cols, int S, int d, const 
   if (n_rows == 0) return CGCN_OK;
   if (!rowptr || !col || !X || !Y || X == Y) return CGCN_ERR_BAD_ARG;
   if (misaligned16(X) || misaligned16(Y)) return CGCN_ERR_BAD_ARG;
+  return CGCN_OK;
+}
+// cgcn_spmm on a square operator runs k_aggregate_sliced: a table too large for the L2s, a hub graph, a band-plus graph
+static inline bool spmm_sliced_route(int n, int S, int d, const float* val, const cgcn_graph_aux* aux) {
+  return (d == 128 || d == 256) && !band_graph(aux, val) &&
+         ((double)n * S * d * 4.0 >= (double)g_fwd_split_bytes.load() || hub_graph(aux) || bandplus_graph(aux, val));
+}
+
+int cgcn_spmm(cgcn_stream_t stream, int n_rows, int n_cols, int S, int d, const int32_t* rowptr, const int32_t* col,
+              const float* val, const float* row_scale, const float* X, float* Y, const cgcn_graph_aux* aux) {
+  const int crc = spmm_check(n_rows, n_cols, S, d, rowptr, col, X, Y);
+  if (crc || n_rows == 0) return crc;
   hipStream_t st = (hipStream_t)stream;
   if (!(d == 128 || d == 256)) {
     const long long rows = (long long)S * n_rows;
@@ -3146,7 +3195,7 @@ int cgcn_spmm(cgcn_stream_t stream, int n_rows, int n_cols, int S, int d, const 
     launch_band_aggregate(st, n_rows, S, d, row_scale, X, Y);
     return launch_status();
   }
-  if (n_rows == n_cols && ((double)n_rows * S * d * 4.0 >= (double)g_fwd_split_bytes.load() || hub_graph(aux) || bandplus_graph(aux, val))) {
+  if (n_rows == n_cols && spmm_sliced_route(n_rows, S, d, val, aux)) {
     // square operator on a table too large for the L2s (or a band-plus graph): the feature-sliced aggregation (see k_aggregate_sliced)
     const int gblocks = (S * d / 32) * ((n_rows + 63) / 64);
     const SlicedCsr c = sliced_csr(aux, rowptr, col, val, n_cols);
@@ -3354,6 +3403,15 @@ size_t cgcn_layer_bwd_workspace_bytes(int n, int S, int d) {
   return (size_t)bwd_partials(n, S, d) * ((size_t)d * d + 2 * d + 4) * sizeof(float);
 }
 
+// A companion aggregation rides in the gather launch when it is the SAME template instance of the sliced kernels as the main
+// gather (main: its SlicedCsr): equal S and d with at most 8 column slices, the same index type, value form and band-plus form --
+// and when cgcn_spmm would run k_aggregate_sliced for it, so that riding never changes a bit of what the caller gets.
+static bool companion_rides(const cgcn_spmm_job* co, int S, int d, const SlicedCsr& main) {
+  if (co->S != S || co->d != d || S * d / 32 > 8 || !spmm_sliced_route(co->n, S, d, co->val, co->aux)) return false;
+  const SlicedCsr cc = sliced_csr(co->aux, co->rowptr, co->col, co->val, co->n);
+  return cc.bp == main.bp && (cc.col16 != nullptr) == (main.col16 != nullptr) && (cc.val != nullptr) == (main.val != nullptr);
+}
+
 // phases: bit 0 = the row-local launch (k_bwd_rowlocal_ring / k_bwd_rowlocal256s), bit 1 = the launch that follows it
 // (k_bwd_sliced with the second-stage sums / the optimizer step in its trailing workgroups, or k_reduce_partials).
 // cgcn_layer_bwd runs both; cgcn_debug_layer_bwd_phases lets a profiler time them one at a time.
@@ -3363,10 +3421,19 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
                           float* dHs, float* dW, float* db, float* dwg, float* dcg, int accumulate, float in_dropout_p,
                           const unsigned long long* rng_state, unsigned int in_stream_id, const cgcn_head_grad* head,
                           void* workspace, size_t workspace_bytes, cgcn_stream_t aux_stream, const cgcn_sgd_fuse* sgd,
-                          int phases, const cgcn_graph_aux* aux_t) {
+                          int phases, const cgcn_graph_aux* aux_t, const cgcn_spmm_job* co = nullptr) {
   int rc = check_shape(n, S, d);
   if (rc) return rc;
   if (!rowptr_t || !col_t || !X || !Z || !H || !gate || !W || !wg || !dW || !db || !dwg || !dcg) return CGCN_ERR_BAD_ARG;
+  if (co) {   // the companion aggregation (cgcn_layer_bwd_co): cgcn_spmm's checks, and an output that is no operand of this call
+    if ((rc = spmm_check(co->n, co->n, co->S, co->d, co->rowptr, co->col, co->X, co->H))) return rc;
+    if (co->n == 0) co = nullptr;
+  }
+  if (co) {
+    const void* mine[] = {X, Z, H, gate, W, wg, dXn, dgate, dX, dHs, dW, db, dwg, dcg, workspace, row_scale};
+    for (const void* q : mine)
+      if (q && q == (const void*)co->H) return CGCN_ERR_BAD_ARG;
+  }
   if (dX && !dHs) return CGCN_ERR_BAD_ARG;  // the gather's operand; without dX it is optional (NULL: not computed)
   SgdFuse sg = {nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0.f, 1.f, 0, nullptr};
   if (sgd) {
@@ -3462,9 +3529,14 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
     if ((rc = launch_status())) return rc;
     if (rs_stream != st && hipEventRecord(ev_join, rs_stream) != hipSuccess) return CGCN_ERR_LAUNCH;
   }
+  // a companion that cannot ride in this call's gather launch is launched right behind it: the caller gets cgcn_spmm's result
+  // either way
+  auto companion_alone = [&]() -> int {
+    return co ? cgcn_spmm(stream, co->n, co->n, co->S, co->d, co->rowptr, co->col, co->val, co->row_scale, co->X, co->H, co->aux) : CGCN_OK;
+  };
   if (n == 0 || !dX) {
     if (rs_stream != st && hipStreamWaitEvent(st, ev_join, 0) != hipSuccess) return CGCN_ERR_LAUNCH;
-    return CGCN_OK;  // parameter gradients only (the input is a leaf nobody differentiates)
+    return companion_alone();  // parameter gradients only (the input is a leaf nobody differentiates)
   }
   const int blocks = (S * d / 32) * ((n + 63) / 64);   // slices x 64-row tiles (k_bwd_sliced)
   if (head) dXn = dX;  // k_bwd_rowlocal left dL/dXn there; each thread reads its elements before overwriting them
@@ -3480,40 +3552,58 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
     else if (S == 1 && d == 256) CALLB(1, 256);
     else CALLB(2, 256);
 #undef CALLB
-  } else if (bandplus_graph(aux_t, val_t)) {   // 'both': the unit-entry CSR + the band window from LDS (BP)
-    const SlicedCsr c = sliced_csr(aux_t, rowptr_t, col_t, val_t, n);
-#define CALLBP(S_, D_, IT_, COL_)                                                                                    \
-  hipLaunchKernelGGL((k_bwd_sliced<S_, D_, false, IT_, true>), dim3(blocks + (fuse_reduce ? rslabs : 0) + head_slabs_g + sgd_blocks), dim3(512), 0, \
-                     st, n, c.rowptr, COL_, nullptr, dHs, dXn, gate, dX, ks, th, rng_state, in_stream_id, blocks, P,  \
-                     part, dW, db, dwg, dcg, accumulate, sg, fuse_reduce ? rslabs : 0, c.order, hp, head_slabs_g)
-#define CALLBP16(S_, D_) CALLBP(S_, D_, uint16_t, c.col16)
-#define CALLBP32(S_, D_) CALLBP(S_, D_, int, c.col)
-    if (c.col16) { if (S == 1 && d == 128) CALLBP16(1, 128); else if (S == 2 && d == 128) CALLBP16(2, 128); else if (S == 1 && d == 256) CALLBP16(1, 256); else CALLBP16(2, 256); }
-    else { if (S == 1 && d == 128) CALLBP32(1, 128); else if (S == 2 && d == 128) CALLBP32(2, 128); else if (S == 1 && d == 256) CALLBP32(1, 256); else CALLBP32(2, 256); }
-#undef CALLBP16
-#undef CALLBP32
-#undef CALLBP
-  } else if (const uint16_t* col16_t = use_col16(aux_t, val_t, n)) {
-#define CALL16(S_, D_)                                                                                               \
-  hipLaunchKernelGGL((k_bwd_sliced<S_, D_, false, uint16_t>), dim3(blocks + (fuse_reduce ? rslabs : 0) + head_slabs_g + sgd_blocks), dim3(512), 0, \
-                     st, n, rowptr_t, col16_t, val_t, dHs, dXn, gate, dX, ks, th, rng_state, in_stream_id, blocks, P, \
-                     part, dW, db, dwg, dcg, accumulate, sg, fuse_reduce ? rslabs : 0, row_order(aux_t), hp, head_slabs_g)
-    if (S == 1 && d == 128) CALL16(1, 128);
-    else if (S == 2 && d == 128) CALL16(2, 128);
-    else if (S == 1 && d == 256) CALL16(1, 256);
-    else CALL16(2, 256);
-#undef CALL16
   } else {
-#define CALL(S_, D_, V_)                                                                                             \
-  hipLaunchKernelGGL((k_bwd_sliced<S_, D_, V_, int>), dim3(blocks + (fuse_reduce ? rslabs : 0) + head_slabs_g + sgd_blocks), dim3(512), 0, \
-                     st, n, rowptr_t, col_t, val_t, dHs, dXn, gate, dX, ks, th, rng_state, in_stream_id, blocks, P,  \
-                     part, dW, db, dwg, dcg, accumulate, sg, fuse_reduce ? rslabs : 0, row_order(aux_t), hp, head_slabs_g)
-    DISPATCH_SDV(S, d, val_t != nullptr, CALL);
+    // the arrays k_bwd_sliced walks: 'both' graphs the unit-entry CSR (+ the band window from LDS, BP), 16-bit indices
+    // when the graph carries them
+    const SlicedCsr c = sliced_csr(aux_t, rowptr_t, col_t, val_t, n);
+    const int nriders = (fuse_reduce ? rslabs : 0) + head_slabs_g + sgd_blocks;
+    CoAgg ca = {0, 0, 0, blocks, blocks + nriders, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int grid = blocks + nriders;
+    if (co && rs_stream == st && companion_rides(co, S, d, c)) {
+      const SlicedCsr cc = sliced_csr(co->aux, co->rowptr, co->col, co->val, co->n);
+      const int cblocks = (S * d / 32) * ((co->n + 63) / 64);
+      // the companion range starts at a multiple of 8 workgroups (slice <-> XCD); the workgroups in between return at once.
+      // Grid order (profiles/co_aggregation_ab.txt): [backward gather | companion | riders]; the A/B build puts the
+      // companion behind the riders (+0.26 % on the genome epoch, inside the spread)
+#if CO_AGG_LAST
+      ca.start = (blocks + nriders + 7) & ~7;
+#else
+      ca.start = (blocks + 7) & ~7;
+      ca.riders = ca.start + cblocks;
+      ca.riders_end = ca.riders + nriders;
+#endif
+      ca.n = co->n;
+      ca.blocks = cblocks;
+      ca.rowptr = cc.rowptr;
+      ca.col = cc.col16 ? (const void*)cc.col16 : (const void*)cc.col;
+      ca.val = cc.val;
+      ca.rs = co->row_scale;
+      ca.X = co->X;
+      ca.H = co->H;
+      ca.order = cc.order;
+      grid = (ca.start + cblocks > ca.riders_end) ? ca.start + cblocks : ca.riders_end;
+      co = nullptr;   // (rides: nothing to launch behind)
+    }
+#define BSL(S_, D_, V_, IT_, BP_, COL_)                                                                               \
+  hipLaunchKernelGGL((k_bwd_sliced<S_, D_, V_, IT_, BP_>), dim3(grid), dim3(512), 0, st, n, c.rowptr, COL_, c.val, dHs, dXn, gate, dX, \
+                     ks, th, rng_state, in_stream_id, blocks, P, part, dW, db, dwg, dcg, accumulate, sg, fuse_reduce ? rslabs : 0, \
+                     c.order, hp, head_slabs_g, ca)
+#define CALLBP16(S_, D_) BSL(S_, D_, false, uint16_t, true, c.col16)
+#define CALLBP32(S_, D_) BSL(S_, D_, false, int, true, c.col)
+#define CALL16(S_, D_) BSL(S_, D_, false, uint16_t, false, c.col16)
+#define CALL(S_, D_, V_) BSL(S_, D_, V_, int, false, c.col)
+    if (c.bp) { if (c.col16) SD4(CALLBP16); else SD4(CALLBP32); }
+    else if (c.col16) SD4(CALL16);
+    else DISPATCH_SDV(S, d, c.val != nullptr, CALL);
 #undef CALL
+#undef CALL16
+#undef CALLBP32
+#undef CALLBP16
+#undef BSL
   }
   if ((rc = launch_status())) return rc;
   if (rs_stream != st && hipStreamWaitEvent(st, ev_join, 0) != hipSuccess) return CGCN_ERR_LAUNCH;  // join
-  return CGCN_OK;
+  return companion_alone();
 }
 
 int cgcn_layer_bwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* rowptr_t, const int32_t* col_t,
@@ -3526,6 +3616,28 @@ int cgcn_layer_bwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* row
   return layer_bwd_impl(stream, n, S, d, rowptr_t, col_t, val_t, row_scale, X, Z, H, gate, W, wg, dXn, dgate, dX, dHs, dW, db,
                         dwg, dcg, accumulate, in_dropout_p, rng_state, in_stream_id, head, workspace, workspace_bytes,
                         aux_stream, sgd, 3, aux_t);
+}
+
+int cgcn_layer_bwd_co(cgcn_stream_t stream, int n, int S, int d, const int32_t* rowptr_t, const int32_t* col_t,
+                      const float* val_t, const float* row_scale, const float* X, const float* Z, const float* H,
+                      const float* gate, const float* W, const float* wg, const float* dXn, const float* dgate, float* dX,
+                      float* dHs, float* dW, float* db, float* dwg, float* dcg, int accumulate, float in_dropout_p,
+                      const unsigned long long* rng_state, unsigned int in_stream_id, const cgcn_head_grad* head,
+                      void* workspace, size_t workspace_bytes, cgcn_stream_t aux_stream, const cgcn_sgd_fuse* sgd,
+                      const cgcn_graph_aux* aux_t, const cgcn_spmm_job* companion) {
+  return layer_bwd_impl(stream, n, S, d, rowptr_t, col_t, val_t, row_scale, X, Z, H, gate, W, wg, dXn, dgate, dX, dHs, dW, db,
+                        dwg, dcg, accumulate, in_dropout_p, rng_state, in_stream_id, head, workspace, workspace_bytes,
+                        aux_stream, sgd, 3, aux_t, companion);
+}
+
+int cgcn_debug_layer_bwd_co_route(int n, int S, int d, const int32_t* rowptr_t, const int32_t* col_t, const float* val_t,
+                                  int have_dX, const cgcn_graph_aux* aux_t, const cgcn_spmm_job* companion) {
+  int rc = check_shape(n, S, d);
+  if (rc) return rc;
+  if (!companion) return 0;
+  if ((rc = spmm_check(companion->n, companion->n, companion->S, companion->d, companion->rowptr, companion->col, companion->X, companion->H))) return rc;
+  if (n == 0 || companion->n == 0 || !have_dX || band_graph(aux_t, val_t)) return 0;
+  return companion_rides(companion, S, d, sliced_csr(aux_t, rowptr_t, col_t, val_t, n)) ? 1 : 0;
 }
 
 int cgcn_debug_layer_bwd_phases(cgcn_stream_t stream, int n, int S, int d, const int32_t* rowptr_t, const int32_t* col_t,

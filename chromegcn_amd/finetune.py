@@ -173,6 +173,14 @@ class GCNStage:
         # per chromosome, when the predictions stay on the device; CGCN_EPOCH_GRAPH=0 / epoch_graph=False = one graph per
         # chromosome (profiles/r04_epoch_graph_experiment.txt)
         self.epoch_graph = epoch_graph if epoch_graph is not None else os.environ.get("CGCN_EPOCH_GRAPH", "1") != "0"
+        # inside that graph (training, input_grad, no cached aggregation, two layers or more): chromosome c + 1's first
+        # aggregation H1 = A X0 -- no parameter enters it -- travels in the last launch of chromosome c's step, the first layer's
+        # backward gather (cgcn_layer_bwd_co), instead of being the first launch of its own step: one launch boundary fewer
+        # per chromosome, same kernels' arithmetic, same bits, every aggregation still recomputed every step
+        # (profiles/co_aggregation_ab.txt).  CGCN_CO_AGG=0 = the serial order.
+        self.co_aggregation = os.environ.get("CGCN_CO_AGG", "1") != "0"
+        self._h1_co: Dict[str, torch.Tensor] = {}        # per chromosome: the buffer its H1 is handed over in
+        self._h1_handoff: Dict[str, dict] = {}           # while an epoch body runs: chromosomes whose H1 is already there
         # where a split's predictions are assembled in a multi-rank run: "all" = on every rank (every rank's run_split
         # returns the whole split, like a single process), "rank0" = on rank 0 only, over direct point-to-point sends
         # (what nn.DataParallel does with the replicas' outputs, main.py:92-94: gathered on device 0; the other ranks'
@@ -245,6 +253,7 @@ class GCNStage:
         """forget every captured HIP graph (and the memory pool they shared, which dies with the last of them)"""
         self._graphs.clear()
         self._pool = None
+        self._h1_co.clear()   # (only the graphs read the hand-over buffers)
 
     # ------------------------------------------------------------------ data
     def add_chromosome(self, name: str, feats: Dict[str, torch.Tensor], hic=None, defer: bool = False):
@@ -570,7 +579,7 @@ class GCNStage:
         slot = self._arena["slots"][c.name] if self._arena is not None else None
         if self.fused_head and hasattr(self.model, "forward_loss"):
             loss, probs, _ = self.model.forward_loss(x, c.graph, c.target,   # fused head + loss kernels
-                                                     h1_cache=c.h1 if self.cache_input_aggregation else None,
+                                                     h1_cache=self._h1_handoff.get(c.name, c.h1 if self.cache_input_aggregation else None),
                                                      out_slots=slot, stat_acc=c.stat_acc)
             return loss, probs
         logits, _ = self.model.forward_strands(x, c.graph)
@@ -583,12 +592,43 @@ class GCNStage:
             slot["loss"].copy_(loss.detach().view(1))
         return loss, slot["probs"]
 
-    def _fwd_bwd_step(self, c: _Chrom):
+    def _co_agg_plan(self, cs):
+        """for every chromosome of a captured training split: does the step BEFORE it carry its first aggregation
+        (co_aggregation)?  Those whose first layer takes the two-launch forward -- the companion is then exactly the
+        aggregation launch the layer would have made itself, and the layer streams its result like a cached H1; a chromosome
+        on the one-launch route keeps it, and so does the first of the split.  Allocates the hand-over buffers."""
+        plan = [False] * len(cs)
+        if not (self.co_aggregation and self.input_grad and not self.cache_input_aggregation and self.fused_head
+                and hasattr(self.model, "forward_loss") and getattr(self.model, "n_layers", 0) >= 2):
+            return plan
+        for k in range(1, len(cs)):
+            cc = cs[k]
+            S, n, d = cc.x.shape
+            plan[k] = _lib_mod.query("cgcn_debug_layer_fwd_route", n=n, S=S, d=d, aux=G.aux_ptr(cc.graph.col), colstats_rows=0) == 1
+            buf = self._h1_co.get(cc.name)
+            if plan[k] and (buf is None or buf.shape != cc.x.shape or buf.device != cc.x.device):
+                self._h1_co[cc.name] = torch.empty_like(cc.x)
+        return plan
+
+    def _fwd_bwd_step(self, c: _Chrom, co_next: Optional[_Chrom] = None):
         """forward + backward + optimizer step of one chromosome (finetune.py:38-49).  With the fused SGD the step
         rides in the last backward launch (cgcn_sgd_fuse: the first layer's gather kernel -- or, when nobody wants
         d loss / d features, its partial-sum launch -- carries it in extra workgroups) instead of being a launch of
-        its own."""
+        its own.  co_next: the chromosome whose first aggregation that launch takes along (_co_agg_plan)."""
         from . import ops
+        if co_next is not None:
+            buf = self._h1_co[co_next.name]
+            ops._co_agg = {"job": ops.spmm_job(co_next.x, co_next.graph, buf), "done": False}
+            try:
+                out = self._fwd_bwd_step(c)
+                if not ops._co_agg["done"]:   # (a model whose backward never reached the first layer's call)
+                    g = co_next.graph
+                    _lib_mod.call("cgcn_spmm", n_rows=g.n, n_cols=g.n, S=buf.shape[0], d=buf.shape[2], rowptr=g.rowptr, col=g.col,
+                              val=g.val, row_scale=g.row_scale, X=co_next.x, Y=buf, aux=G.aux_ptr(g.col))
+            finally:
+                ops._co_agg = None
+            self._h1_handoff[co_next.name] = {"h": buf}
+            return out
         fuse = self._fused == "sgd" and getattr(self.model, "_grad_sink", False) and getattr(self.model, "n_layers", 0) >= 1
         if fuse:
             g = self.optimizer.param_groups[0]
@@ -659,12 +699,17 @@ class GCNStage:
         was_training = self.model.training
         self.model.train(kind not in ("eval", "epoch_eval"))
         snap = self._snapshot()
+        co_plan = self._co_agg_plan(c) if kind == "epoch" else None
 
         def body(collective=True):
             if kind in ("epoch", "epoch_eval"):   # c: the split's chromosomes; their steps one after the other in ONE graph
                 out = None
-                for cc in c:
-                    out = self._fwd_bwd_step(cc) if kind == "epoch" else self._eval(cc) + (None,)
+                try:
+                    for k, cc in enumerate(c):
+                        nxt = c[k + 1] if (co_plan is not None and k + 1 < len(c) and co_plan[k + 1]) else None
+                        out = self._fwd_bwd_step(cc, nxt) if kind == "epoch" else self._eval(cc) + (None,)
+                finally:
+                    self._h1_handoff.clear()
                 return out
             if kind == "eval":
                 loss, probs = self._eval(c)

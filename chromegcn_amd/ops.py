@@ -113,6 +113,19 @@ def _sgd_fuse_arg(layer_id, sink):
                         _lib.ptr(rq["rng_state"]))
 
 
+# Set by the stage engine around one chromosome's step inside a captured epoch (finetune.GCNStage, CGCN_CO_AGG): the NEXT
+# chromosome's first aggregation H1 = A X0 as a cgcn_spmm_job {"job": _lib.SpmmJob, "done": False}.  The first layer's
+# backward -- the last launch of the step -- takes it along (cgcn_layer_bwd_co) and marks it done.
+_co_agg = None
+
+
+def spmm_job(x, graph, h):
+    """the cgcn_spmm_job  h = diag(row_scale) A x  on `graph` (x, h: dense [S, n, d]; the caller keeps them alive)"""
+    S, n, d = x.shape
+    return _lib.SpmmJob(n, S, d, _lib.ptr(graph.rowptr), _lib.ptr(graph.col), _lib.ptr(graph.val), _lib.ptr(graph.row_scale),
+                        x.data_ptr(), h.data_ptr(), G.aux_ptr(graph.col))
+
+
 # The one call site of each launch, shared with torch_ops.py.  Inputs arrive dense (_dense, _layer_params, _head_params);
 # csr / csr_t: (rowptr, col, val, row_scale) of the graph and (rowptr_t, col_t, val_t, row_scale) of its transpose.
 def _layer_params(weight, bias, gate_w, gate_b):
@@ -150,10 +163,16 @@ def layer_bwd(x, z, h, gate, weight, wg, csr_t, dx, dhs, dropout_in, rng_state, 
     ws = _lib.layer_bwd_workspace(n, S, d, x.device)
     sgd = _sgd_fuse_arg(layer_id, fuse_sink) if aux_stream is None else None
     rowptr_t, col_t, val_t, row_scale = csr_t
-    _lib.call("cgcn_layer_bwd", n=n, S=S, d=d, rowptr_t=rowptr_t, col_t=col_t, val_t=val_t, row_scale=row_scale, X=x, Z=z,
-              H=h, gate=gate, W=weight, wg=wg, dXn=dxn, dgate=dgate, dX=dx, dHs=dhs, dW=dw, db=db, dwg=dwg, dcg=dcg,
-              accumulate=0, in_dropout_p=float(dropout_in), rng_state=rng_state, in_stream_id=max(layer_id - 1, 0),
-              head=head, workspace=ws, workspace_bytes=ws.numel(), aux_stream=aux_stream, sgd=sgd, aux_t=G.aux_ptr(col_t))
+    co = _co_agg if (layer_id == 1 and _co_agg is not None and not _co_agg["done"]) else None
+    args = dict(n=n, S=S, d=d, rowptr_t=rowptr_t, col_t=col_t, val_t=val_t, row_scale=row_scale, X=x, Z=z,
+                H=h, gate=gate, W=weight, wg=wg, dXn=dxn, dgate=dgate, dX=dx, dHs=dhs, dW=dw, db=db, dwg=dwg, dcg=dcg,
+                accumulate=0, in_dropout_p=float(dropout_in), rng_state=rng_state, in_stream_id=max(layer_id - 1, 0),
+                head=head, workspace=ws, workspace_bytes=ws.numel(), aux_stream=aux_stream, sgd=sgd, aux_t=G.aux_ptr(col_t))
+    if co is None:
+        _lib.call("cgcn_layer_bwd", **args)
+    else:
+        _lib.call("cgcn_layer_bwd_co", companion=co["job"], **args)
+        co["done"] = True
     if sgd is not None:
         _sgd_fuse["done"] = True
     return dw, db, dwg, dcg

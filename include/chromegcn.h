@@ -319,6 +319,48 @@ int cgcn_debug_layer_bwd_phases(cgcn_stream_t stream, int n, int S, int d,
                                 unsigned int in_stream_id, const cgcn_head_grad *head,
                                 void *workspace, size_t workspace_bytes, int phases, const cgcn_graph_aux *aux_t);
 
+/*
+ * cgcn_layer_bwd with a COMPANION aggregation: one more, independent cgcn_spmm -- H = diag(row_scale) Ahat X of another
+ * problem, cgcn_spmm's operands on a square operator -- enqueued by the same call.  The engine hands the first layer's
+ * backward of chromosome c (the last launch of its train step) the first aggregation of chromosome c + 1, which reads the
+ * graph and the input features only.  When the companion is the same instance of the feature-sliced kernels as the call's own
+ * gather over Ahat^T -- equal S and d with S*d/32 <= 8, the same index width, both with or both without explicit values,
+ * both or neither band-plus, and a problem for which cgcn_spmm takes the feature-sliced route -- its workgroups are a second
+ * block range of that gather launch: one launch boundary fewer, nothing waits for anything inside the launch.  In every other
+ * case (and without a gather launch: dX == NULL; with an aux_stream; on a band graph) the aggregation is launched on its own
+ * right behind.  Either way H holds, bit for bit, what cgcn_spmm(stream, n, n, S, d, ..., X, H, aux) gives, and every other
+ * output is cgcn_layer_bwd's.  companion == NULL: exactly cgcn_layer_bwd.
+ * CGCN_ERR_BAD_ARG / CGCN_ERR_UNSUPPORTED as cgcn_spmm for the companion's operands, and CGCN_ERR_BAD_ARG when companion->H
+ * is one of this call's own operands; nothing is launched then.  Additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing
+ * above changes.
+ * cgcn_debug_layer_bwd_co_route: 1 when that companion would ride in the gather launch of such a call on `stream` alone
+ * (have_dX: dX != NULL), 0 when it would be launched on its own, < 0: an error code.
+ */
+typedef struct cgcn_spmm_job {
+  int n, S, d;
+  const int32_t *rowptr;
+  const int32_t *col;
+  const float *val;         /* NULL = implicit unit values */
+  const float *row_scale;   /* NULL = 1 */
+  const float *X;           /* [S, n, d] */
+  float *H;                 /* [S, n, d], written */
+  const cgcn_graph_aux *aux;
+} cgcn_spmm_job;
+
+int cgcn_layer_bwd_co(cgcn_stream_t stream, int n, int S, int d,
+                      const int32_t *rowptr_t, const int32_t *col_t, const float *val_t, const float *row_scale,
+                      const float *X, const float *Z, const float *H, const float *gate,
+                      const float *W, const float *wg,
+                      const float *dXn, const float *dgate,
+                      float *dX, float *dHs, float *dW, float *db, float *dwg, float *dcg,
+                      int accumulate, float in_dropout_p, const unsigned long long *rng_state,
+                      unsigned int in_stream_id, const cgcn_head_grad *head,
+                      void *workspace, size_t workspace_bytes, cgcn_stream_t aux_stream,
+                      const cgcn_sgd_fuse *sgd, const cgcn_graph_aux *aux_t, const cgcn_spmm_job *companion);
+
+int cgcn_debug_layer_bwd_co_route(int n, int S, int d, const int32_t *rowptr_t, const int32_t *col_t, const float *val_t,
+                                  int have_dX, const cgcn_graph_aux *aux_t, const cgcn_spmm_job *companion);
+
 /* Bytes of scratch cgcn_head_fwd / cgcn_head_bwd need for (n, S, d, C).  0 on unsupported shapes. */
 size_t cgcn_head_workspace_bytes(int n, int S, int d, int C);
 
