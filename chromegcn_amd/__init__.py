@@ -2,13 +2,18 @@
 
 Public surface mirrors the reference modules it replaces (see layers.py / graph.py / finetune.py)."""
 from .ablation import label_pair_ablation  # noqa: F401
+from .embed import class_embeddings  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
+from .tsne import (TsneAffinities, joint_probabilities_host, kl_gradient_host, tsne_embed, tsne_embed_host,  # noqa: F401
+                   tsne_sweep)
 
 __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_graph", "process_graph",
            "upload", "as_graph", "FeatureCollector", "label_pair_ablation", "HicContacts",
            "build_hic_graph", "build_hic_graph_host", "expand_contacts_host", "contacts_from_text",
-           "parse_contacts_text_host", "release_text_staging", "windows_from_bed"]
+           "parse_contacts_text_host", "release_text_staging", "windows_from_bed", "class_embeddings",
+           "TsneAffinities", "tsne_embed", "tsne_sweep", "joint_probabilities_host",
+           "kl_gradient_host", "tsne_embed_host"]

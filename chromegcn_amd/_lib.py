@@ -95,6 +95,13 @@ _HEADER = {
     "cgcn_text_count": (_c_int, "stream text n_bytes:ll workspace workspace_bytes:z n_records"),
     "cgcn_text_parse": (_c_int, "stream text n_bytes:ll M:ll pos1_out pos2_out count_out flags flag_capacity:ll flag_totals "
                                 "workspace workspace_bytes:z"),
+    "cgcn_tsne_workspace_bytes": (_c_sz, "n:i"),
+    "cgcn_tsne_sqdist": (_c_int, "stream n:i d:i ld:i X D"),
+    "cgcn_tsne_affinities": (_c_int, "stream n:i ld:i D perplexity:f C beta"),
+    "cgcn_tsne_symmetrize": (_c_int, "stream n:i ld:i C P workspace workspace_bytes:z"),
+    "cgcn_tsne_gradient": (_c_int, "stream n:i ld:i P Y exaggeration:f grad want_kl:i workspace workspace_bytes:z"),
+    "cgcn_tsne_update": (_c_int, "stream n:i Y update gains grad momentum:f learning_rate:f have_kl:i record workspace "
+                                 "workspace_bytes:z"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

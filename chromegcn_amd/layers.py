@@ -174,6 +174,24 @@ class ChromeGCN(nn.Module):
         x, gates = self._gated_stack(x_fr, graph, self._step_rng())
         return self._head(x), gates
 
+    def hidden_strands(self, x_fr, adj):
+        """The hidden representation of every window: the output of the gated stack, [S, n, d] -- what `_head` consumes,
+        before its ReLU, so that `_head(hidden_strands(x, adj))` is `forward_strands(x, adj)[0]` in eval mode.
+        scripts/visualize.py:152-170 embeds an `all_single_class_z` that the reference never defines; this is the
+        definition chosen here (the last tensor the graph layers produce, the input of the classifier).
+        Always the eval forward (no dropout) without autograd, whatever the module's training flag, which it leaves alone."""
+        ops._require_cuda(x_fr, "x_fr")
+        graph = as_graph(adj, x_fr.device, n=x_fr.shape[1])
+        ops._check_feat(x_fr, graph, "x_fr")
+        with torch.no_grad():
+            x = ops._dense(x_fr.detach())
+            for k in range(1, self.n_layers + 1):
+                gc, wk = getattr(self, "GC%d" % k), getattr(self, "W%d" % k)
+                x, _ = ops.layer_fwd(x, ops._layer_params(gc.weight.detach(), gc.bias.detach(), wk.weight.detach(),
+                                                          wk.bias.detach()),
+                                     (graph.rowptr, graph.col, graph.val, graph.row_scale), None, None)
+        return x
+
     def forward_loss(self, x_fr, adj, target, h1_cache=None, out_slots=None, stat_acc=False):
         """The whole per-chromosome forward of the GCN stage (finetune.py:41-45,52) in fused kernels:
         gated stack on both strands, then ReLU/BatchNorm/dropout/Linear/strand-mean/BCE.  The last gated

@@ -739,6 +739,56 @@ int cgcn_text_parse(cgcn_stream_t stream, const void *text, long long n_bytes, l
                     int32_t *pos2_out, double *count_out, long long *flags, long long flag_capacity,
                     long long *flag_totals, void *workspace, size_t workspace_bytes);
 
+/*
+ * Exact t-SNE of n points into the plane (the class-embedding maps of scripts/visualize.py:148-188, which call scikit-learn's
+ * TSNE thirteen times; chromegcn_amd/tsne.py).  Additions to ABI 26 like the functions above; nothing
+ * above changes.  The objective is scikit-learn's method='exact' form (sklearn/manifold/_t_sne.py: _joint_probabilities,
+ * _kl_divergence at one degree of freedom, _gradient_descent), function by function.
+ *
+ * Shapes: 2 <= n, n * n < 2^31, d >= 4 and d % 4 == 0; anything else is CGCN_ERR_UNSUPPORTED, decided before any pointer is
+ * looked at.  Every n x n matrix (D, C, P) is row-major fp32 with the row pitch ld = (n + 3) & ~3 floats and a 16-byte
+ * aligned base; the columns n .. ld - 1 are never read for their value and never written.  X is [n, d] fp32, 16-byte aligned;
+ * Y, update, gains and grad are [n, 2] fp32.  eps = 2.220446049250313e-16 throughout.
+ * Enqueue only, no allocation, no sync; no atomics and a fixed reduction order in every kernel: the same inputs give the
+ * same bits.  One workspace of cgcn_tsne_workspace_bytes(n) bytes (0 for an unsupported n) serves every call; it carries
+ * Z and the KL row partials from cgcn_tsne_gradient to the cgcn_tsne_update behind it.
+ *
+ * cgcn_tsne_sqdist      D[i,j] = sum_k (x_ik - x_jk)^2 in fp32, in the difference form and one order over k: the diagonal is
+ *                       exactly 0 and D[i,j] == D[j,i] bit for bit.
+ * cgcn_tsne_affinities  the conditional row C[i,:] of _binary_search_perplexity: beta starts at 1, at most 100 steps, entropy
+ *                       H = log S + beta (sum_j D_ij e^(-beta D_ij)) / S with S = sum_{j != i} e^(-beta D_ij) (a zero S reads
+ *                       1e-8), stop at |H - log perplexity| <= 1e-5; beta doubles (H too large) or halves while the other
+ *                       bound is unknown, then moves to the midpoint.  The search is float64 on the fp32 D; perplexity is
+ *                       taken as the fp32 it is passed as.  C[i,j] = e^(-beta D_ij) / S as fp32 with the LAST EVALUATED beta,
+ *                       C[i,i] = 0; beta[i] (fp64) is that beta.
+ * cgcn_tsne_symmetrize  P = max((C + C^T) / sum (C + C^T), eps), the diagonal 0 (scikit-learn keeps the condensed form, which
+ *                       has none); the total in float64 in two stages.  P == C (in place) is allowed.
+ * cgcn_tsne_gradient    with w_ij = 1 / (1 + |y_i - y_j|^2): Z = sum_{i != j} w_ij (fp32 per row, float64 over rows, left in
+ *                       the workspace), then one pass over P: grad[i] = 4 sum_j (e P_ij - max(w_ij / Z, eps)) w_ij (y_i - y_j)
+ *                       with e = exaggeration, and when want_kl the row partials of
+ *                       KL = sum_ij e P_ij log(max(e P_ij, eps) / max(w_ij / Z, eps)).  P's diagonal must be 0.
+ * cgcn_tsne_update      _gradient_descent's body: gains += 0.2 where update * grad < 0, gains *= 0.8 elsewhere, floor 0.01;
+ *                       grad *= gains; update = momentum update - learning_rate grad; Y += update.  record (fp64 [4], device):
+ *                       {KL (NaN unless have_kl; the gradient call before it must have had want_kl), |gains * grad|_2 -- the
+ *                       norm _gradient_descent tests --, Z, 0}.  grad itself is left as it was.
+ * CGCN_ERR_BAD_ARG: a NULL or misaligned buffer, a perplexity that is not positive; CGCN_ERR_WORKSPACE: workspace_bytes below
+ * cgcn_tsne_workspace_bytes(n).
+ */
+size_t cgcn_tsne_workspace_bytes(int n);
+
+int cgcn_tsne_sqdist(cgcn_stream_t stream, int n, int d, int ld, const float *X, float *D);
+
+int cgcn_tsne_affinities(cgcn_stream_t stream, int n, int ld, const float *D, float perplexity, float *C, double *beta);
+
+int cgcn_tsne_symmetrize(cgcn_stream_t stream, int n, int ld, const float *C, float *P, void *workspace,
+                         size_t workspace_bytes);
+
+int cgcn_tsne_gradient(cgcn_stream_t stream, int n, int ld, const float *P, const float *Y, float exaggeration, float *grad,
+                       int want_kl, void *workspace, size_t workspace_bytes);
+
+int cgcn_tsne_update(cgcn_stream_t stream, int n, float *Y, float *update, float *gains, const float *grad, float momentum,
+                     float learning_rate, int have_kl, double *record, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
