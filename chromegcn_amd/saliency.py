@@ -15,11 +15,12 @@ from .graph import ChromGraph, as_graph
 
 def adjacency_saliency(model, x_f: torch.Tensor, x_r: torch.Tensor, adj, targets: torch.Tensor, normalize: bool = True):
     """Returns (graph, sal) with sal[k] the saliency of stored entry k of the graph's CSR (row-major).
-    model: chromegcn_amd.ChromeGCN; x_f, x_r: [n,d]; targets: [n,C] -- the arguments of scripts/visualize.py:37-49."""
+    model: chromegcn_amd.ChromeGCN; x_f, x_r: [n,d]; targets: [n,C] -- the arguments of scripts/visualize.py:37-49.
+    adj: a ChromGraph or a torch sparse COO tensor, symmetric or not, with or without explicit values: dL/dA_ij =
+    <dHs_i, X_j> holds for any A (the backward walks the transposed lists, the product the forward pattern), so the
+    reference's own call -- process_graph('both', ...), row-normalised and therefore asymmetric -- is served as it is."""
     graph: ChromGraph = as_graph(adj, x_f.device)
-    if not graph.symmetric and graph.val_t is not graph.val:
-        raise NotImplementedError("saliency is implemented for symmetric A-hat (every graph the reference writes)")
-    x = torch.stack([x_f, x_r]).detach().requires_grad_(True)
+    x =torch.stack([x_f, x_r]).detach().requires_grad_(True)
     tap = []
     ops._saliency_tap = tap
     try:

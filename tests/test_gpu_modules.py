@@ -7,6 +7,7 @@ import scipy.sparse as sp
 import torch
 
 import chromegcn_amd as C
+import saliency_ref as R
 from chromegcn_amd import graph as G, ops, synth
 from chromegcn_amd.finetune import GCNStage
 from oracle import chromegcn_oracle as O
@@ -20,7 +21,10 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
-@pytest.mark.parametrize("d_in,d_out", [(128, 128), (128, 256), (64, 192), (100, 36), (256, 128), (128, 4), (128, 103), (77, 1), (128, 130)])
+# d_out 260 / 320 / 516 / 1028: k_spmm_any walks 65 / 80 / 129 / 257 float4 column groups 64 at a time, i.e. takes 2 / 2 / 3 / 5
+# column passes (the last pass of 260, 516 and 1028 is a single lane wide); every other width here fits one pass
+@pytest.mark.parametrize("d_in,d_out", [(128, 128), (128, 256), (64, 192), (100, 36), (256, 128), (128, 4), (128, 103), (77, 1), (128, 130),
+                                        (128, 260), (128, 320), (64, 516), (32, 1028)])
 @pytest.mark.parametrize("adj_kind", ["hic", "both", "coo", "none"])
 def test_graph_convolution_module_matches_oracle(d_in, d_out, adj_kind):
     """layers.GraphConvolution.forward(input, adj, deg) = adj @ (input @ W) + b  (models/SubLayers.py:42-52), forward and
@@ -54,6 +58,36 @@ def test_graph_convolution_module_matches_oracle(d_in, d_out, adj_kind):
     np.testing.assert_allclose(xt.grad.cpu().numpy(), ds @ W.T, **TOL)
     np.testing.assert_allclose(gc.weight.grad.cpu().numpy(), x.astype(np.float64).T @ ds, atol=1e-4 * np.abs(x.astype(np.float64).T @ ds).max(), rtol=1e-4)
     np.testing.assert_allclose(gc.bias.grad.cpu().numpy(), gup.astype(np.float64).sum(0), atol=1e-4 * np.abs(gup.astype(np.float64).sum(0)).max(), rtol=1e-4)
+
+
+def _spmm_any_graph(name):
+    if name == "both_hub":           # explicit values 1 / 2 with a row scale, one row of 200 entries (four 64-entry chunks)
+        hic, hubs, _ = R.hub_hic(300, "both", lengths=(200,), empty_row=False)
+        h = G.normalize_graph("both", hic, 300)
+        assert h.val is not None and int(np.diff(h.rowptr)[hubs[0]]) == 200
+    elif name == "asymmetric_valued":   # negative and fractional values, no row scale, a transpose of its own
+        h = G.host_csr_from_matrix(R.asymmetric_valued(300, 0.04, 12, lengths=(65,), empty_row=17))
+        assert not h.symmetric and (h.val < 0).any()
+    else:                            # S * n = 34 000 rows > 4 waves x 8192 blocks: the waves of the capped launch go round again
+        h = G.normalize_graph("constant", None, 17000)
+    return h
+
+
+@pytest.mark.parametrize("name", ["both_hub", "asymmetric_valued", "band_17000"])
+def test_spmm_any_width_with_two_strands_past_one_column_pass(name):
+    """ops.spmm at S = 2 and width 320 (k_spmm_any: 80 column groups, two passes of its column loop) against float64 scipy,
+    forward and the gradient (the transposed lists, the same kernel)"""
+    S, d = 2, 320
+    h = _spmm_any_graph(name)
+    g = G.upload(h, DEV)
+    rng = np.random.RandomState(31)
+    x, dy = rng.randn(S, h.n, d).astype(np.float32), rng.randn(S, h.n, d).astype(np.float32)
+    xt = _dev(x).requires_grad_(True)
+    y = ops.spmm(xt, g)
+    y.backward(_dev(dy))
+    a = h.to_scipy().astype(np.float64)
+    np.testing.assert_allclose(y.detach().cpu().numpy(), np.stack([a @ x[s].astype(np.float64) for s in range(S)]), **TOL)
+    np.testing.assert_allclose(xt.grad.cpu().numpy(), np.stack([a.T @ dy[s].astype(np.float64) for s in range(S)]), **TOL)
 
 
 def test_graph_convolution_rejects_widths_the_kernels_cannot_serve_loudly():
