@@ -9,8 +9,9 @@
 //       the unablated forward's layer inputs:
 //         k_abl_layer  masked aggregation of the kept neighbours (plain form: the kept entries only, so a row that keeps
 //                      one of many neighbours has no cancellation; a row that keeps nothing is exactly zero, decided by
-//                      the kept count), then U = H W + b, tanh, gate and residual mix for the 2 x 16 rows of one
-//                      (u, 16 column labels) block in fp32 vector FMAs.  Layer 2 reads a neighbour's ablated layer-1
+//                      the kept count; the renormalisation is decided by the kept SUM, which stored zeros leave 0),
+//                      then U = H W + b, tanh, gate and residual mix for the 2 x 16 rows of one (u, 16 column labels)
+//                      block in fp32 vector FMAs.  Layer 2 reads a neighbour's ablated layer-1
 //                      value wherever it lies in P_i (and the row's own, as its residual input).
 //         k_abl_head   label i's head on those rows (ReLU, eval BatchNorm, one dot product per strand, strand mean,
 //                      sigmoid), a fixed-order mean over P_i, and M[i, j]
@@ -73,7 +74,8 @@ __global__ __launch_bounds__(ABL_NT) void k_abl_lists(int n, int Wd, const uint3
 
 // One gated layer for the instances (jb0 + jb, k), jb < ABL_JB, of row u = pos_list[k] (a row of P_i):
 //   H = rs' * sum over kept entries (u, v) of val_uv * X_v,  kept <=> v not in P_j  (j = cols[jb0 + jb]),
-//   rs' = row_scale[u] (1 if NULL) when nothing was removed, else 1 / (sum of the kept values), 0 when nothing is kept;
+//   rs' = row_scale[u] (1 if NULL) when nothing was removed, else 1 / (sum of the kept values); where that sum is 0 (stored
+//   zeros, or values that cancel) the reference's `s == 0 -> 1` leaves row_scale[u]; a row that keeps nothing is exactly 0;
 //   U = H W + b;  Z = tanh U;  g = sigmoid(Z . wg + cg);  X' = (1 - g) X_u + g Z.
 // X_v is X[s, v] (the unablated layer input) unless X_inst is given and v is in P_i: then the instance's own ablated
 // value X_inst[jb0 + jb, rank(v)].  Instance rows are [n_cols][n_pos][S][D].
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(ABL_NT) void k_abl_layer(int n, const int* __restri
   const float rs_u = row_scale ? row_scale[u] : 1.f;
 #pragma unroll
   for (int jb = 0; jb < ABL_JB; ++jb) {
-    const float sc = rem[jb] == 0 ? rs_u : (kept[jb] > 0 ? 1.f / wsum[jb] : 0.f);
+    const float sc = rem[jb] == 0 || wsum[jb] == 0.f ? rs_u : 1.f / wsum[jb];   // kept sum 0: the reference's s == 0 -> 1
 #pragma unroll
     for (int q = 0; q < EPT; ++q) hs[(jb * ABL_S + s) * D + c0 + q] = kept[jb] > 0 ? acc[jb][q] * sc : 0.f;
   }
@@ -293,7 +295,8 @@ __global__ __launch_bounds__(ABL_NT) void k_abl_mask(int n, const int* __restric
         ++kept;
       }
     }
-    rs_out[u] = rem == 0 ? (row_scale ? row_scale[u] : 1.f) : (kept > 0 ? 1.f / sum : 0.f);
+    const float rs_u = row_scale ? row_scale[u] : 1.f;
+    rs_out[u] = rem == 0 ? rs_u : (sum != 0.f ? 1.f / sum : (kept > 0 ? rs_u : 0.f));   // kept sum 0: s == 0 -> 1
     if (rem) atomicAdd(&blk_rem, rem);
   }
   __syncthreads();

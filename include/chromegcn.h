@@ -582,7 +582,8 @@ size_t cgcn_ablation_workspace_bytes(int n_inst, int S, int d, int layers);
  * Restricted route, one gated layer for the instances (b, k) of row label i, b < n_cols, k < n_pos = |P_i|: row
  * u = pos_list[k] under the mask of column label cols[b].  X [S, n, d] is the unablated input of the layer; X_inst
  * (NULL for layer 1) the instances' ablated input [n_cols][n_pos][S][d], read for the neighbours v in P_i (pos_rank:
- * the [n] ranks of P_i) and for the row itself.  Kept neighbours only are gathered; then U = H W + b, Z = tanh U,
+ * the [n] ranks of P_i) and for the row itself.  Kept neighbours only are gathered and scaled by 1 / kept sum (by the row's
+ * own scale where nothing was removed or that sum is 0; a row that keeps nothing is exactly 0); then U = H W + b, Z = tanh U,
  * g = sigmoid(Z . wg + cg), X_out = (1 - g) X_u + g Z in fp32, [n_cols][n_pos][S][d].  removed (may be NULL):
  * int32 [n_cols][n_pos], the entries each instance's row lost.
  */
@@ -609,7 +610,8 @@ int cgcn_ablation_head(cgcn_stream_t stream, int n, int S, int d, int C, const f
 /*
  * Composed route, the masked graph of pair (label_i, label_j) on the unchanged pattern: val_out[nnz] (val, or 1 when
  * NULL, with the removed entries 0), row_scale_out[n] (row_scale, or 1 when NULL, for untouched rows; 1 / kept sum for
- * touched ones, 0 when nothing is kept) and removed (int32 [1]): the number of removed entries.
+ * touched ones, unchanged where that sum is 0, and 0 when nothing is kept) and removed (int32 [1]): the number of removed
+ * entries.
  */
 int cgcn_ablation_mask(cgcn_stream_t stream, int n, int C, const int32_t *rowptr, const int32_t *col, const float *val,
                        const float *row_scale, const uint32_t *label_bits, int label_i, int label_j, float *val_out,

@@ -9,6 +9,7 @@ import torch
 
 import chromegcn_amd as C
 from chromegcn_amd import _lib, ops, synth
+from ablation_ref import _dense_adj, _dense_forward, reference_matrix  # noqa: F401
 from chromegcn_amd.ablation import RestrictedAblation, label_pair_ablation
 from oracle import chromegcn_oracle as O
 
@@ -32,46 +33,6 @@ def _models(d, c, layers, seed, scale=1.5):
     model = C.ChromeGCN(d, d, c, 0.0, True, layers)
     model.load_state_dict(orc.state_dict())
     return orc.double().eval(), model.to(DEV).eval()
-
-
-def _dense_forward(orc, adj, x):
-    h = x
-    for k in range(1, orc.n_layers + 1):
-        gc, wk = getattr(orc, "GC%d" % k), getattr(orc, "W%d" % k)
-        z = torch.tanh(adj @ (h @ gc.weight) + gc.bias)
-        g = torch.sigmoid(wk(z))
-        h = (1 - g) * h + g * z
-    return orc.out(orc.batch_norm(torch.relu(h)))
-
-
-def reference_matrix(orc, adj, x_f, x_r, targets, rows=None, cols=None):
-    """scripts/visualize.py:79-119 restated in float64 (adj: the dense normalised adjacency)"""
-    c = targets.shape[1]
-    rows = range(c) if rows is None else rows
-    cols = range(c) if cols is None else cols
-    x_f, x_r = x_f.double(), x_r.double()
-    with torch.no_grad():
-        pred = (_dense_forward(orc, adj, x_f) + _dense_forward(orc, adj, x_r)) / 2
-        mat = torch.zeros(c, c, dtype=torch.float64)
-        zero_mat = torch.zeros(adj.shape, dtype=torch.bool)
-        for i in rows:
-            pi = targets[:, i].nonzero().view(-1)
-            base = pred[pi, i].sigmoid().mean()
-            pi_mat = zero_mat.index_fill(0, pi, True)
-            for j in cols:
-                pj = targets[:, j].nonzero().view(-1)
-                if len(pj) > 0 and i != j:
-                    adj2 = adj.masked_fill(pi_mat & zero_mat.index_fill(1, pj, True), 0)
-                    s = adj2.sum(1).view(-1, 1)
-                    s[s == 0] = 1
-                    adj2 = adj2 / s
-                    p = (_dense_forward(orc, adj2, x_f) + _dense_forward(orc, adj2, x_r)) / 2
-                    mat[i, j] = (base - p[pi, i].sigmoid().mean()) / base
-    return mat.numpy()
-
-
-def _dense_adj(adj_type, a, n):
-    return torch.from_numpy(O.normalized_adjacency(adj_type, a, n).toarray()).double()
 
 
 def _case(n, pairs, c, layers, d=128, seed=0, rate=0.2, adj_type="hic", a=None):
