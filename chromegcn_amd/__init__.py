@@ -2,6 +2,8 @@
 
 Public surface mirrors the reference modules it replaces (see layers.py / graph.py / finetune.py)."""
 from .ablation import label_pair_ablation  # noqa: F401
+from .curves import (Curves, optimal_cutoff_host, optimal_cutoffs, pr_curve_host, pr_curves, roc_curve_host,  # noqa: F401
+                     roc_curves)
 from .embed import class_embeddings  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
@@ -16,4 +18,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "build_hic_graph", "build_hic_graph_host", "expand_contacts_host", "contacts_from_text",
            "parse_contacts_text_host", "release_text_staging", "windows_from_bed", "class_embeddings",
            "TsneAffinities", "tsne_embed", "tsne_sweep", "joint_probabilities_host",
-           "kl_gradient_host", "tsne_embed_host"]
+           "kl_gradient_host", "tsne_embed_host", "Curves", "roc_curves", "pr_curves", "optimal_cutoffs",
+           "roc_curve_host", "pr_curve_host", "optimal_cutoff_host"]

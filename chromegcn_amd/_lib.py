@@ -102,6 +102,11 @@ _HEADER = {
     "cgcn_tsne_gradient": (_c_int, "stream n:i ld:i P Y exaggeration:f grad want_kl:i workspace workspace_bytes:z"),
     "cgcn_tsne_update": (_c_int, "stream n:i Y update gains grad momentum:f learning_rate:f have_kl:i record workspace "
                                  "workspace_bytes:z"),
+    "cgcn_curves_workspace_bytes": (_c_sz, "n:ll C:i"),
+    "cgcn_curves_count": (_c_int, "stream n:ll C:i probs targets kind:i drop_intermediate:i offsets bad workspace "
+                                  "workspace_bytes:z"),
+    "cgcn_curves_fill": (_c_int, "stream n:ll C:i offsets capacity:ll tps fps thresholds workspace workspace_bytes:z"),
+    "cgcn_curves_cutoff": (_c_int, "stream C:i offsets tps fps thresholds cutoffs"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))
@@ -113,6 +118,7 @@ _PLANS = {fn: (tuple(p for p, _ in params), tuple(i for i, (_, t) in enumerate(p
           for fn, (_, params) in _ABI.items()}
 ABI_VERSION = 26
 COLSTATS_RECORDS, COLSTATS_ACCUMULATE = 0, 1   # include/chromegcn.h: CGCN_COLSTATS_*
+CURVE_ROC, CURVE_PR = 0, 1   # include/chromegcn.h: CGCN_CURVE_*
 COLSTATS_ROWS_ACCUMULATE, COLSTATS_ROWS_ZERO_ONLY, COLSTATS_ROWS_ACCUMULATE_ZEROED = -1, -2, -3   # CGCN_COLSTATS_ROWS_*
 _lib = None
 

@@ -621,6 +621,33 @@ static size_t sort_temp_bytes(long long n, int C) {
 }
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// pack + segmented sort of the non-negative-score path (n > 0): label c's sorted 32-bit keys end up in k_a[c n, (c + 1) n)
+static void nonneg_pack_sort(hipStream_t st, long long n, int C, const float* probs, const float* targets, unsigned* k_a,
+                             unsigned* k_b, unsigned* hist, unsigned* base, int* bad) {
+  const int T = rs_tiles(n);
+  dim3 grid((unsigned)((n + 31) / 32), (unsigned)((C + 31) / 32));
+  // rows per block of the flat pack: a power of two, [C][R + 1] keys within 48 KB of LDS
+  int R = 128, rshift = 7;
+  while (R > 4 && (size_t)C * (R + 1) * 4 > 48 * 1024) { R >>= 1; --rshift; }
+  if ((size_t)C * (R + 1) * 4 <= 48 * 1024) {
+    const unsigned blocks = (unsigned)((n + R - 1) / R);
+    const size_t lds = (size_t)C * (R + 1) * 4;
+    if ((((uintptr_t)probs | (uintptr_t)targets) & 15) == 0)
+      hipLaunchKernelGGL(k_metrics_pack32_flat<4>, dim3(blocks), dim3(256), lds, st, n, C, R, rshift, probs, targets, k_a, bad);
+    else
+      hipLaunchKernelGGL(k_metrics_pack32_flat<1>, dim3(blocks), dim3(256), lds, st, n, C, R, rshift, probs, targets, k_a, bad);
+  } else   // thousands of labels: the tile transposition
+    hipLaunchKernelGGL(k_metrics_pack32, grid, dim3(256), 0, st, n, C, probs, targets, k_a, bad);
+  unsigned* a = k_a;
+  unsigned* b = k_b;
+  for (int shift = 1; shift < 32; shift += 8) {   // key bits 1 .. 31: four passes, the sorted keys end up in k_a again
+    hipLaunchKernelGGL(k_rs_pass<false>, dim3(T, C), dim3(RS_THREADS), 0, st, n, T, shift, (const unsigned*)a, b, hist, (const unsigned*)base);
+    hipLaunchKernelGGL(k_rs_scan, dim3(C), dim3(256), 0, st, T, hist, base);
+    hipLaunchKernelGGL(k_rs_pass<true>, dim3(T, C), dim3(RS_THREADS), 0, st, n, T, shift, (const unsigned*)a, b, hist, (const unsigned*)base);
+    unsigned* tsw = a; a = b; b = tsw;
+  }
+}
+
 extern "C" {
 
 size_t cgcn_metrics_workspace_bytes(long long n, int C) {
@@ -656,29 +683,7 @@ int cgcn_multilabel_metrics_nonneg(cgcn_stream_t stream, long long n, int C, con
   double* Ptot = (double*)w; w += al((size_t)C * 8);
   if ((size_t)(w - (char*)workspace) > workspace_bytes) return CGCN_ERR_WORKSPACE;   // (cannot happen: the size above covers this layout)
   if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) return CGCN_ERR_LAUNCH;
-  if (n > 0) {
-    dim3 grid((unsigned)((n + 31) / 32), (unsigned)((C + 31) / 32));
-    // rows per block of the flat pack: a power of two, [C][R + 1] keys within 48 KB of LDS
-    int R = 128, rshift = 7;
-    while (R > 4 && (size_t)C * (R + 1) * 4 > 48 * 1024) { R >>= 1; --rshift; }
-    if ((size_t)C * (R + 1) * 4 <= 48 * 1024) {
-      const unsigned blocks = (unsigned)((n + R - 1) / R);
-      const size_t lds = (size_t)C * (R + 1) * 4;
-      if ((((uintptr_t)probs | (uintptr_t)targets) & 15) == 0)
-        hipLaunchKernelGGL(k_metrics_pack32_flat<4>, dim3(blocks), dim3(256), lds, st, n, C, R, rshift, probs, targets, k_a, bad);
-      else
-        hipLaunchKernelGGL(k_metrics_pack32_flat<1>, dim3(blocks), dim3(256), lds, st, n, C, R, rshift, probs, targets, k_a, bad);
-    } else   // thousands of labels: the tile transposition
-      hipLaunchKernelGGL(k_metrics_pack32, grid, dim3(256), 0, st, n, C, probs, targets, k_a, bad);
-    unsigned* a = k_a;
-    unsigned* b = k_b;
-    for (int shift = 1; shift < 32; shift += 8) {   // key bits 1 .. 31: four passes, the sorted keys end up in k_a again
-      hipLaunchKernelGGL(k_rs_pass<false>, dim3(T, C), dim3(RS_THREADS), 0, st, n, T, shift, (const unsigned*)a, b, hist, (const unsigned*)base);
-      hipLaunchKernelGGL(k_rs_scan, dim3(C), dim3(256), 0, st, T, hist, base);
-      hipLaunchKernelGGL(k_rs_pass<true>, dim3(T, C), dim3(RS_THREADS), 0, st, n, T, shift, (const unsigned*)a, b, hist, (const unsigned*)base);
-      unsigned* tsw = a; a = b; b = tsw;
-    }
-  }
+  if (n > 0) nonneg_pack_sort(st, n, C, probs, targets, k_a, k_b, hist, base, bad);
   hipLaunchKernelGGL(k_metrics_summary<true>, dim3(nch, C), dim3(64), 0, st, n, nch, (const void*)k_a, (const unsigned char*)nullptr, rec);
   hipLaunchKernelGGL(k_metrics_prefix, dim3(C), dim3(64), 0, st, nch, rec, Ptot);
   hipLaunchKernelGGL(k_metrics_chunks<true>, dim3(nch, C), dim3(64), 0, st, n, nch, (const void*)k_a, (const unsigned char*)nullptr, rec, Ptot, (double)fdr_cutoff, outp);
@@ -716,6 +721,312 @@ int cgcn_multilabel_metrics(cgcn_stream_t stream, long long n, int C, const floa
   hipLaunchKernelGGL(k_metrics_prefix, dim3(C), dim3(64), 0, st, nch, rec, Ptot);
   hipLaunchKernelGGL(k_metrics_chunks<false>, dim3(nch, C), dim3(64), 0, st, n, nch, (const void*)keys_out, (const unsigned char*)vals_out, rec, Ptot, (double)fdr_cutoff, outp);
   hipLaunchKernelGGL(k_metrics_final, dim3(C), dim3(64), 0, st, n, C, nch, outp, Ptot, out);
+  return launch_status();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// ROC and precision-recall curves of every label: the points the
+// scan above walks over, written out.  utils/evals.py:28-84 draws them with one roc_curve / precision_recall_curve
+// call per label (utils/metrics.py:255-303).  The lists are packed and sorted by the non-negative-score path above;
+// what is new is ordered stream compaction, twice, each time as count per 4096-slot chunk (one wave) -> prefix per
+// label (one wave) -> write:
+//   level 1  elements -> curve points.  A point is the last element of a run of equal scores (sklearn's
+//            _binary_clf_curve); point k of label c is kept as (its sorted position, positives up to it) in
+//            pidx / ptp[c n + k] -- K_c <= n, so every label's points fit its own segment and no prefix over labels
+//            is needed.  fps = position + 1 - tps; the threshold is read back from the key at that position.
+//   level 2  points -> output.  roc_curve(drop_intermediate=True) keeps point k iff it is the first, the last, or the
+//            second difference of fps or of tps at k is not zero, and only when K_c > 2; the neighbours k - 1 and
+//            k + 1 are array neighbours here, whichever element chunks they came from.  Every other kind keeps every point.
+// Counts are ballots and popcounts of integers: no floating-point sum, the same bits on every run.
+// ------------------------------------------------------------------------------------------
+struct CurveRec { int pos, ends; };   // k_curves_runs: positives / run ends IN a chunk; after k_curves_prefix: BEFORE it
+
+struct CurveWs {
+  unsigned *k_a, *k_b, *hist, *base;
+  int *pidx, *ptp;      // pidx shares k_b: the sort's second buffer is dead once the keys are back in k_a
+  CurveRec* rec;        // [C][nch]
+  int* kept;            // [C][nch] kept points in a chunk of points, then those before it
+  int* tot;             // [3][C]: K_c (points), P_c (positives), output length of label c
+  int* mode;            // bit 0: the origin point leads every label (ROC), bit 1: corner rule
+};
+static size_t curve_ws_layout(void* workspace, long long n, int C, CurveWs& L) {
+  const size_t items = (size_t)n * C, nrec = (size_t)C * metric_chunks(n);
+  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w0 = w;
+  L.k_a = (unsigned*)w; w += al(items * 4);
+  L.k_b = (unsigned*)w; L.pidx = (int*)w; w += al(items * 4);
+  L.ptp = (int*)w; w += al(items * 4);
+  L.hist = (unsigned*)w; w += al((size_t)C * rs_tiles(n) * 256 * 4);
+  L.base = (unsigned*)w; w += al((size_t)C * 256 * 4);
+  L.rec = (CurveRec*)w; w += al(nrec * sizeof(CurveRec));
+  L.kept = (int*)w; w += al(nrec * 4);
+  L.tot = (int*)w; w += al((size_t)C * 12);
+  L.mode = (int*)w; w += 256;
+  return (size_t)(w - w0) + 256;   // + what aligning the caller's pointer may take
+}
+
+// exclusive prefix of one int per lane; `total` is the wave's sum
+__device__ __forceinline__ int wave_excl_scan_i(int v, int lane, int& total) {
+  int incl = v;
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    const int o = __shfl_up(incl, off, WAVE);
+    if (lane >= off) incl += o;
+  }
+  total = __shfl(incl, WAVE - 1, WAVE);
+  return incl - v;
+}
+
+// element i of a label's sorted list: is it a positive, does a run of equal scores end at it
+__device__ __forceinline__ void curve_element(const unsigned* __restrict__ q, long long i, long long i1, long long n, bool& pos,
+                                              bool& end) {
+  const bool ok = i < i1;
+  const unsigned k = ok ? q[i] : 0u;
+  const unsigned nb = (ok && i + 1 < n) ? q[i + 1] : 0u;
+  pos = ok && (k & 1u);
+  end = ok && (i + 1 == n || (k >> 1) != (nb >> 1));
+}
+
+__global__ __launch_bounds__(64) void k_curves_runs(long long n, int nch, const unsigned* __restrict__ keys,
+                                                    CurveRec* __restrict__ rec) {
+  const int c = blockIdx.y, ch = blockIdx.x, lane = threadIdx.x;
+  const unsigned* q = keys + (long long)c * n;
+  const long long i0 = (long long)ch * METRIC_CHUNK, i1 = min(n, i0 + METRIC_CHUNK);
+  int pos = 0, ends = 0;
+#pragma unroll 4
+  for (long long b = i0; b < i1; b += WAVE) {
+    bool p, e;
+    curve_element(q, b + lane, i1, n, p, e);
+    pos += __builtin_popcountll(__ballot(p));
+    ends += __builtin_popcountll(__ballot(e));
+  }
+  if (lane == 0) rec[(size_t)c * nch + ch] = CurveRec{pos, ends};
+}
+
+// one wave per label: the chunk records become exclusive prefixes; tot[c] = K_c, tot[C + c] = P_c
+__global__ __launch_bounds__(64) void k_curves_prefix(int C, int nch, CurveRec* __restrict__ rec, int* __restrict__ tot) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  CurveRec* r = rec + (size_t)c * nch;
+  int cpos = 0, cends = 0;
+  for (int k0 = 0; k0 < nch; k0 += WAVE) {
+    const int k = k0 + lane;
+    const CurveRec v = k < nch ? r[k] : CurveRec{0, 0};
+    int tp, te;
+    const int ep = wave_excl_scan_i(v.pos, lane, tp), ee = wave_excl_scan_i(v.ends, lane, te);
+    if (k < nch) r[k] = CurveRec{cpos + ep, cends + ee};
+    cpos += tp;
+    cends += te;
+  }
+  if (lane == 0) {
+    tot[c] = cends;
+    tot[C + c] = cpos;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_curves_points(long long n, int nch, const unsigned* __restrict__ keys,
+                                                      const CurveRec* __restrict__ rec, int* __restrict__ pidx,
+                                                      int* __restrict__ ptp) {
+  const int c = blockIdx.y, ch = blockIdx.x, lane = threadIdx.x;
+  const unsigned* q = keys + (long long)c * n;
+  const long long i0 = (long long)ch * METRIC_CHUNK, i1 = min(n, i0 + METRIC_CHUNK);
+  const CurveRec r = rec[(size_t)c * nch + ch];
+  int cpos = r.pos;
+  long long k0 = (long long)c * n + r.ends;   // slot of the chunk's first point: r.ends + (ends in the chunk) <= K_c <= n
+#pragma unroll 4
+  for (long long b = i0; b < i1; b += WAVE) {
+    bool p, e;
+    curve_element(q, b + lane, i1, n, p, e);
+    const unsigned long long pb = __ballot(p), eb = __ballot(e);
+    if (e) {
+      const long long k = k0 + __builtin_popcountll(eb & lanes_lt(lane));
+      pidx[k] = (int)(b + lane);
+      ptp[k] = cpos + (int)__builtin_popcountll(pb & lanes_le(lane));
+    }
+    cpos += (int)__builtin_popcountll(pb);
+    k0 += __builtin_popcountll(eb);
+  }
+}
+
+// is point k of a label with K points part of the output (pi / pt: the label's own segment)
+__device__ __forceinline__ bool curve_keep(const int* __restrict__ pi, const int* __restrict__ pt, int k, int K, bool drop) {
+  if (k >= K) return false;
+  if (!drop || K <= 2 || k == 0 || k == K - 1) return true;
+  const long long t0 = pt[k - 1], t1 = pt[k], t2 = pt[k + 1];
+  const long long f0 = (long long)pi[k - 1] + 1 - t0, f1 = (long long)pi[k] + 1 - t1, f2 = (long long)pi[k + 1] + 1 - t2;
+  return (f2 - 2 * f1 + f0) != 0 || (t2 - 2 * t1 + t0) != 0;
+}
+
+__global__ __launch_bounds__(64) void k_curves_keep_count(long long n, int nch, const int* __restrict__ pidx,
+                                                          const int* __restrict__ ptp, const int* __restrict__ tot, int drop,
+                                                          int* __restrict__ kept) {
+  const int c = blockIdx.y, ch = blockIdx.x, lane = threadIdx.x;
+  const int K = tot[c];
+  const int* pi = pidx + (long long)c * n;
+  const int* pt = ptp + (long long)c * n;
+  const long long p0 = (long long)ch * METRIC_CHUNK, p1 = min((long long)K, p0 + METRIC_CHUNK);
+  int count = 0;
+#pragma unroll 4
+  for (long long b = p0; b < p1; b += WAVE)
+    count += __builtin_popcountll(__ballot(curve_keep(pi, pt, (int)min(b + lane, (long long)K), K, drop != 0)));
+  if (lane == 0) kept[(size_t)c * nch + ch] = count;
+}
+
+// one wave per label: kept[] becomes an exclusive prefix; tot[2 C + c] = the label's output length
+__global__ __launch_bounds__(64) void k_curves_keep_prefix(int C, int nch, int origin, int* __restrict__ kept, int* __restrict__ tot) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  int* r = kept + (size_t)c * nch;
+  int carry = 0;
+  for (int k0 = 0; k0 < nch; k0 += WAVE) {
+    const int k = k0 + lane;
+    const int v = k < nch ? r[k] : 0;
+    int t;
+    const int e = wave_excl_scan_i(v, lane, t);
+    if (k < nch) r[k] = carry + e;
+    carry += t;
+  }
+  if (lane == 0) tot[2 * C + c] = carry + origin;
+}
+
+// one wave: offsets[c] = exclusive prefix over the labels of their output lengths, offsets[C] the total; and the mode word
+__global__ __launch_bounds__(64) void k_curves_offsets(int C, const int* __restrict__ tot, int mode, long long* __restrict__ offsets,
+                                                       int* __restrict__ mode_out) {
+  const int lane = threadIdx.x;
+  long long carry = 0;
+  for (int c0 = 0; c0 < C; c0 += WAVE) {
+    const int c = c0 + lane;
+    const long long v = c < C ? tot[2 * C + c] : 0;
+    long long incl = v;   // (64 bits: n C + C may pass 2^31)
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      const long long o = __shfl_up(incl, off, WAVE);
+      if (lane >= off) incl += o;
+    }
+    if (c < C) offsets[c] = carry + incl - v;
+    carry += __shfl(incl, WAVE - 1, WAVE);
+  }
+  if (lane == 0) {
+    offsets[C] = carry;
+    *mode_out = mode;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_curves_fill(long long n, int nch, const unsigned* __restrict__ keys,
+                                                    const int* __restrict__ pidx, const int* __restrict__ ptp,
+                                                    const int* __restrict__ tot, const int* __restrict__ kept,
+                                                    const int* __restrict__ mode, const long long* __restrict__ offsets,
+                                                    long long capacity, int* __restrict__ tps, int* __restrict__ fps,
+                                                    float* __restrict__ thr) {
+  const int c = blockIdx.y, ch = blockIdx.x, lane = threadIdx.x;
+  const int K = tot[c], m = *mode;
+  const bool origin = m & 1, drop = m & 2;
+  const unsigned* q = keys + (long long)c * n;
+  const int* pi = pidx + (long long)c * n;
+  const int* pt = ptp + (long long)c * n;
+  const long long first = offsets[c];
+  if (ch == 0 && lane == 0 && origin && first >= 0 && first < capacity) {   // (0, 0, +inf), as roc_curve prepends it
+    tps[first] = 0;
+    fps[first] = 0;
+    thr[first] = __uint_as_float(0x7F800000u);
+  }
+  long long o0 = first + (origin ? 1 : 0) + kept[(size_t)c * nch + ch];
+  const long long p0 = (long long)ch * METRIC_CHUNK, p1 = min((long long)K, p0 + METRIC_CHUNK);
+#pragma unroll 2
+  for (long long b = p0; b < p1; b += WAVE) {
+    const int k = (int)min(b + lane, (long long)K);
+    const bool keep = curve_keep(pi, pt, k, K, drop);
+    const unsigned long long kb = __ballot(keep);
+    const long long o = o0 + __builtin_popcountll(kb & lanes_lt(lane));
+    if (keep && o >= 0 && o < capacity) {
+      const int idx = pi[k], t = pt[k];
+      tps[o] = t;
+      fps[o] = idx + 1 - t;
+      thr[o] = __uint_as_float(0x7FFFFFFFu - (q[idx] >> 1));   // the score's own bits (-0 was folded onto +0)
+    }
+    o0 += __builtin_popcountll(kb);
+  }
+}
+
+// one wave per label of a filled ROC curve: threshold of the FIRST point that minimises |tps / P - (1 - fps / N)|
+// (float64, IEEE quotients, that operation order); NaN without a positive or without a negative
+__global__ __launch_bounds__(64) void k_curves_cutoff(const long long* __restrict__ offsets, const int* __restrict__ tps,
+                                                      const int* __restrict__ fps, const float* __restrict__ thr,
+                                                      float* __restrict__ cutoffs) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  const long long o0 = offsets[c], len = offsets[c + 1] - o0;
+  const int Pn = len > 0 ? tps[o0 + len - 1] : 0, Nn = len > 0 ? fps[o0 + len - 1] : 0;
+  if (Pn <= 0 || Nn <= 0) {
+    if (lane == 0) cutoffs[c] = __int_as_float(0x7fc00000);
+    return;
+  }
+  const double P = (double)Pn, N = (double)Nn;
+  double best = __longlong_as_double(0x7FF0000000000000ll);
+  long long at = len;
+  for (long long j = lane; j < len; j += WAVE) {
+    const double tpr = (double)tps[o0 + j] / P, fpr = (double)fps[o0 + j] / N;
+    const double v = __builtin_fabs(tpr - (1.0 - fpr));
+    if (v < best) { best = v; at = j; }   // ascending j: a lane keeps its earliest minimum
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ob = __shfl_xor(best, off, WAVE);
+    const long long oa = __shfl_xor(at, off, WAVE);
+    if (ob < best || (ob == best && oa < at)) { best = ob; at = oa; }
+  }
+  if (lane == 0) cutoffs[c] = thr[o0 + at];
+}
+
+extern "C" {
+
+size_t cgcn_curves_workspace_bytes(long long n, int C) {
+  if (n < 1 || C < 1 || (double)n * C >= 2147483647.0) return 0;
+  CurveWs L;
+  return curve_ws_layout(nullptr, n, C, L);
+}
+
+int cgcn_curves_count(cgcn_stream_t stream, long long n, int C, const float* probs, const float* targets, int kind,
+                      int drop_intermediate, long long* offsets, int32_t* bad, void* workspace, size_t workspace_bytes) {
+  if (n < 0 || C < 1 || !offsets || !bad || !probs || !targets || !workspace) return CGCN_ERR_BAD_ARG;
+  if (kind != CGCN_CURVE_ROC && kind != CGCN_CURVE_PR) return CGCN_ERR_BAD_ARG;
+  if (n < 1 || (double)n * C >= 2147483647.0) return CGCN_ERR_UNSUPPORTED;
+  if (kind == CGCN_CURVE_PR && drop_intermediate) return CGCN_ERR_UNSUPPORTED;
+  if (workspace_bytes < cgcn_curves_workspace_bytes(n, C)) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  CurveWs L;
+  curve_ws_layout(workspace, n, C, L);
+  const int nch = metric_chunks(n);
+  const int origin = kind == CGCN_CURVE_ROC ? 1 : 0, drop = (origin && drop_intermediate) ? 1 : 0;
+  if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) return CGCN_ERR_LAUNCH;
+  nonneg_pack_sort(st, n, C, probs, targets, L.k_a, L.k_b, L.hist, L.base, bad);
+  hipLaunchKernelGGL(k_curves_runs, dim3(nch, C), dim3(64), 0, st, n, nch, (const unsigned*)L.k_a, L.rec);
+  hipLaunchKernelGGL(k_curves_prefix, dim3(C), dim3(64), 0, st, C, nch, L.rec, L.tot);
+  hipLaunchKernelGGL(k_curves_points, dim3(nch, C), dim3(64), 0, st, n, nch, (const unsigned*)L.k_a, (const CurveRec*)L.rec, L.pidx, L.ptp);
+  hipLaunchKernelGGL(k_curves_keep_count, dim3(nch, C), dim3(64), 0, st, n, nch, (const int*)L.pidx, (const int*)L.ptp, (const int*)L.tot, drop, L.kept);
+  hipLaunchKernelGGL(k_curves_keep_prefix, dim3(C), dim3(64), 0, st, C, nch, origin, L.kept, L.tot);
+  hipLaunchKernelGGL(k_curves_offsets, dim3(1), dim3(64), 0, st, C, (const int*)L.tot, origin | (drop << 1), offsets, L.mode);
+  return launch_status();
+}
+
+int cgcn_curves_fill(cgcn_stream_t stream, long long n, int C, const long long* offsets, long long capacity, int32_t* tps,
+                     int32_t* fps, float* thresholds, void* workspace, size_t workspace_bytes) {
+  if (n < 0 || C < 1 || capacity < 0 || !offsets || !workspace) return CGCN_ERR_BAD_ARG;
+  if (capacity > 0 && (!tps || !fps || !thresholds)) return CGCN_ERR_BAD_ARG;
+  if (n < 1 || (double)n * C >= 2147483647.0) return CGCN_ERR_UNSUPPORTED;
+  if (workspace_bytes < cgcn_curves_workspace_bytes(n, C)) return CGCN_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  CurveWs L;
+  curve_ws_layout(workspace, n, C, L);
+  const int nch = metric_chunks(n);
+  hipLaunchKernelGGL(k_curves_fill, dim3(nch, C), dim3(64), 0, st, n, nch, (const unsigned*)L.k_a, (const int*)L.pidx, (const int*)L.ptp,
+                     (const int*)L.tot, (const int*)L.kept, (const int*)L.mode, offsets, capacity, tps, fps, thresholds);
+  return launch_status();
+}
+
+int cgcn_curves_cutoff(cgcn_stream_t stream, int C, const long long* offsets, const int32_t* tps, const int32_t* fps,
+                       const float* thresholds, float* cutoffs) {
+  if (C < 1 || !offsets || !tps || !fps || !thresholds || !cutoffs) return CGCN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_curves_cutoff, dim3(C), dim3(64), 0, (hipStream_t)stream, offsets, tps, fps, thresholds, cutoffs);
   return launch_status();
 }
 

@@ -56,12 +56,29 @@ def multilabel_metrics(probs: torch.Tensor, targets: torch.Tensor, fdr_cutoff: f
     return _split(flat, C)
 
 
+def group_means(per_label: Dict[str, np.ndarray], label_groups) -> Dict[str, float]:
+    """{<group>_meanAUC, <group>_meanAUPR, <group>_meanFDR} for every group of `label_groups` (a mapping group name -> list
+    of label indices, e.g. {"tfbs": [...], "hm": [...], "dnase": [...]}: utils/evals.py:38-71 averages over these three):
+    means of per_label["auroc" / "aupr" / "recall_at_fdr"] ([C] arrays, NaN where undefined) over the group's labels with
+    a defined value, NaN when it has none.  Pure host arithmetic."""
+    out = {}
+    for group, idx in label_groups.items():
+        idx = np.asarray(list(idx), dtype=np.int64)
+        for key, name in (("auroc", "meanAUC"), ("aupr", "meanAUPR"), ("recall_at_fdr", "meanFDR")):
+            v = np.asarray(per_label[key], dtype=np.float64)[idx]
+            v = v[~np.isnan(v)]
+            out["%s_%s" % (group, name)] = float(np.mean(v)) if v.size else float("nan")
+    return out
+
+
 def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, data_dict=None, cell_type=None,
-                    device="cuda", verbose=False):
-    """Same positional arguments and result keys as the reference's compute_metrics (utils/evals.py:26,107-120;
-    the per_label_type / plot branches are analysis-only and not reproduced).  Labels whose metric is undefined
-    (a single class present) are skipped in the means, as the reference's try/except does.  Unlike the reference
-    this does NOT threshold all_predictions in place (utils/evals.py:99-100)."""
+                    device="cuda", verbose=False, label_groups=None):
+    """Same positional arguments and result keys as the reference's compute_metrics (utils/evals.py:26,107-120).
+    Labels whose metric is undefined (a single class present) are skipped in the means, as the reference's try/except
+    does.  Unlike the reference this does NOT threshold all_predictions in place (utils/evals.py:99-100).
+    Of the per_label_type branch (utils/evals.py:28-84) the group means are here: with `label_groups` (see group_means;
+    the caller supplies the index lists) the result also holds <group>_meanAUC / _meanAUPR / _meanFDR, from the per-label
+    results of the same single metrics call.  The curves its plot branch draws are chromegcn_amd.curves."""
     p = torch.as_tensor(all_predictions).to(device=device, dtype=torch.float32)
     t = torch.as_tensor(all_targets).to(device=device, dtype=torch.float32)
     C = p.shape[1]
@@ -84,6 +101,8 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
         "medianFDR": float(np.median(fdr)) if fdr.size else float("nan"),
         "loss": loss, "time": elapsed,
     }
+    if label_groups is not None:
+        out.update(group_means(m, label_groups))
     if verbose:  # utils/evals.py:102-105
         print("mAP:      " + str(round(out["mAP"], 3)))
         print("meanAUC:  " + str(round(out["meanAUC"], 3)))

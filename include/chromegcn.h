@@ -791,6 +791,45 @@ int cgcn_tsne_gradient(cgcn_stream_t stream, int n, int ld, const float *P, cons
 int cgcn_tsne_update(cgcn_stream_t stream, int n, float *Y, float *update, float *gains, const float *grad, float momentum,
                      float learning_rate, int have_kl, double *record, void *workspace, size_t workspace_bytes);
 
+/*
+ * ROC and precision-recall curves of every label (utils/evals.py:28-84 -> utils/metrics.py:255-303: one scikit-learn
+ * roc_curve / precision_recall_curve call per label; chromegcn_amd/curves.py).  These four functions
+ * are additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing above changes.
+ * Scores are probabilities (non-negative, as for cgcn_multilabel_metrics_nonneg, whose pack and segmented sort run
+ * here): a negative score or a NaN sets bad[0] and leaves every output unspecified.  1 <= n, n * C < 2^31, else
+ * CGCN_ERR_UNSUPPORTED.  A curve point is the last element of each run of equal scores in a label's descending list
+ * (sklearn's _binary_clf_curve): tps = positives down to it, fps = negatives down to it, threshold = that score.
+ *
+ * Two calls, because only the device knows how many points there are (as cgcn_graph_count / cgcn_graph_fill):
+ * cgcn_curves_count    sorts, marks the points and writes offsets (int64 [C + 1], device): label c's points are
+ *                      [offsets[c], offsets[c + 1]) of the flat outputs, offsets[C] is their length.
+ *                      kind CGCN_CURVE_ROC: every label starts with the origin (0, 0, +inf), as roc_curve prepends it; with
+ *                      drop_intermediate != 0 and more than two points, point k stays iff it is the first, the last, or the
+ *                      second difference of fps or of tps at k is non-zero (roc_curve's rule, applied before the origin
+ *                      is prepended).  kind CGCN_CURVE_PR: the points only; drop_intermediate must be 0.
+ * cgcn_curves_fill     writes tps, fps (int32) and thresholds (fp32: the score's own bits, -0 as +0) in descending-score
+ *                      order per label, from the workspace the count call left (same n, C, workspace, nothing else run on
+ *                      it in between).  capacity: elements each output holds; nothing is written at or past it.
+ * cgcn_curves_cutoff   from a filled ROC curve: cutoffs[c] (fp32 [C]) = threshold of the first point that minimises
+ *                      |tps / P - (1 - fps / N)| in float64, P / N the label's positives / negatives (Find_Optimal_Cutoff,
+ *                      utils/metrics.py:224-235); NaN without a positive or without a negative.  No workspace.
+ * Enqueue only: no allocation, no sync, nothing kept between calls but the workspace contents; integer counts throughout,
+ * so the same inputs give the same bits.  cgcn_curves_workspace_bytes is 0 for an unsupported size.
+ */
+#define CGCN_CURVE_ROC 0
+#define CGCN_CURVE_PR 1
+
+size_t cgcn_curves_workspace_bytes(long long n, int C);
+
+int cgcn_curves_count(cgcn_stream_t stream, long long n, int C, const float *probs, const float *targets, int kind,
+                      int drop_intermediate, long long *offsets, int32_t *bad, void *workspace, size_t workspace_bytes);
+
+int cgcn_curves_fill(cgcn_stream_t stream, long long n, int C, const long long *offsets, long long capacity, int32_t *tps,
+                     int32_t *fps, float *thresholds, void *workspace, size_t workspace_bytes);
+
+int cgcn_curves_cutoff(cgcn_stream_t stream, int C, const long long *offsets, const int32_t *tps, const int32_t *fps,
+                       const float *thresholds, float *cutoffs);
+
 #ifdef __cplusplus
 }
 #endif
