@@ -10,6 +10,8 @@ from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
+from .thresholds import (ThresholdCounts, best_thresholds, metrics_from_counts, threshold_counts,  # noqa: F401
+                         threshold_counts_host, threshold_metrics, threshold_metrics_host)
 from .tsne import (TsneAffinities, joint_probabilities_host, kl_gradient_host, tsne_embed, tsne_embed_host,  # noqa: F401
                    tsne_sweep)
 
@@ -19,4 +21,6 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "parse_contacts_text_host", "release_text_staging", "windows_from_bed", "class_embeddings",
            "TsneAffinities", "tsne_embed", "tsne_sweep", "joint_probabilities_host",
            "kl_gradient_host", "tsne_embed_host", "Curves", "roc_curves", "pr_curves", "optimal_cutoffs",
-           "roc_curve_host", "pr_curve_host", "optimal_cutoff_host"]
+           "roc_curve_host", "pr_curve_host", "optimal_cutoff_host", "ThresholdCounts", "threshold_counts",
+           "threshold_metrics", "metrics_from_counts", "best_thresholds", "threshold_counts_host",
+           "threshold_metrics_host"]

@@ -107,6 +107,10 @@ _HEADER = {
                                   "workspace_bytes:z"),
     "cgcn_curves_fill": (_c_int, "stream n:ll C:i offsets capacity:ll tps fps thresholds workspace workspace_bytes:z"),
     "cgcn_curves_cutoff": (_c_int, "stream C:i offsets tps fps thresholds cutoffs"),
+    "cgcn_threshold_workspace_bytes": (_c_sz, "n:ll C:i T:i"),
+    "cgcn_debug_threshold_route": (_c_int, "n:ll C:i T:i"),
+    "cgcn_threshold_counts": (_c_int, "stream n:ll C:i T:i probs targets thresholds pos tp pp exact rows tpsum workspace "
+                                      "workspace_bytes:z"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -72,13 +72,16 @@ def group_means(per_label: Dict[str, np.ndarray], label_groups) -> Dict[str, flo
 
 
 def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, data_dict=None, cell_type=None,
-                    device="cuda", verbose=False, label_groups=None):
+                    device="cuda", verbose=False, label_groups=None, br_threshold=None):
     """Same positional arguments and result keys as the reference's compute_metrics (utils/evals.py:26,107-120).
     Labels whose metric is undefined (a single class present) are skipped in the means, as the reference's try/except
     does.  Unlike the reference this does NOT threshold all_predictions in place (utils/evals.py:99-100).
     Of the per_label_type branch (utils/evals.py:28-84) the group means are here: with `label_groups` (see group_means;
     the caller supplies the index lists) the result also holds <group>_meanAUC / _meanAUPR / _meanFDR, from the per-label
-    results of the same single metrics call.  The curves its plot branch draws are chromegcn_amd.curves."""
+    results of the same single metrics call.  The curves its plot branch draws are chromegcn_amd.curves.
+    `br_threshold` (default: `args.br_threshold` where `args` has one, else off; config_args.py:28): with a value the result
+    also holds the scalars ACC, HA, ebF1, miF1, maF1 of the decisions p >= br_threshold (chromegcn_amd.thresholds, one more
+    stream over the device tensors); all_predictions is still not modified."""
     p = torch.as_tensor(all_predictions).to(device=device, dtype=torch.float32)
     t = torch.as_tensor(all_targets).to(device=device, dtype=torch.float32)
     C = p.shape[1]
@@ -103,6 +106,12 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
     }
     if label_groups is not None:
         out.update(group_means(m, label_groups))
+    if br_threshold is None:
+        br_threshold = getattr(args, "br_threshold", None)
+    if br_threshold is not None:
+        from . import thresholds
+        tm = thresholds.threshold_metrics(p, t, float(br_threshold))
+        out.update({k: float(tm[k][0]) for k in thresholds.METRIC_KEYS})
     if verbose:  # utils/evals.py:102-105
         print("mAP:      " + str(round(out["mAP"], 3)))
         print("meanAUC:  " + str(round(out["meanAUC"], 3)))

@@ -53,6 +53,8 @@ def parse(argv=None):
     ap.add_argument("-synthetic", action="store_true")
     ap.add_argument("-synthetic_chroms", type=str, default=",".join(synth.HG19_LEN))
     ap.add_argument("-gpu_id", type=int, default=0)
+    ap.add_argument("-br_threshold", type=float, default=None,       # config_args.py:28 (there 0.5; here off unless given)
+                    help="also report ACC, HA, ebF1, miF1, maF1 of the decisions p >= this (chromegcn_amd.thresholds)")
     return ap.parse_args(argv)
 
 

@@ -830,6 +830,33 @@ int cgcn_curves_fill(cgcn_stream_t stream, long long n, int C, const long long *
 int cgcn_curves_cutoff(cgcn_stream_t stream, int C, const long long *offsets, const int32_t *tps, const int32_t *fps,
                        const float *thresholds, float *cutoffs);
 
+/*
+ * Thresholded multi-label counts (utils/metrics.py:29-109 behind utils/evals.py:94-100's -br_threshold: subset accuracy,
+ * Hamming loss, example-based / micro / macro F1; chromegcn_amd/thresholds.py).  These three
+ * functions are additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing above changes.
+ * With Y[i][c] = targets[i][c] > 0.5f and P[t][i][c] = probs[i][c] >= thresholds[t][c] in float32 (a NaN probability is
+ * never predicted; thresholds [T][C] may be +-inf), one stream over probs and targets ([n][C] row-major) writes, as int64:
+ *   pos[c]        rows with Y                                  [C]
+ *   tp[t][c]      rows with P and Y                            [T][C]
+ *   pp[t][c]      rows with P (fp = pp - tp, fn = pos - tp)    [T][C]
+ *   exact[t]      rows whose C decisions equal their C targets [T]
+ *   rows[t][k]    rows with |P_i| + |Y_i| = k, k = 0 .. 2C     [T][2C + 1]
+ *   tpsum[t][k]   sum of |P_i and Y_i| over those rows         [T][2C + 1]
+ * (sum_i 2 tp_i / (|P_i| + |Y_i|) = sum_k (2 / k) tpsum[k]: the example-based F1 without a floating-point sum over rows.)
+ * Every element of every output is written; callers do not clear them.  1 <= n < 2^47, 1 <= C <= 1024, 1 <= T <= 64,
+ * else CGCN_ERR_UNSUPPORTED and cgcn_threshold_workspace_bytes is 0.  Enqueue only: no allocation, no sync; integer sums, so
+ * the same inputs give the same bits.  The workspace is reserved: it must be given at the queried size and is not written.
+ * cgcn_debug_threshold_route: the number of passes over the rows the call makes (thresholds are taken in groups whose row
+ * histograms fit the LDS: 1 = one pass; more = the slow route of large C * T), or CGCN_ERR_UNSUPPORTED.  Host logic only.
+ */
+size_t cgcn_threshold_workspace_bytes(long long n, int C, int T);
+
+int cgcn_debug_threshold_route(long long n, int C, int T);
+
+int cgcn_threshold_counts(cgcn_stream_t stream, long long n, int C, int T, const float *probs, const float *targets,
+                          const float *thresholds, long long *pos, long long *tp, long long *pp, long long *exact,
+                          long long *rows, long long *tpsum, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
