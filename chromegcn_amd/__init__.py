@@ -9,6 +9,8 @@ from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, 
 from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
+from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_norm_vector_host,  # noqa: F401
+                      kr_balance_host)
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 from .thresholds import (ThresholdCounts, best_thresholds, metrics_from_counts, threshold_counts,  # noqa: F401
                          threshold_counts_host, threshold_metrics, threshold_metrics_host)
@@ -23,4 +25,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "kl_gradient_host", "tsne_embed_host", "Curves", "roc_curves", "pr_curves", "optimal_cutoffs",
            "roc_curve_host", "pr_curve_host", "optimal_cutoff_host", "ThresholdCounts", "threshold_counts",
            "threshold_metrics", "metrics_from_counts", "best_thresholds", "threshold_counts_host",
-           "threshold_metrics_host"]
+           "threshold_metrics_host", "HicNormError", "contact_matrix_host", "kr_balance_host",
+           "hic_norm_vector_host", "hic_norm_vector"]

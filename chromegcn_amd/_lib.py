@@ -111,6 +111,14 @@ _HEADER = {
     "cgcn_debug_threshold_route": (_c_int, "n:ll C:i T:i"),
     "cgcn_threshold_counts": (_c_int, "stream n:ll C:i T:i probs targets thresholds pos tp pp exact rows tpsum workspace "
                                       "workspace_bytes:z"),
+    "cgcn_hicnorm_workspace_bytes": (_c_sz, "M:ll n_bins:ll"),
+    "cgcn_hicnorm_count": (_c_int, "stream M:ll pos1 pos2 count resolution_bp:i n_bins:ll workspace workspace_bytes:z sizes"),
+    "cgcn_hicnorm_fill": (_c_int, "stream M:ll pos1 pos2 count resolution_bp:i n_bins:ll capacity:ll workspace "
+                                  "workspace_bytes:z rowptr col val vc row_nnz sizes"),
+    "cgcn_hicnorm_spmv": (_c_int, "stream n:i rowptr col val mask x p y long_row_nnz:i"),
+    "cgcn_hicnorm_kr_state_bytes": (_c_sz, "n:i"),
+    "cgcn_hicnorm_kr_step": (_c_int, "stream n:i op:i flag:i parity:i vc row_nnz state state_bytes:z"),
+    "cgcn_hicnorm_vector": (_c_int, "stream n:i kind:i vc state out"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

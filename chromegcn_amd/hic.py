@@ -7,7 +7,8 @@ The rule, for one chromosome: a record (pos1, pos2, count) survives iff pos1 != 
 peaks; its value is count / (nv[pos1 // res] * nv[pos2 // res]) in float64, nv = the norm vector with NaN and 0 replaced by
 +inf (count itself without a vector); the K survivors that come first in a STABLE descending sort by value are taken;
 A[i, j] = A[j, i] = 1 for each of them, i, j the ranks of the two positions among the windows.  Outside the contract: two
-records with the same ordered (pos1, pos2), NaN counts, 2 K >= 2^31.
+records with the same ordered (pos1, pos2), NaN counts, 2 K >= 2^31.  Where a norm vector is taken, the names 'KR', 'VC' and
+'SQRTVC' stand for the vector computed from the records themselves (chromegcn_amd/hicnorm.py; HicContacts.norm_vector).
 
 Records coarser than the windows (K562: 5 kb records, 1 kb windows; data/extras/upsample_hic.py:36-44,
 data/create_data.py:47-55): with `window_bp` dividing `resolution_bp`, up = resolution_bp / window_bp <= 8, the graph is the
@@ -163,11 +164,20 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
     return idx, i, j, v
 
 
-def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None) -> sp.csr_matrix:
+def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None,
+                         norm_args=None) -> sp.csr_matrix:
     """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns).  With window_bp: of
-    the expanded file, which is never written out (the CPU path for coarse records at full size)."""
-    n = _windows(window_start).size
+    the expanded file, which is never written out (the CPU path for coarse records at full size).  norm = 'KR' / 'VC' /
+    'SQRTVC': the vector computed from the records (hicnorm.hic_norm_vector_host with norm_args)."""
+    ws = _windows(window_start)
+    n = ws.size
     k = _budget(hic_edges)
+    if isinstance(norm, str):
+        from . import hicnorm
+        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **(norm_args or {}))
+        if not info.get("converged", True):
+            raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+        norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
     _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp)
     take = np.argsort(-v, kind="stable")[:k]
     i, j = i[take], j[take]
@@ -494,6 +504,8 @@ class HicContacts:
         self._survivors_up = {}  # of the current window set, per (resolution_bp, window_bp)
         self._on_grid = set()    # the resolutions of which every position is known to be a multiple
         self._vectors = []   # (the caller's object, its device copy): a sweep passes the same vector again
+        self._matrices = {}  # (resolution_bp, n_bins or None) -> hicnorm.DeviceContactMatrix
+        self._norms = {}     # norm_vector's argument tuple -> (vector, info)
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
 
     @classmethod
@@ -605,6 +617,32 @@ class HicContacts:
         t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(device=self.device, dtype=dtype).contiguous()
 
+    def contact_matrix(self, resolution_bp, n_bins=None):
+        """the symmetric fp64 contact matrix of the records on the device (hicnorm.DeviceContactMatrix), aggregated once per
+        (resolution_bp, n_bins) and kept"""
+        from . import hicnorm
+        key = (int(resolution_bp), None if n_bins is None else int(n_bins))
+        if key not in self._matrices:
+            a = hicnorm.aggregate_contacts(self.pos1, self.pos2, self.count, key[0], key[1])
+            self._matrices[key] = self._matrices[(key[0], a.n)] = a
+        return self._matrices[key]
+
+    def norm_vector(self, kind, resolution_bp, n_bins=None, tol=1e-6, max_mvp=1000, min_row_nnz=1, kr_retry=True,
+                    return_info=False, long_row_nnz=-1):
+        """The 'KR', 'VC' or 'SQRTVC' vector of the records (hicnorm's docstring) as a float64 device tensor [n_bins]; NaN
+        at empty (KR: and excluded) bins.  The three kinds share one aggregation; vectors are kept per argument tuple.  A KR
+        that did not converge is returned as it is with info["converged"] False: build(norm="KR") raises instead.
+        return_info: (vector, info) -- KR: converged, residual, mvp, outer, kept, excluded, min_row_nnz, ladder, host_syncs."""
+        from . import hicnorm
+        kr = dict(tol=float(tol), max_mvp=int(max_mvp), min_row_nnz=int(min_row_nnz), kr_retry=bool(kr_retry))
+        key = (hicnorm._kind(kind), int(resolution_bp), None if n_bins is None else int(n_bins), int(long_row_nnz))
+        key += tuple(sorted(kr.items())) if kind == "KR" else ()
+        if key not in self._norms:
+            a = self.contact_matrix(resolution_bp, n_bins)
+            self._norms[key] = hicnorm.vector_from_matrix(a, kind, long_row_nnz=int(long_row_nnz), **(kr if kind == "KR" else {}))
+        v, info = self._norms[key]
+        return (v, dict(info)) if return_info else v
+
     def _norm(self, norm) -> Optional[torch.Tensor]:
         if norm is None:
             return None
@@ -664,11 +702,20 @@ class HicContacts:
             self._survivors_up[(res, wbp)] = int(s)
         return self._survivors_up[(res, wbp)]
 
-    def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None):
+    def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None):
         """(rowptr int32 [N + 1], col int32 [>= nnz], sizes int64 [2] = (nnz, survivors)), all on the device, enqueued
-        on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors()."""
+        on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors() -- and, for
+        norm = 'KR' / 'VC' / 'SQRTVC', those of norm_vector(norm, resolution_bp, **norm_args) when it is not cached; a KR
+        that did not converge raises HicNormError."""
         from . import _lib
         k = _budget(hic_edges)
+        if isinstance(norm, str):
+            from . import hicnorm
+            norm, info = self.norm_vector(norm, resolution_bp, return_info=True, **(norm_args or {}))
+            if not info.get("converged", True):
+                raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+            ws_last = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
+            norm = hicnorm.pad_vector(norm, int(ws_last[-1]) // int(resolution_bp) + 1 if ws_last.size else 0)
         up = _upsample(resolution_bp, window_bp)
         direct = window_bp is None or int(window_bp) == int(resolution_bp)
         cap = self.survivors(window_start) if direct else self.survivors(window_start, resolution_bp, window_bp)
@@ -699,10 +746,13 @@ class HicContacts:
                           col_out=col, nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
         return rowptr, col, sizes
 
-    def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None):
+    def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
+              norm_args=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
-        host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back."""
-        rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp)
+        host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back.  norm: a vector,
+        None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords)."""
+        rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
+                                            norm_args=norm_args)
         n = int(rowptr.numel()) - 1
         g = G.normalize_device_csr(adj_type, n, rowptr, col, None, self.device)
         if not return_raw:
@@ -713,13 +763,14 @@ class HicContacts:
 
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
-                    return_raw=False, window_bp=None):
+                    return_raw=False, window_bp=None, norm_args=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
     `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
     coarser than the windows and stand for their expanded file (the module's docstring)."""
     _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
-    return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp)
+    return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp,
+                   norm_args=norm_args)
 
 
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
@@ -732,23 +783,28 @@ def contact_cache_path(root: str, chrom: str) -> str:
 
 
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",
-                               sizes: Optional[Dict[str, int]] = None, window_bp=None) -> Dict[str, G.ChromGraph]:
+                               sizes: Optional[Dict[str, int]] = None, window_bp=None,
+                               compute_norm: bool = False) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
-    (`-hic_upsample`): the window size; a cache whose resolution_bp is coarser is built as its expanded file."""
+    (`-hic_upsample`): the window size; a cache whose resolution_bp is coarser is built as its expanded file.  compute_norm
+    (`-hic_compute_norm`): a `hicnorm` of 'KR' / 'VC' / 'SQRTVC' that the cache lacks is computed from its records."""
+    from . import hicnorm as HN
     out = {}
     for chrom in chroms:
         c = load_contacts_cache(contact_cache_path(root, chrom))
         if c.window_start is None:
             raise ValueError("%s holds no window list" % contact_cache_path(root, chrom))
-        if hicnorm and hicnorm not in c.norms:
+        computed = bool(compute_norm) and hicnorm in HN.KINDS and hicnorm not in c.norms
+        if hicnorm and hicnorm not in c.norms and not computed:
             raise ValueError("%s holds no %r norm vector (has: %s)" % (contact_cache_path(root, chrom), hicnorm,
                                                                        ", ".join(sorted(c.norms)) or "none"))
         if sizes is not None and sizes[chrom] != c.window_start.size:
             raise ValueError("%s has %d windows but the chromosome's features have %d rows"
                              % (contact_cache_path(root, chrom), c.window_start.size, sizes[chrom]))
         up = {"window_bp": int(window_bp)} if window_bp is not None and c.resolution_bp > int(window_bp) else {}
-        out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, c.norms[hicnorm] if hicnorm else None, c.resolution_bp,
+        norm = hicnorm if computed else c.norms[hicnorm] if hicnorm else None
+        out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device, **up)
     return out

@@ -32,6 +32,8 @@ def parse(argv=None):
     ap.add_argument("-hic_contacts", type=str, default=None, metavar="DIR",
                     help="build every chromosome's graph on the GPU from DIR/<chrom>.cghic (chromegcn_amd.hic contact caches) "
                          "for the given -hicsize / -hicnorm, instead of opening a pickle under -graph_root")
+    ap.add_argument("-hic_compute_norm", action="store_true",
+                    help="-hic_contacts: compute a -hicnorm of KR / VC / SQRTVC that a cache lacks from its records on the GPU")
     ap.add_argument("-hic_upsample", action="store_true",
                     help="-hic_contacts: a cache whose records are coarser than -window_size (K562: 5 kb) stands for its "
                          "expanded file, every record for the window pairs it covers (data/extras/upsample_hic.py)")
@@ -78,7 +80,8 @@ def load_inputs(opt):
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
-                                                        window_bp=opt.window_size if opt.hic_upsample else None)
+                                                        window_bp=opt.window_size if opt.hic_upsample else None,
+                                                        compute_norm=opt.hic_compute_norm)
         elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:

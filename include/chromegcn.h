@@ -857,6 +857,86 @@ int cgcn_threshold_counts(cgcn_stream_t stream, long long n, int C, int T, const
                           const float *thresholds, long long *pos, long long *tp, long long *pp, long long *exact,
                           long long *rows, long long *tpsum, void *workspace, size_t workspace_bytes);
 
+/*
+ * KR / VC / SQRTVC normalisation vectors of a Hi-C contact matrix from the contact records (chromegcn_amd/hicnorm.py,
+ * DESIGN.md section 4.10).  These seven functions are additions to ABI 26: CGCN_ABI_VERSION stays 26, nothing above changes.
+ * Enqueue only: no allocation, no synchronisation, caller-owned workspace and state, no floating-point atomics -- the same
+ * inputs give the same bits in every run.
+ *
+ * The matrix A (n_bins x n_bins, symmetric, fp64): a record (pos1, pos2, c) with i = pos1 / resolution_bp, j = pos2 /
+ * resolution_bp adds c to A[i][i] when i == j and to A[i][j] and A[j][i] otherwise; the records of one entry are added in
+ * record order.  cgcn_hicnorm_count writes sizes[0] = the number of stored entries, sizes[1] = flags (1: a count that is
+ * negative or not finite, 2: a negative position, 4: a bin >= n_bins when n_bins > 0; such records are left out),
+ * sizes[2] = the largest bin + 1; sizes holds four int64.  n_bins = 0 there: not known yet.  cgcn_hicnorm_fill writes the
+ * CSR (rowptr [n_bins + 1], col and val [capacity], columns ascending, duplicates merged), vc[i] = the sum of row i (in the
+ * order of cgcn_hicnorm_spmv's default route), row_nnz[i] = its entries > 0, and sizes again; capacity >= sizes[0], or the
+ * matrix is cut off behind `capacity` entries (no row pointer exceeds it; sizes[0] tells).  M < 2^31 - 1, n_bins < 2^31 - 1, capacity < 2^31 - 1,
+ * and for cgcn_hicnorm_fill 2 bits(n_bins) + bits(M) + 1 <= 64 (the sort key holds row, column and record index: 250 000 bins
+ * with 1.3 * 10^8 records fit, 2^20 bins with more than 2^23 records do not), else CGCN_ERR_UNSUPPORTED and
+ * cgcn_hicnorm_workspace_bytes(M, n_bins) is 0.
+ *
+ * cgcn_hicnorm_spmv: y = mask o (A (mask o x o p)), o the elementwise product; mask (0 / 1 as fp64), x and p may each be
+ * NULL (all ones).  A row with more than long_row_nnz entries is summed by a whole workgroup, any other by 16 lanes;
+ * long_row_nnz < 0: the default (512); 0: every non-empty row takes the workgroup route.  The two routes add in different
+ * orders, each in a fixed one.
+ *
+ * Knight-Ruiz balancing (Knight & Ruiz 2013, inner-outer Newton with CG; the listing is in chromegcn_amd/hicnorm.py) is
+ * driven by the host, one bounded step per call.  The state (cgcn_hicnorm_kr_state_bytes(n) bytes, 8-byte aligned) is
+ * CGCN_HICNORM_HDR fp64 (the record, then reduction partials) followed by eleven vectors of stride (n + 31) & ~31 fp64 in
+ * the order CGCN_HICNORM_VEC_*: mask, x, v, p, w, y[2], rk[2], Z[2]; `parity` names the current copy of y, rk and Z.
+ * Record, fp64: [0] rho1, [1] rho2, [2] p.w, [3] min ynew, [4] max ynew, [5] gamma of the lower bound, [6] gamma of the
+ * upper bound, [7] rho1 after the step, [8] rout, [9] alpha, [10] kept rows, [11] non-empty rows.  Steps (w holds a product
+ * of cgcn_hicnorm_spmv where one is named):
+ *   CGCN_HICNORM_OP_MASK   mask = vc > 0 and row_nnz >= flag; x = y = 1; [10], [11]
+ *   CGCN_HICNORM_OP_RES    w = product(x, p = y when flag, else p = NULL); x *= y (flag); v = x o w; rk = mask o (1 - v);
+ *                          y = 1; [0] = [8] = rk.rk
+ *   CGCN_HICNORM_OP_FIRST  Z = rk / v; p = Z; [0] = rk.Z
+ *   CGCN_HICNORM_OP_DIR    p = Z + ([7] / [0]) p   (after an accepted step, whose copy `parity` now names)
+ *   CGCN_HICNORM_OP_W      w = product(x, p); w = x o w + v o p; flag: [1] = [0], [0] = [7] first; [2] = p.w; [9] = [0] / [2]
+ *   CGCN_HICNORM_OP_Y      the other copy: ynew = y + [9] p, rk - [9] w, Z = that / v; [3] .. [7]
+ *   CGCN_HICNORM_OP_CLIP   y += gamma ([9] p), gamma = [5] (flag 0) or [6] (flag 1)
+ * cgcn_hicnorm_vector: kind 0: out = vc, 1: sqrt(vc), both NaN where vc is not > 0; 2: 1 / x on the kept rows of `state`,
+ * NaN elsewhere.
+ * CGCN_ERR_BAD_ARG: a negative size, resolution_bp < 1, a NULL buffer that would be read or written, an unknown op, kind or
+ * parity; CGCN_ERR_WORKSPACE: workspace_bytes / state_bytes below the queried size.
+ */
+#define CGCN_HICNORM_REC 32
+#define CGCN_HICNORM_HDR (CGCN_HICNORM_REC + 6 * 1024)
+#define CGCN_HICNORM_OP_MASK 0
+#define CGCN_HICNORM_OP_RES 1
+#define CGCN_HICNORM_OP_FIRST 2
+#define CGCN_HICNORM_OP_DIR 3
+#define CGCN_HICNORM_OP_W 4
+#define CGCN_HICNORM_OP_Y 5
+#define CGCN_HICNORM_OP_CLIP 6
+#define CGCN_HICNORM_VEC_MASK 0
+#define CGCN_HICNORM_VEC_X 1
+#define CGCN_HICNORM_VEC_V 2
+#define CGCN_HICNORM_VEC_P 3
+#define CGCN_HICNORM_VEC_W 4
+#define CGCN_HICNORM_VEC_Y 5
+#define CGCN_HICNORM_VEC_RK 7
+#define CGCN_HICNORM_VEC_Z 9
+
+size_t cgcn_hicnorm_workspace_bytes(long long M, long long n_bins);
+
+int cgcn_hicnorm_count(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                       int resolution_bp, long long n_bins, void *workspace, size_t workspace_bytes, long long *sizes);
+
+int cgcn_hicnorm_fill(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                      int resolution_bp, long long n_bins, long long capacity, void *workspace, size_t workspace_bytes,
+                      int32_t *rowptr, int32_t *col, double *val, double *vc, int32_t *row_nnz, long long *sizes);
+
+int cgcn_hicnorm_spmv(cgcn_stream_t stream, int n, const int32_t *rowptr, const int32_t *col, const double *val,
+                      const double *mask, const double *x, const double *p, double *y, int long_row_nnz);
+
+size_t cgcn_hicnorm_kr_state_bytes(int n);
+
+int cgcn_hicnorm_kr_step(cgcn_stream_t stream, int n, int op, int flag, int parity, const double *vc, const int32_t *row_nnz,
+                         void *state, size_t state_bytes);
+
+int cgcn_hicnorm_vector(cgcn_stream_t stream, int n, int kind, const double *vc, const void *state, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,10 @@ Walks the reference's layout (data/7create_graph_new.py:145, :174-175):
 plus the `<chrom>_<res>kb.{KR,VC,SQRTVC}norm` files that exist beside it, and a windows bed (chrom<TAB>start<TAB>...: the
 chromosome's windows with peaks, create_bin_dict :14-47).  Per chromosome the contact text is parsed on the device
 (chromegcn_amd.hic.contacts_from_text), the norm vectors -- one value per bin -- on the host, and
-`<out>/<chrom>.cghic` is written (hic.save_contacts_cache).  Prints one JSON line per chromosome."""
+`<out>/<chrom>.cghic` is written (hic.save_contacts_cache).  Prints one JSON line per chromosome.
+--compute-norms KR,VC,SQRTVC also computes those vectors from the records on the device (chromegcn_amd/hicnorm.py) and
+stores them as cKR / cVC / cSQRTVC -- names Juicer's files never take -- so that `-hicnorm cKR` finds them; the line then
+carries what the KR run reports.  A KR that did not converge is not stored."""
 import argparse
 import json
 import os
@@ -24,7 +27,7 @@ def chrom_dir(hic_root, cell, res_kb, chrom):
     return os.path.join(hic_root, "%s_combined" % cell, "%skb_resolution_intrachromosomal" % res_kb, chrom, "MAPQGE30")
 
 
-def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=None):
+def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=None, compute_norms=()):
     """writes <out>/<chrom>.cghic for every chromosome of `chroms`; returns one dict per chromosome"""
     windows = hic.windows_from_bed(bed, chroms)
     os.makedirs(out, exist_ok=True)
@@ -42,11 +45,19 @@ def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=
             p = os.path.join(d, "%s_%skb.%snorm" % (chrom, res_kb, name))
             if os.path.exists(p):
                 norms[name] = np.loadtxt(p, dtype=np.float64, ndmin=1)
+        computed = {}
+        for name in compute_norms:
+            v, info = c.norm_vector(name, int(res_kb) * 1000, return_info=True)
+            if name == "KR":
+                computed["KR"] = info
+            if info.get("converged", True):
+                norms["c" + name] = v.cpu().numpy()
         path = hic.contact_cache_path(out, chrom)
         hic.save_contacts_cache(path, c.to_host(norms=norms, resolution_bp=int(res_kb) * 1000, window_start=windows[chrom]))
         lines.append({"chrom": chrom, "records": c.M, "text_bytes": c.text_info["n_bytes"],
                       "host_parsed_lines": int(c.text_info["slow_lines"].size), "windows": int(windows[chrom].size),
-                      "norms": sorted(norms), "cache": path, "seconds": round(time.perf_counter() - t0, 3)})
+                      "norms": sorted(norms), "cache": path, "seconds": round(time.perf_counter() - t0, 3),
+                      **({"kr": computed["KR"]} if "KR" in computed else {})})
         print(json.dumps(lines[-1]), flush=True)
     return lines
 
@@ -60,11 +71,16 @@ def main(argv=None):
     ap.add_argument("--chroms", required=True, help="comma-separated")
     ap.add_argument("--out", required=True, help="the directory of the caches (train's -hic_contacts)")
     ap.add_argument("--chunk-bytes", type=int, default=None)
+    ap.add_argument("--compute-norms", default="", help="comma-separated subset of KR,VC,SQRTVC: stored as cKR, cVC, cSQRTVC")
     opt = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("tools/hic_ingest.py needs a GPU")
-    return ingest(opt.hic_root, opt.cell, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, chunk_bytes=opt.chunk_bytes)
+    kinds = [k for k in opt.compute_norms.split(",") if k]
+    if any(k not in NORMS for k in kinds):
+        raise SystemExit("--compute-norms takes a subset of %s" % ",".join(NORMS))
+    return ingest(opt.hic_root, opt.cell, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, chunk_bytes=opt.chunk_bytes,
+                  compute_norms=kinds)
 
 
 if __name__ == "__main__":
