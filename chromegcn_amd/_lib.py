@@ -119,6 +119,12 @@ _HEADER = {
     "cgcn_hicnorm_kr_state_bytes": (_c_sz, "n:i"),
     "cgcn_hicnorm_kr_step": (_c_int, "stream n:i op:i flag:i parity:i vc row_nnz state state_bytes:z"),
     "cgcn_hicnorm_vector": (_c_int, "stream n:i kind:i vc state out"),
+    "cgcn_pairs_parse_workspace_bytes": (_c_sz, "n_bytes:ll"),
+    "cgcn_pairs_parse": (_c_int, "stream text n_bytes:ll byte_base:ll names n_chroms:i resolution_bp:i binning:i min_diff:ll keys "
+                                 "key_capacity:ll flags flag_capacity:ll totals chunk_totals workspace workspace_bytes:z"),
+    "cgcn_pairs_reduce_workspace_bytes": (_c_sz, "n_keys:ll"),
+    "cgcn_pairs_reduce": (_c_int, "stream n_keys:ll keys n_chroms:i resolution_bp:i pos1_out pos2_out count_out chrom_offsets "
+                                  "n_records workspace workspace_bytes:z"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

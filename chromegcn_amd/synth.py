@@ -156,6 +156,50 @@ def raw_contacts_coarse(chrom: str, resolution_bp: int = 5000, window_bp: int = 
             "resolution_bp": int(resolution_bp), "window_bp": int(window_bp)}
 
 
+def read_pairs(chrom_sizes: Dict[str, int], n_pairs: int, seed: int, inter_share: float = 0.15, duplicate_share: float = 0.2,
+               name_prefix: str = "SRR5831489") -> bytes:
+    """The text of a HiC-Pro-shaped `allValidPairs` file of `n_pairs` lines over the chromosomes of `chrom_sizes` (name ->
+    length in bp): 12 TAB-separated columns -- read name, chr1, pos1, strand1, chr2, pos2, strand2, fragment size, two
+    restriction-fragment names and two mapping qualities -- with read names of varying length, an `inter_share` of
+    inter-chromosomal pairs, separations that follow the truncated 1/k law of contact_graph(hic_like=True) (down to a few bp, so
+    that some pairs fall into one bin), and a `duplicate_share` of lines that repeat an earlier pair's two positions under a
+    new read name.  Pairs are spread over the chromosomes by length; the second read is the upstream one in half of them.
+    Seeded: the same arguments give the same bytes."""
+    rng = np.random.RandomState(seed)
+    names = list(chrom_sizes)
+    sizes = np.array([chrom_sizes[c] for c in names], dtype=np.int64)
+    n = int(n_pairs)
+    c1 = rng.choice(len(names), n, p=sizes / sizes.sum())
+    size = sizes[c1]
+    dist = np.minimum(np.floor(np.exp(rng.random_sample(n) * np.log(size - 1.0))).astype(np.int64), size - 1)
+    a = (rng.random_sample(n) * (size - dist)).astype(np.int64)
+    b = a + dist
+    dup = np.flatnonzero(rng.random_sample(n) < duplicate_share)
+    dup = dup[dup > 0]
+    src = (rng.random_sample(dup.size) * dup).astype(np.int64)   # an earlier line (which may itself be a copy further down)
+    order = np.argsort(dup)
+    for d, s in zip(dup[order].tolist(), src[order].tolist()):
+        c1[d], a[d], b[d] = c1[s], a[s], b[s]
+    c2 = c1.copy()
+    if len(names) > 1:
+        inter = np.flatnonzero(rng.random_sample(n) < inter_share)
+        c2[inter] = (c1[inter] + 1 + rng.randint(0, len(names) - 1, inter.size)) % len(names)
+        b[inter] = (rng.random_sample(inter.size) * sizes[c2[inter]]).astype(np.int64)
+    swap = rng.random_sample(n) < 0.5
+    a, b = np.where(swap & (c1 == c2), b, a), np.where(swap & (c1 == c2), a, b)
+    cols = [("%s.%%d" % name_prefix) % k for k in range(1, n + 1)]
+    for extra in (rng.randint(1101, 2679, n), rng.randint(1000, 30000, n), rng.randint(1000, 200000, n)):
+        cols = [c + ":" + e for c, e in zip(cols, map(str, extra.tolist()))]   # read names of varying length
+    s1, s2 = rng.randint(0, 2, n).tolist(), rng.randint(0, 2, n).tolist()
+    n1, n2 = [names[k] for k in c1.tolist()], [names[k] for k in c2.tolist()]
+    rows = zip(cols, n1, map(str, a.tolist()), ("+-"[k] for k in s1), n2, map(str, b.tolist()), ("+-"[k] for k in s2),
+               map(str, rng.randint(50, 900, n).tolist()),
+               ("HIC_%s_%d" % t for t in zip(n1, rng.randint(1, 900000, n).tolist())),
+               ("HIC_%s_%d" % t for t in zip(n2, rng.randint(1, 900000, n).tolist())),
+               map(str, rng.randint(0, 61, n).tolist()), map(str, rng.randint(0, 61, n).tolist()))
+    return ("\n".join(map("\t".join, rows)) + "\n").encode()
+
+
 def chrom_features(n: int, d: int, n_labels: int, seed: int, positive_rate: float = 0.05) -> Dict[str, torch.Tensor]:
     g = torch.Generator().manual_seed(seed)
     return {"forward": torch.randn(n, d, generator=g), "backward": torch.randn(n, d, generator=g),

@@ -937,6 +937,91 @@ int cgcn_hicnorm_kr_step(cgcn_stream_t stream, int n, int op, int flag, int pari
 
 int cgcn_hicnorm_vector(cgcn_stream_t stream, int n, int kind, const double *vc, const void *state, double *out);
 
+/*
+ * Read-pair text (a HiC-Pro `allValidPairs` file: one line per read pair, as data/eqtl_data/HiChIP.py:8-24 reads it) turned on
+ * the device into binned pairs and into contact records, the arrays cgcn_hic_count, cgcn_hic_build and cgcn_hicnorm_* take
+ * (chromegcn_amd/pairs.py).  Additions to ABI 26 like the functions above; nothing above changes.
+ *
+ * THE RULE.
+ * Lines.  A line ends with LF or CR LF; the last line may end with nothing.  An empty line is skipped, as csv.DictReader
+ *   skips it.  A line has at least six TAB-separated fields (read name, chr1, pos1, strand1, chr2, pos2, ...); fields 2, 3, 5
+ *   and 6 are used and the rest are ignored.  Line numbers count every line, empty ones included, from 0.
+ * Parameters.  chroms: 1 to CGCN_PAIRS_MAX_CHROMS names of 1 to CGCN_PAIRS_NAME_MAX bytes each.  resolution_bp >= 8.
+ *   binning: CGCN_PAIRS_NEAREST is the reference's round(int(pos), -3) generalised -- with q, r = divmod(pos, resolution_bp):
+ *   q when 2 r < res, q + 1 when 2 r > res, the even one of the two on a tie; times resolution_bp.  CGCN_PAIRS_FLOOR is
+ *   pos - pos % resolution_bp, the binning of Juicer's dumps and of data/7create_graph_old.py:89.  min_diff: a pair is kept iff
+ *   |p2 - p1| > min_diff on the binned positions (the reference: 10).
+ * Fate of a pair.  Field 2 != field 5 (byte for byte): dropped, counted as inter_chrom, its positions are not looked at.
+ *   Otherwise both positions are read and binned; then a name that is not in chroms: dropped, other_chrom; a pair that fails
+ *   min_diff: dropped, too_close; else kept.
+ * Classes of line.
+ *   FAST (decided and parsed on the device): at most CGCN_PAIRS_LINE_MAX bytes without its terminator, six or more fields,
+ *     fields 3 and 6 one to ten plain digits with a value below 2^31, fields 2 and 5 of 1 to CGCN_PAIRS_NAME_MAX bytes, no `"`
+ *     byte and no CR other than the one of a CR LF.
+ *   SLOW: not fast, but the reference's statements accept it: blanks, `+` or `_` inside int(), a longer line, a longer name.
+ *     The device reports it; the caller runs the host rule on exactly those lines and merges their pairs in at their input
+ *     positions.
+ *   MALFORMED: everything else -- fewer than six fields, a position int() refuses (on a line whose two names are equal), a
+ *     negative position, a binned position >= 2^31, a `"` byte, a lone CR.
+ *   The device decides fast exactly.  Of the other lines it reports as CGCN_PAIRS_MALFORMED the ones that (within the bound)
+ *   hold fewer than five TABs, a `"`, a lone CR or a binned position >= 2^31, and every remaining one as CGCN_PAIRS_SLOW:
+ *   what the reference's statements make of a reported line is the host's to say.
+ *
+ * STAGE A, binned pairs: cgcn_pairs_parse takes one chunk of whole lines (text: n_bytes bytes, 16-byte aligned, the bytes
+ * byte_base .. of the file) and appends the keys of its kept pairs, in input order, to keys (device uint64 [key_capacity])
+ * behind the keys of the earlier chunks.  A key is  chromosome index << 57 | lo << 29 | hi << 1 | swapped  with
+ * lo = min(p1, p2) / res, hi = max(p1, p2) / res (28 bits each: binned positions are below 2^31 and res >= 8) and
+ * swapped = 1 when p1 > p2; bit 63 is 0.  names: device bytes [n_chroms][16], 8-byte aligned -- a name's bytes, zeros, and its
+ * length in byte 15.  totals (device int64 [8], the CGCN_PAIRS_T_* words; the caller zeroes it before the first chunk): the
+ * running totals; the call starts its line numbers at totals[CGCN_PAIRS_T_LINES] and its keys at totals[CGCN_PAIRS_T_KEPT]
+ * and adds the chunk's totals, which it also leaves in chunk_totals (device int64 [8]).  A key whose index is key_capacity or
+ * more is not written (the totals still count it).  flags: int64 [flag_capacity][4] = (line, byte offset of the line in the
+ * file, kind, number of keys in front of the line once this call's keys are in place), appended in any order from entry 0 in
+ * every call; when the chunk's slow + malformed lines exceed flag_capacity only flag_capacity entries were written: restore
+ * totals and call again with a larger one.
+ *
+ * STAGE B, contact records (this project's definition, not the reference's, which stops at the binned pairs and never
+ * aggregates them: it is the one Juicer's `dump observed` would give for the same pairs): cgcn_pairs_reduce sorts n_keys keys
+ * and writes, per chromosome in table order, one record for every distinct unordered bin pair -- pos1 = lo * res,
+ * pos2 = hi * res (int32), count = the number of kept pairs (fp64) -- sorted by (pos1, pos2).  pos1_out / pos2_out / count_out
+ * hold n_keys entries; n_records (device int64 [1]) receives the record count and chrom_offsets (device int64 [n_chroms + 1])
+ * the first record of every chromosome.  keys is left as it is.
+ *
+ * Enqueue only, no allocation, no sync, nothing kept between calls except what the caller passes back in.  Integer arithmetic
+ * throughout; the one conversion is count's.  CGCN_ERR_BAD_ARG: a negative size, an unknown binning, a NULL or misaligned
+ * buffer; CGCN_ERR_UNSUPPORTED: n_chroms outside 1 .. CGCN_PAIRS_MAX_CHROMS or resolution_bp < 8 (the key has no room for
+ * them), n_keys >= 2^31 - 1; CGCN_ERR_WORKSPACE: workspace_bytes below cgcn_pairs_parse_workspace_bytes(n_bytes) /
+ * cgcn_pairs_reduce_workspace_bytes(n_keys).
+ */
+#define CGCN_PAIRS_LINE_MAX 256
+#define CGCN_PAIRS_NAME_MAX 15
+#define CGCN_PAIRS_MAX_CHROMS 64
+#define CGCN_PAIRS_SLOW 1
+#define CGCN_PAIRS_MALFORMED 2
+#define CGCN_PAIRS_NEAREST 0
+#define CGCN_PAIRS_FLOOR 1
+#define CGCN_PAIRS_T_LINES 0
+#define CGCN_PAIRS_T_EMPTY 1
+#define CGCN_PAIRS_T_KEPT 2
+#define CGCN_PAIRS_T_INTER_CHROM 3
+#define CGCN_PAIRS_T_OTHER_CHROM 4
+#define CGCN_PAIRS_T_TOO_CLOSE 5
+#define CGCN_PAIRS_T_SLOW 6
+#define CGCN_PAIRS_T_MALFORMED 7
+
+size_t cgcn_pairs_parse_workspace_bytes(long long n_bytes);
+
+int cgcn_pairs_parse(cgcn_stream_t stream, const void *text, long long n_bytes, long long byte_base, const void *names,
+                     int n_chroms, int resolution_bp, int binning, long long min_diff, unsigned long long *keys,
+                     long long key_capacity, long long *flags, long long flag_capacity, long long *totals,
+                     long long *chunk_totals, void *workspace, size_t workspace_bytes);
+
+size_t cgcn_pairs_reduce_workspace_bytes(long long n_keys);
+
+int cgcn_pairs_reduce(cgcn_stream_t stream, long long n_keys, const unsigned long long *keys, int n_chroms, int resolution_bp,
+                      int32_t *pos1_out, int32_t *pos2_out, double *count_out, long long *chrom_offsets,
+                      long long *n_records, void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

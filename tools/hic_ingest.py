@@ -8,7 +8,11 @@ chromosome's windows with peaks, create_bin_dict :14-47).  Per chromosome the co
 `<out>/<chrom>.cghic` is written (hic.save_contacts_cache).  Prints one JSON line per chromosome.
 --compute-norms KR,VC,SQRTVC also computes those vectors from the records on the device (chromegcn_amd/hicnorm.py) and
 stores them as cKR / cVC / cSQRTVC -- names Juicer's files never take -- so that `-hicnorm cKR` finds them; the line then
-carries what the KR run reports.  A KR that did not converge is not stored."""
+carries what the KR run reports.  A KR that did not converge is not stored.
+--pairs FILE [--pairs-binning floor|nearest] starts one step earlier, for data that has no Juicer output: FILE is a HiC-Pro
+`allValidPairs` file (one line per read pair); its pairs are binned at --resolution-kb and turned into contact records on the
+device (chromegcn_amd/pairs.py) for every chromosome of --chroms, and the same caches are written.  --hic-root and --cell are
+not needed then; there are no norm files, so --compute-norms is what gives a pairs file its vectors."""
 import argparse
 import json
 import os
@@ -62,10 +66,45 @@ def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=
     return lines
 
 
+def ingest_pairs(pairs_file, res_kb, bed, chroms, out, binning="nearest", device="cuda", chunk_bytes=None, compute_norms=()):
+    """writes <out>/<chrom>.cghic for every chromosome of `chroms` from a read-pair file; returns one dict per chromosome"""
+    from chromegcn_amd.pairs import ReadPairs
+    windows = hic.windows_from_bed(bed, chroms)
+    os.makedirs(out, exist_ok=True)
+    res = int(res_kb) * 1000
+    kw = {} if chunk_bytes is None else {"chunk_bytes": int(chunk_bytes)}
+    t0 = time.perf_counter()
+    rp = ReadPairs.from_text(pairs_file, chroms=chroms, resolution_bp=res, binning=binning, device=device, **kw)
+    records = rp.contacts_all()
+    t_parse = time.perf_counter() - t0
+    lines = []
+    for chrom in chroms:
+        t0 = time.perf_counter()
+        c, norms, computed = records[chrom], {}, {}
+        for name in compute_norms:
+            v, info = c.norm_vector(name, res, return_info=True)
+            if name == "KR":
+                computed["KR"] = info
+            if info.get("converged", True):
+                norms["c" + name] = v.cpu().numpy()
+        path = hic.contact_cache_path(out, chrom)
+        hic.save_contacts_cache(path, c.to_host(norms=norms, resolution_bp=res, window_start=windows[chrom]))
+        lines.append({"chrom": chrom, "records": c.M, "kept_pairs": rp.info["kept_per_chrom"][chrom],
+                      "host_parsed_lines": rp.info["slow"], "windows": int(windows[chrom].size), "norms": sorted(norms),
+                      "cache": path, "seconds": round(time.perf_counter() - t0 + (t_parse if not lines else 0.0), 3),
+                      **({"kr": computed["KR"]} if "KR" in computed else {})})
+        print(json.dumps(lines[-1]), flush=True)
+    print(json.dumps({"pairs": {k: v for k, v in rp.info.items() if k not in ("slow_lines", "kept_per_chrom")}}), flush=True)
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--hic-root", required=True)
-    ap.add_argument("--cell", required=True, help="the cell type: <hic_root>/<cell>_combined")
+    ap.add_argument("--hic-root")
+    ap.add_argument("--cell", help="the cell type: <hic_root>/<cell>_combined")
+    ap.add_argument("--pairs", help="a HiC-Pro allValidPairs file, instead of --hic-root and --cell")
+    ap.add_argument("--pairs-binning", choices=("floor", "nearest"), default="nearest",
+                    help="nearest: the reference's round(pos, -3) at any resolution; floor: Juicer's bins")
     ap.add_argument("--resolution-kb", default="1")
     ap.add_argument("--bed", required=True, help="the windows bed (windows.bed or chipseq_windows.bed of the reference)")
     ap.add_argument("--chroms", required=True, help="comma-separated")
@@ -79,6 +118,11 @@ def main(argv=None):
     kinds = [k for k in opt.compute_norms.split(",") if k]
     if any(k not in NORMS for k in kinds):
         raise SystemExit("--compute-norms takes a subset of %s" % ",".join(NORMS))
+    if opt.pairs:
+        return ingest_pairs(opt.pairs, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, binning=opt.pairs_binning,
+                            chunk_bytes=opt.chunk_bytes, compute_norms=kinds)
+    if not opt.hic_root or not opt.cell:
+        raise SystemExit("--hic-root and --cell are needed unless --pairs is given")
     return ingest(opt.hic_root, opt.cell, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, chunk_bytes=opt.chunk_bytes,
                   compute_norms=kinds)
 
