@@ -147,7 +147,7 @@ def _kr_run_host(A, tol, max_mvp):
         return A @ z
 
     x = np.ones(n)
-    outer = 0
+    outer, clips = 0, [0, 0]
     with np.errstate(all="ignore"):
         v = x * mv(x)
         rk = 1.0 - v
@@ -174,10 +174,12 @@ def _kr_run_host(A, tol, max_mvp):
                 if ynew.min() <= KR_DELTA:
                     sel = ap < 0
                     y = y + np.min((KR_DELTA - y[sel]) / ap[sel], initial=np.inf) * ap
+                    clips[0] += 1
                     break
                 if ynew.max() >= KR_DELTA_UP:
                     sel = ynew > KR_DELTA_UP
                     y = y + np.min((KR_DELTA_UP - y[sel]) / ap[sel], initial=np.inf) * ap
+                    clips[1] += 1
                     break
                 y = ynew
                 rk = rk - alpha * w
@@ -197,12 +199,13 @@ def _kr_run_host(A, tol, max_mvp):
                 eta = max(eta, KR_G * eta_o * eta_o)
             eta = max(min(eta, KR_ETAMAX), stop_tol / math.sqrt(rout) if rout > 0 else KR_ETAMAX)
     return x, {"converged": bool(rout <= rt), "residual": math.sqrt(rout) if rout >= 0 else float("nan"), "mvp": mvp[0],
-               "outer": outer}
+               "outer": outer, "clips": tuple(clips)}
 
 
 def kr_balance_host(A, tol=1e-6, max_mvp=1000, min_row_nnz=1, kr_retry=True):
-    """(x, info): x float64 [n], NaN outside the kept set S; info: converged, residual, mvp, outer, kept, excluded (non-empty
-    rows outside S), min_row_nnz (the value of the run reported), ladder (every value tried), host_syncs (0 here)"""
+    """(x, info): x float64 [n], NaN outside the kept set S; info: converged, residual, mvp, outer, clips (how often the inner
+    loop ended on the listing's lower and on its upper bound of y), kept, excluded (non-empty rows outside S), min_row_nnz
+    (the value of the run reported), ladder (every value tried), host_syncs (0 here)"""
     A = sp.csr_matrix(A, dtype=np.float64)
     vc, nnz = _row_stats_host(A)
     full = vc > 0
@@ -336,7 +339,7 @@ def _kr_run_device(A: DeviceContactMatrix, tol, max_mvp, min_row_nnz, long_row_n
     def product(pvec):
         spmv(A, x=x, p=pvec, mask=m, out=w, long_row_nnz=long_row_nnz)
 
-    c, mvp, outer = 0, 1, 0
+    c, mvp, outer, clips = 0, 1, 0, [0, 0]
     step(_OP_MASK, min_row_nnz, c)
     product(None)
     step(_OP_RES, 0, c)
@@ -358,9 +361,11 @@ def _kr_run_device(A: DeviceContactMatrix, tol, max_mvp, min_row_nnz, long_row_n
             rec = record()
             if rec[3] <= KR_DELTA:
                 step(_OP_CLIP, 0, c)
+                clips[0] += 1
                 break
             if rec[4] >= KR_DELTA_UP:
                 step(_OP_CLIP, 1, c)
+                clips[1] += 1
                 break
             c ^= 1   # accepted: ynew, the new rk and Z are the current copies
             rho1 = rec[7]
@@ -376,7 +381,8 @@ def _kr_run_device(A: DeviceContactMatrix, tol, max_mvp, min_row_nnz, long_row_n
             eta = max(eta, KR_G * eta_o * eta_o)
         eta = max(min(eta, KR_ETAMAX), stop_tol / math.sqrt(rout) if rout > 0 else KR_ETAMAX)
     info = {"converged": bool(rout <= rt), "residual": math.sqrt(rout) if rout >= 0 else float("nan"), "mvp": mvp, "outer": outer,
-            "kept": kept, "excluded": nonempty - kept, "min_row_nnz": int(min_row_nnz), "host_syncs": syncs[0]}
+            "clips": tuple(clips), "kept": kept, "excluded": nonempty - kept, "min_row_nnz": int(min_row_nnz),
+            "host_syncs": syncs[0]}
     return state, info
 
 
@@ -385,7 +391,7 @@ def kr_balance_device(A: DeviceContactMatrix, tol=1e-6, max_mvp=1000, min_row_nn
     from . import _lib
     out = torch.empty(A.n, dtype=torch.float64, device=A.rowptr.device)
     if A.n == 0:
-        return out, {"converged": True, "residual": 0.0, "mvp": 0, "outer": 0, "kept": 0, "excluded": 0,
+        return out, {"converged": True, "residual": 0.0, "mvp": 0, "outer": 0, "clips": (0, 0), "kept": 0, "excluded": 0,
                      "min_row_nnz": int(min_row_nnz), "ladder": [int(min_row_nnz)], "host_syncs": 0}
     tried, mrn, syncs, ladder = [], int(min_row_nnz), 0, None
     with torch.cuda.device(A.rowptr.device):

@@ -126,6 +126,14 @@ def mixed_lines(n, seed, slow_share=0.008):
     return out
 
 
+def dense_lines(n=100000, slow_every=1000, seed=3):
+    """n lines of the shortest form, `d TAB d TAB d` (6 bytes with the LF: two or three line starts in every 16 bytes, 682 or
+    683 in a 4 KiB tile), every `slow_every`-th one the slow line `1 TAB 2 TAB 1e23`"""
+    rng = random.Random(seed)
+    return [b"1\t2\t1e23" if k % slow_every == slow_every - 1 else
+            b"%d\t%d\t%d" % (rng.randrange(10), rng.randrange(10), rng.randrange(10)) for k in range(n)]
+
+
 def juicer_text(pos1, pos2, count) -> bytes:
     """a Juicer `RAWobserved` dump of the records: %d<TAB>%d<TAB>%.1f"""
     rows = np.char.add(np.char.add(np.char.add(pos1.astype(str), "\t"), np.char.add(pos2.astype(str), "\t")),

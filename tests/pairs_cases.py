@@ -1,11 +1,13 @@
 """Lines and files of read-pair text (HiC-Pro `allValidPairs`) for tests/test_pairs_host.py and tests/test_gpu_pairs.py: every
 shape of the fast and the slow form, malformed lines, the rule written out once more with str methods and Python's own int()
-and round(), and the generator of the mixed file."""
+and round(), the generator of the mixed file, and the dense files whose 4 KiB tiles hold more line starts than one round of the
+parse kernel hands out."""
 import random
 
 import numpy as np
 
 LINE_MAX, NAME_MAX = 256, 15
+TILE, ROUND, TILE_KEYS = 4096, 256, 416      # cgcn_pairs.hip: PAIRS_TILE bytes per workgroup, PAIRS_THREADS line starts per round
 CHROMS = ("chr1", "chr2", "chr10", "chrX", "c", "chr_fifteen_byt")          # 1 and 15 bytes among them
 OTHER_NAMES = ("chrM", "chrUn_gl000220", "chr", "chr11", "CHR1", "chr1 ")     # same-chromosome pairs outside the table
 # positions the fast form takes, and spellings int() takes that it does not
@@ -163,3 +165,51 @@ def arrays(pairs):
     """[(p1, p2), ...] -> two int32 vectors"""
     a = np.array(pairs, dtype=np.int64).reshape(-1, 2)
     return a[:, 0].astype(np.int32), a[:, 1].astype(np.int32)
+
+
+# ----------------------------------------------------------------------------------------------
+# dense files: lines so short that a tile's line starts need several rounds of 256
+# ----------------------------------------------------------------------------------------------
+DENSE_RULE = dict(chroms=["c"], min_diff=-1, resolution_bp=8)     # what dense_kept is parsed with: every line is kept
+BAD_SHORT = b"\tc\t1"                                               # three fields: malformed
+
+
+def tile_ranks(data: bytes):
+    """for every line start of `data` (byte 0 and every byte behind an LF), in line order: (its 4 KiB tile, its place among
+    the line starts of that tile, 0-based).  Line k of the file is entry k."""
+    buf = np.frombuffer(data, np.uint8)
+    starts = np.concatenate([np.zeros(1, np.int64), np.flatnonzero(buf == 10) + 1])
+    starts = starts[starts < buf.size]
+    tile = starts // TILE
+    return tile, np.arange(starts.size) - np.searchsorted(tile, tile)
+
+
+def dense_kept(n=60000, seed=1):
+    """n lines of the shortest kept form, `TAB c TAB d TAB TAB c TAB d LF` = 10 bytes (DENSE_RULE keeps every one of them):
+    4096 = 6 mod 10, so the tiles start at five phases of a line and every fifth tile starts on a line start and holds 410"""
+    rng = random.Random(seed)
+    return [b"\tc\t%d\t\tc\t%d" % (rng.randrange(10), rng.randrange(10)) for _ in range(n)]
+
+
+def dense_mixed(n=40000, seed=2, slow_every=211):
+    """n short lines of every class at the default min_diff with chroms=["c"]: kept, too close, inter-chromosomal, outside the
+    table, empty; every `slow_every`-th line is a slow one (a blank inside int()), kept and too close in turn"""
+    rng = random.Random(seed)
+    out = []
+    for k in range(n):
+        if k % slow_every == slow_every - 1:
+            out.append(b"\tc\t 1\t\tc\t%d" % (7000 + k if (k // slow_every) % 2 else 2))
+            continue
+        u = rng.random()
+        if u < 0.45:
+            a, b = rng.randrange(10), 1000 * rng.randint(1, 99) + rng.randrange(10)
+            out.append(b"\tc\t%d\t\tc\t%d" % ((a, b) if rng.random() < 0.5 else (b, a)))
+        elif u < 0.6:
+            out.append(b"\tc\t%d\t\tc\t%d" % (rng.randrange(10), rng.randrange(10)))
+        elif u < 0.75:
+            out.append(b"\tc\t1\t\td\t2")
+        elif u < 0.85:
+            out.append(b"\td\t1\t\td\t2")
+        else:
+            out.append(b"")
+    return out

@@ -10,7 +10,7 @@ import torch
 
 from chromegcn_amd import hic, synth
 
-from hic_text_cases import FAST_F3, SLOW_F3, assert_parses_like_python, juicer_text, mixed_lines
+from hic_text_cases import FAST_F3, SLOW_F3, assert_parses_like_python, dense_lines, juicer_text, mixed_lines
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -107,6 +107,27 @@ def test_every_listed_shape_against_python_itself():
     p1, p2, cnt = bits(c)
     assert_parses_like_python(lines, data, got=(p1, p2, cnt.view(np.float64), c.text_info["slow_lines"]))
     assert c.text_info["slow_lines"].tolist() == list(range(len(FAST_F3), len(lines)))
+
+
+def test_a_file_of_six_byte_lines_has_two_or_three_line_starts_in_every_lane():
+    """k_text_starts reads 16 bytes per lane: in a file of 6-byte lines every lane of every tile holds two or three line
+    starts and a tile 682 or 683, five times what the Juicer and the mixed files reach.  Against Python's own int() and
+    float(), with room for every slow line and with a flag list that overflows."""
+    lines = dense_lines()
+    data = b"\n".join(lines) + b"\n"
+    starts = np.concatenate([[0], np.flatnonzero(np.frombuffer(data, np.uint8) == 10)[:-1] + 1])
+    per_lane, per_tile = np.bincount(starts // 16)[:-1], np.bincount(starts // 4096)[:-1]
+    assert starts.size == len(lines) == 100000 and per_lane.min() == 2 and per_lane.max() == 3
+    assert per_tile.min() == 682 and per_tile.max() == 683
+    n_slow = sum(ln == b"1\t2\t1e23" for ln in lines)
+    assert n_slow == 100
+    for cap, calls in ((1 << 16, 1), (n_slow - 1, 2), (7, 2)):
+        c = hic.contacts_from_text(data, device=DEV, flag_capacity=cap)
+        assert c.M == len(lines) and c.text_info["parse_calls"] == calls, cap
+        p1, p2, cnt = bits(c)
+        slow = assert_parses_like_python(lines, data, got=(p1, p2, cnt.view(np.float64), c.text_info["slow_lines"]))
+        assert slow.tolist() == list(range(999, 100000, 1000))
+    assert_same_records(c, hic.parse_contacts_text_host(data), "dense")
 
 
 def test_empty_file_single_line_and_crlf(mixed):

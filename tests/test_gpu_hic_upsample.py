@@ -3,6 +3,8 @@ csrc/cgcn_hic.hip) against (a) the numpy restatement build_hic_graph_host(window
 tests/test_hic_upsample_host.py ties to the reference's step 7, and (b) the device path for records at the windows' own
 resolution, run on the expanded file written out (expand_contacts_host).  Every comparison is exact: rowptr, col[:nnz], nnz
 and the survivor count S."""
+import math
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -85,6 +87,59 @@ def test_full_size_equals_the_merged_device_path_on_the_expanded_file(chrom):
                 assert_is_host_build(got, _args(r, norm, edges), (chrom, norm, edges))
                 host_checked = True
     assert host_checked == (chrom == "chr21")
+
+
+def _records_2kb(target, seed=5, n_bins=124626):
+    """more than `target` records on chr1's 2 kb grid, made as synth.raw_contacts makes its background (the truncated 1/k law
+    of distances, each ordered pair once, sorted by (pos1, pos2), the diagonal present, counts that fall with distance, a norm
+    vector with NaN and zeros), and 50 000 windows of 1 kb"""
+    rng = np.random.RandomState(seed)
+    k = int(1.12 * target)
+    dist = np.clip(np.floor(np.exp(rng.random_sample(k) * math.log(n_bins - 1))).astype(np.int64) - 1, 0, n_bins - 1)
+    a = (rng.random_sample(k) * (n_bins - dist)).astype(np.int64)
+    key = np.unique(a * n_bins + a + dist)
+    bin1, bin2 = key // n_bins, key % n_bins
+    count = 1.0 + rng.poisson(40.0 / (1.0 + (bin2 - bin1)) ** 0.8)
+    norm = 0.5 + rng.random_sample(n_bins)
+    norm[rng.random_sample(n_bins) < 0.02] = np.nan
+    norm[rng.random_sample(n_bins) < 0.01] = 0.0
+    ws = np.sort(rng.choice(2 * n_bins, 50000, replace=False)).astype(np.int32) * 1000
+    return {"pos1": (bin1 * 2000).astype(np.int32), "pos2": (bin2 * 2000).astype(np.int32), "count": count.astype(np.float64),
+            "norm": norm, "window_start": ws, "resolution_bp": 2000, "window_bp": 1000}
+
+
+@pytest.mark.timeout(600)
+def test_more_records_than_one_sweep_of_the_persistent_filter():
+    """k_hic_filter_up's waves stride over the 512-record wave tiles: a grid of 2 x CUs workgroups of 16 waves visits
+    2 x CUs x 16 tiles in its first trip, so records from 2 x CUs x 16 x 512 on are read in the second one (about 4.4 M
+    records of 2 kb for 1 kb windows, up = 2, at 256 CUs).  Exactly the host restatement, and exactly the merged device path
+    on the expanded file; on the bitmap route (every window on the 1 kb grid) and on the search route (one window off it)."""
+    sweep_tiles = 2 * torch.cuda.get_device_properties(torch.device(DEV)).multi_processor_count * 16
+    r = _records_2kb(int(1.05 * sweep_tiles * 512))
+    M = r["pos1"].size
+    tiles = -(-M // 512)
+    assert M > sweep_tiles * 512 and tiles - 1 > sweep_tiles, (M, sweep_tiles)
+    compact = hic.HicContacts(r["pos1"], r["pos2"], r["count"], DEV)
+    written_out = hic.HicContacts(*hic.expand_contacts_host(r["pos1"], r["pos2"], r["count"], 2000, 1000), DEV)
+    off_grid = r["window_start"].copy()
+    off_grid[1000] += 500
+    for ws in (r["window_start"], off_grid):
+        # survivors of every record from the positions: (children of pos1 that are windows) x (of pos2), less the pairs (w, w)
+        c1 = np.isin(r["pos1"], ws).astype(np.int64) + np.isin(r["pos1"] + 1000, ws)
+        c2 = np.isin(r["pos2"], ws).astype(np.int64) + np.isin(r["pos2"] + 1000, ws)
+        surv = c1 * c2 - (r["pos1"] == r["pos2"]) * c1
+        tile = np.arange(M) // 512
+        in_last, in_second_trip = surv[tile == tiles - 1].sum(), surv[(tile >= sweep_tiles) & (tile < tiles - 1)].sum()
+        print("M %d, %d wave tiles, %d in a sweep; survivors: %d, %d of them in the second trip before the last tile, %d in the last"
+              % (M, tiles, sweep_tiles, surv.sum(), in_second_trip, in_last))
+        assert in_last > 0 and in_second_trip > 1000 and surv[tile < sweep_tiles].sum() > 1000
+        for norm in (False, True):
+            args = dict(_args(r, norm, 500000), window_start=ws)
+            got = device_csr(args, compact)
+            assert got[3] == surv.sum() and got[2] > 400000
+            assert_is_host_build(got, args, ("beyond one sweep", ws is off_grid, norm))
+            want = device_csr({k: v for k, v in args.items() if k != "window_bp"}, written_out)
+            assert got[2:] == want[2:] and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (ws is off_grid, norm)
 
 
 def _buffers(n, K, fill=-7):

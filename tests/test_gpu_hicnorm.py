@@ -4,6 +4,7 @@ compared exactly; sums of integer counts bit for bit; fractional sums and Knight
 number format and from the host restatement alone (each test's docstring says which).  Every figure is printed before it is
 asserted."""
 import functools
+import math
 
 import numpy as np
 import pytest
@@ -222,6 +223,217 @@ def test_cap_excluded_rows_and_determinism():
         a, ia = hicnorm.kr_balance_device(m, tol=1e-10)
         b, ib = hicnorm.kr_balance_device(m, tol=1e-10)
         assert torch.equal(a.view(torch.int64), b.view(torch.int64)) and ia == ib
+
+
+@pytest.mark.parametrize("tol", [1e-6, 1e-10])
+@pytest.mark.parametrize("name", sorted(set(HC.UPPER_CLIP + HC.LOWER_CLIP)))
+def test_kr_clips_the_steps_the_host_clips(name, tol):
+    """OP_CLIP with either flag inside a whole run, the two step-length minima of OP_Y read, an inner loop left without a
+    flip of the parity: the device reports the host's (lower, upper) pair -- tests/test_hicnorm_host.py shows that no run
+    comes within 1e-6 of another branch -- and the run meets test_kr_residual_recomputed_on_the_host's criterion"""
+    x, info = device_kr(name, tol)
+    host = HC.host_kr(name, tol)
+    worst, k_row = HC.kr_residual(HC.host_matrix(name), x)
+    print("%s tol %g: clips %s (host %s), device residual %.3g recomputed max %.3g, %d products (host %d)"
+          % (name, tol, info["clips"], host[1]["clips"], info["residual"], worst, info["mvp"], host[1]["mvp"]))
+    assert info["clips"] == host[1]["clips"]
+    assert (info["clips"][1] >= 1) == (name in HC.UPPER_CLIP) and (info["clips"][0] >= 1) == (name in HC.LOWER_CLIP)
+    assert info["converged"] is True and info["residual"] <= tol and np.array_equal(np.isnan(x), np.isnan(host[0]))
+    assert worst <= tol + (k_row + 2) * 2.0 ** -52
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("tol", [1e-6, 1e-10])
+@pytest.mark.parametrize("name", HC.KR_LARGE)
+def test_kr_beyond_one_trip_of_the_vector_step(name, tol):
+    """70 001 bins: 274 partials, k_hn_finish folds them in two trips; 262 401 bins: 1026 tiles for a grid of 1024, k_hn_vec
+    strides.  The criterion of test_kr_residual_recomputed_on_the_host."""
+    c = HC.case(name)
+    blocks = -(-c["n_bins"] // 256)
+    assert blocks > 256 and (blocks > 1024) == (name == "n262401")
+    x, info = device_kr(name, tol)
+    host = HC.host_kr(name, tol)
+    worst, k_row = HC.kr_residual(HC.host_matrix(name), x)
+    print("%s tol %g: device residual %.3g recomputed max %.3g, %d products (host %d), clips %s (host %s)"
+          % (name, tol, info["residual"], worst, info["mvp"], host[1]["mvp"], info["clips"], host[1]["clips"]))
+    assert info["converged"] is True and info["residual"] <= tol
+    assert np.array_equal(np.isnan(x), np.isnan(host[0])) and info["kept"] == host[1]["kept"] == c["n_bins"] - c["empty"].size
+    assert worst <= tol + (k_row + 2) * 2.0 ** -52
+    assert info["clips"] == host[1]["clips"] and (info["clips"][1] >= 1) == (name in HC.UPPER_CLIP)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("name", ["n70001", "n262401"])
+def test_vc_and_row_nnz_beyond_65536_bins(name):
+    c, a = HC.case(name), HC.host_matrix(name)
+    vc_host, nnz_host = hicnorm._row_stats_host(a)
+    m = device_matrix(name)
+    assert np.array_equal(m.row_nnz.cpu().numpy(), nnz_host)
+    vc = contacts(name).norm_vector("VC", c["res"], c["n_bins"]).cpu().numpy()
+    assert np.array_equal(np.flatnonzero(np.isnan(vc)), c["empty"]) and c["empty"].size > 30
+    assert same_bits(vc[~np.isnan(vc)], vc_host[vc_host > 0])                    # integer counts: exact in any order
+
+
+# ----------------------------------------------------------------------------------------------
+# cgcn_hicnorm_kr_step, one operation at a time
+# ----------------------------------------------------------------------------------------------
+STEP_SIZES = [1, 31, 256, 257, 65536, 65537, 262144, 262145, 300001]
+REC_SUMS = {(HC.OP_RES, 0): ("rk", "rk"), (HC.OP_RES, 8): ("rk", "rk"), (HC.OP_FIRST, 0): ("rk", "z"), (HC.OP_W, 2): ("p", "w"),
+            (HC.OP_Y, 7): ("rk'", "z'")}     # (op, slot): the two vectors whose product the slot sums; ' = the other parity
+
+
+def _random_state(n, seed):
+    """a state of seeded vectors and scalars: x, y, v away from 0, w so that x w and x y w stay below 1.7, a mask with 15 %
+    zeros, alpha = 0.1, every other scalar its own value (a slot read in place of another one shows)"""
+    rng = np.random.default_rng(seed)
+    vec = {"m": (rng.random(n) < 0.85).astype(np.float64), "x": rng.uniform(0.5, 2.0, n), "v": rng.uniform(0.5, 2.0, n),
+           "p": rng.standard_normal(n), "w": rng.uniform(0.1, 0.4, n), "y0": rng.uniform(0.5, 2.0, n), "y1": rng.uniform(0.5, 2.0, n),
+           "rk0": 0.3 * rng.standard_normal(n), "rk1": 0.3 * rng.standard_normal(n), "z0": rng.standard_normal(n),
+           "z1": rng.standard_normal(n)}
+    rec = np.zeros(32)
+    rec[:12] = [1.3, 0.7, 2.1, 0.4, 2.6, 0.61, 0.23, 0.9, 1.7, 0.1, 5.0, 6.0]
+    rec[12:] = 100.0 + np.arange(20)                                  # the slots no step writes
+    return vec, rec
+
+
+def _trip_positions(n):
+    """four rows: the first, the last (alone in a second trip at n = 65 537 and 262 145), one that only the second trip of
+    k_hn_vec's grid stride reaches (rows from 262 144) where there is one, and one whose partial only the second trip of
+    k_hn_finish's fold reaches (partials from 256: rows from 65 536); without such rows, two in the middle"""
+    if n < 31:
+        return None
+    fold = 65536 + 1000 if n > 65536 + 1001 else n // 2 + 1
+    stride = 262144 + (n - 1 - 262144) // 2 if n > 262144 + 1 else 65536 + (n - 1 - 65536) // 2 if n > 65536 + 1 else n // 2
+    assert len({0, n - 1, stride, fold}) == 4
+    return [0, n - 1, stride, fold]
+
+
+def _planted_y_state(n, seed, variant, c):
+    """the state of an OP_Y step whose four extremes are each decided by one known row.  The other kept rows have
+    y in (0.5, 2) and alpha p in (-0.2, 0.3): ynew in (0.3, 2.3), step lengths to the lower bound above 2, none to the upper
+    one.  Rows outside the mask hold y = 0.5, alpha p = -50 or 50 and must not count.  variant 2: alpha p >= 0 on every kept
+    row and no ynew above 3: both step lengths stay +inf."""
+    vec, rec = _random_state(n, seed)
+    rng = np.random.default_rng(seed + 1)
+    alpha, y = rec[9], "y%d" % c
+    ap = rng.uniform(-0.2, 0.3, n) if variant < 2 else rng.uniform(0.0, 0.3, n)
+    off = vec["m"] == 0.0
+    ap[off] = np.where(rng.random(int(off.sum())) < 0.5, -50.0, 50.0)
+    vec[y][off] = 0.5
+    pos = _trip_positions(n)
+    want = {}
+    if pos is not None and variant < 2:
+        i_min, i_max, i_lo, i_up = pos if variant == 0 else (pos[2], pos[3], pos[1], pos[0])
+        vec["m"][[i_min, i_max, i_lo, i_up]] = 1.0
+        vec[y][[i_min, i_max, i_lo, i_up]] = [0.5, 2.0, 0.2, 2.9]
+        ap[[i_min, i_max, i_lo, i_up]] = [-0.45, 2.5, -0.13, 0.5]     # ynew 0.05, 4.5, 0.07, 3.4; lengths 0.889, 0.4, 0.769, 0.2
+        want = {3: i_min, 4: i_max, 5: i_lo, 6: i_up}
+    vec["p"] = ap / alpha
+    return vec, rec, want
+
+
+def _pack(n, vec, rec):
+    from chromegcn_amd import _lib
+    nbytes = _lib.query("cgcn_hicnorm_kr_state_bytes", n=n)
+    ns = (n + 31) & ~31
+    st = np.zeros(nbytes // 8)
+    st[:32] = rec
+    for k, name in enumerate(HC.KR_VECTORS):
+        st[hicnorm._HDR + k * ns:hicnorm._HDR + k * ns + n] = vec[name]
+    return st, nbytes, ns
+
+
+def _check_step(n, op, flag, c, vec, rec, vc, nnz, worst):
+    from chromegcn_amd import _lib
+    st, nbytes, ns = _pack(n, vec, rec)
+    first = torch.from_numpy(st).to(DEV)
+    second = first.clone()
+    for state in (first, second):
+        _lib.call("cgcn_hicnorm_kr_step", n=n, op=op, flag=flag, parity=c, vc=vc[1], row_nnz=nnz[1], state=state, state_bytes=nbytes)
+    assert torch.equal(first.view(torch.int64), second.view(torch.int64)), (op, flag, c, "two calls, two results")
+    got = first.cpu().numpy()
+    gvec = {name: got[hicnorm._HDR + k * ns:hicnorm._HDR + k * ns + n] for k, name in enumerate(HC.KR_VECTORS)}
+    pad = np.concatenate([got[hicnorm._HDR + k * ns + n:hicnorm._HDR + (k + 1) * ns] for k in range(len(HC.KR_VECTORS))])
+    assert not pad.any(), (op, flag, c, "a write behind a vector's n rows")
+    out, slots = HC.kr_step_host(op, flag, c, vec, rec, vc[0], nnz[0])
+    what = (n, op, flag, c)
+    for name in HC.KR_VECTORS:
+        if name not in out:
+            assert same_bits(gvec[name], vec[name]), (what, name, "written, and the step does not own it")
+            continue
+        val, mag = out[name]
+        err, bound = np.abs(gvec[name] - val), 2.0 ** -52 * mag
+        quotient = op == HC.OP_Y and name == "z%d" % (c ^ 1)     # held to the device's own new rk below, bit for bit
+        assert quotient or np.all(err <= bound), (what, name, float(err.max()))
+        k = ("quotient" if quotient else "vector", op)
+        worst[k] = max(worst.get(k, 0.0), float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0)
+    other = {"rk'": gvec["rk%d" % (c ^ 1)], "z'": gvec["z%d" % (c ^ 1)], "rk": gvec["rk%d" % c], "z": gvec["z%d" % c],
+             "p": gvec["p"], "w": gvec["w"]}
+    keep = vec["m"] != 0.0
+    if op == HC.OP_Y:       # Z of the new parity is one IEEE division of the device's own new rk
+        assert same_bits(other["z'"], np.where(keep, other["rk'"] / vec["v"], 0.0)), what
+    for slot in range(32):
+        if slot not in slots:
+            assert got[slot] == rec[slot], (what, slot, "written, and the step does not own it")
+            continue
+        val, mag = slots[slot]
+        if (op, slot) in REC_SUMS:          # a sum: of the products of the vectors the device itself holds
+            a, b = REC_SUMS[(op, slot)]
+            terms = other[a] * other[b]
+            exact, size = math.fsum(terms.tolist()), math.fsum(np.abs(terms).tolist())
+            err = abs(got[slot] - exact)
+            k = ("sum", op)
+            worst[k] = max(worst.get(k, 0.0), err / ((n + 1) * U * size) if size else 0.0)
+            assert err <= (n + 1) * U * size, (what, slot, got[slot], exact)
+        elif op == HC.OP_W and slot == 9:   # alpha: one IEEE division by the device's own p . w
+            assert got[9] == (rec[7] if flag else rec[0]) / got[2], what
+        elif op == HC.OP_Y:                 # a minimum or a maximum
+            assert got[slot] == val if np.isinf(val) else abs(got[slot] - val) <= 4 * U * abs(val), (what, slot, got[slot], val)
+            if not np.isinf(val):
+                worst[("extreme", op)] = max(worst.get(("extreme", op), 0.0), abs(got[slot] / val - 1.0) / (4 * U))
+        else:                               # a count or a copy
+            assert got[slot] == val, (what, slot, got[slot], val)
+    return slots
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("n", STEP_SIZES)
+def test_kr_step_one_operation_at_a_time(n):
+    """Every operation of cgcn_hicnorm_kr_step (OP_MASK, OP_RES and OP_W and OP_CLIP with either flag, OP_FIRST, OP_DIR, OP_Y)
+    at either parity, once from a seeded state, every vector and every record slot against HC.kr_step_host -- the float64
+    numpy restatement that tests/test_hicnorm_host.py ties to _kr_run_host's listing.  n = 65 537 gives 257 partials
+    (k_hn_finish's second trip), n > 262 144 more tiles than the grid (k_hn_vec's stride).
+    Bounds, from the number format (the compiler may contract a multiply-add):  a vector element within 2^-52 x the sum of the
+    magnitudes of its terms; a quotient (Z = rk / v) bit for bit from the device's own operands -- OP_Y's new Z divides the new rk,
+    whose contracted multiply-add may differ from the restatement's by one rounding that the division then carries, up to
+    2.5 x 2^-52 (|rk| + |alpha w|) / |v| against the restatement's own Z (observed: up to 1.95 of 2^-52 x those terms, at n = 262 145): its
+    figure is printed, the assertion is the exact one;  a sum
+    within (n + 1) 2^-53 x the sum of the magnitudes of its terms -- the terms being the products of the vectors the device
+    holds after the step, which are the ones it added (against the restatement's own vectors the comparison would also
+    carry the element errors above);  a minimum or maximum within 4 x 2^-53 relative;  counts, copied scalars, +inf and
+    everything the step does not own: bit for bit.  The same call on the same state twice: the same bits."""
+    rng = np.random.default_rng(n)
+    vc_h = np.where(rng.random(n) < 0.8, rng.uniform(1.0, 50.0, n), 0.0)
+    nnz_h = rng.integers(0, 5, n).astype(np.int32)
+    vc, nnz = (vc_h, torch.from_numpy(vc_h).to(DEV)), (nnz_h, torch.from_numpy(nnz_h).to(DEV))
+    worst = {}
+    for c in (0, 1):
+        vec, rec = _random_state(n, 1000 + n + c)
+        for op, flag in HC.KR_STEPS:
+            if op != HC.OP_Y:
+                slots = _check_step(n, op, flag, c, vec, rec, vc, nnz, worst)
+                if op == HC.OP_MASK and n >= 31:
+                    assert 0 < slots[10][0] < slots[11][0] < n                               # kept rows, non-empty rows
+        for variant in (0, 1, 2):
+            vec_y, rec_y, want = _planted_y_state(n, 2000 + n + c, variant, c)
+            slots = _check_step(n, HC.OP_Y, 0, c, vec_y, rec_y, vc, nnz, worst)
+            if variant == 2:
+                assert np.isinf(slots[5][0]) and np.isinf(slots[6][0]) and slots[4][0] < 3.0
+            elif want:       # the planted rows decide: the restatement's extremes are theirs
+                y, ap = vec_y["y%d" % c], rec_y[9] * vec_y["p"]
+                assert slots[3][0] == (y + ap)[want[3]] < 0.1 and slots[4][0] == (y + ap)[want[4]] > 3.0
+                assert slots[5][0] == ((0.1 - y) / ap)[want[5]] and slots[6][0] == ((3.0 - y) / ap)[want[6]]
+    print("kr_step n=%d: worst error / bound %s" % (n, ", ".join("%s op %d: %.3g" % (k[0], k[1], v) for k, v in sorted(worst.items()))))
 
 
 def test_string_norms_end_to_end(tmp_path):

@@ -182,6 +182,64 @@ def test_flag_list_that_overflows_is_fetched_by_a_second_call(mixed):
     assert_same(rp, want, "capacity 0, several chunks")
 
 
+def test_tiles_of_410_kept_lines_take_two_rounds():
+    """every tile of dense_kept holds 409 or 410 line starts, all kept: the second round of k_pairs_starts<true> ranks its
+    kept lines behind the 256 of the first, k_pairs_compact copies more than 256 keys of a tile"""
+    data = PC.join_lines(PC.dense_kept())
+    tile, rank = PC.tile_ranks(data)
+    assert np.bincount(tile).max() == 410 and rank.max() == 409 > PC.ROUND
+    want = bin_read_pairs_host(data, **PC.DENSE_RULE)
+    assert want.info["kept"] == want.info["lines"] == 60000
+    rp = ReadPairs.from_text(data, device=DEV, **PC.DENSE_RULE)
+    assert rp.info["parse_calls"] == 1
+    assert_same(rp, want, "dense kept")
+    for chunk in (4096 * 5, 4099):                                   # chunks of 2048 and of 409 whole lines: each starts on a line start
+        again = ReadPairs.from_text(data, device=DEV, chunk_bytes=chunk, **PC.DENSE_RULE)
+        assert torch.equal(again.keys, rp.keys) and pairs.same_info(again.info, want.info), chunk
+
+
+@pytest.mark.parametrize("data,starts", [(b"\n" * 20000, 4096), (b"\r\n" * 10000, 2048)], ids=["lf", "crlf"])
+def test_a_text_of_line_ends_alone(data, starts):
+    """4096 (2048) line starts in a tile, every line empty: 16 (8) rounds"""
+    assert np.bincount(PC.tile_ranks(data)[0]).max() == starts
+    want = bin_read_pairs_host(data, chroms=["c"])
+    rp = ReadPairs.from_text(data, chroms=["c"], device=DEV)
+    assert rp.info["lines"] == rp.info["empty"] == data.count(b"\n") and rp.keys.numel() == 0 and rp.info["slow"] == 0
+    assert_same(rp, want, starts)
+
+
+def test_dense_lines_of_every_class_with_slow_lines_in_late_rounds():
+    lines = PC.dense_mixed()
+    data = PC.join_lines(lines)
+    tile, rank = PC.tile_ranks(data)
+    want = bin_read_pairs_host(data, chroms=["c"])
+    late = [k for k in want.info["slow_lines"].tolist() if rank[k] >= PC.ROUND]
+    assert np.bincount(tile).min() > PC.ROUND and len(late) >= 10 and want.info["slow"] > 100
+    rp = ReadPairs.from_text(data, chroms=["c"], device=DEV)
+    assert rp.info["parse_calls"] == 1
+    assert_same(rp, want, "default capacity")
+    for kw in (dict(flag_capacity=4), dict(flag_capacity=0), dict(chunk_bytes=4099)):
+        again = ReadPairs.from_text(data, chroms=["c"], device=DEV, **kw)
+        assert again.keys.dtype == torch.int64 and torch.equal(again.keys, rp.keys), kw          # the same bits in the same order
+        assert_same(again, want, kw)
+    assert ReadPairs.from_text(data, chroms=["c"], device=DEV, flag_capacity=4).info["parse_calls"] == 2
+
+
+def test_a_malformed_line_in_a_late_round_raises_the_hosts_message():
+    good = PC.dense_kept(6000)
+    for k in (300, 2048 + 350):
+        data = PC.join_lines(good[:k] + [PC.BAD_SHORT] + good[k:] + [b"also\tbad"])
+        tile, rank = PC.tile_ranks(data)
+        assert rank[k] >= 300
+        with pytest.raises(ValueError) as host:
+            bin_read_pairs_host(data, **PC.DENSE_RULE)
+        assert str(host.value).startswith("read pairs: line %d is not" % (k + 1))
+        for cap in (1 << 16, 1):
+            with pytest.raises(ValueError) as dev:
+                ReadPairs.from_text(data, device=DEV, flag_capacity=cap, **PC.DENSE_RULE)
+            assert str(dev.value) == str(host.value), (k, cap)
+
+
 def test_two_runs_are_bitwise_equal(mixed, mixed_dev):
     again = ReadPairs.from_text(mixed[1], chroms=PC.CHROMS, device=DEV)
     assert torch.equal(again.keys, mixed_dev.keys) and pairs.same_info(again.info, mixed_dev.info)

@@ -74,7 +74,7 @@ def fixture(golden):
     return {"X": f["X"], "Y0": f["Y0"], "P": P, "kl_bound": float(f["kl_bound"])}
 
 
-@pytest.mark.parametrize("d", [4, 128, 256])
+@pytest.mark.parametrize("d", [4, 36, 100, 128, 256])     # 36 and 100: a partly filled slice of 32 features behind a full one
 @pytest.mark.parametrize("n", NS)
 def test_sqdist(n, d):
     x = _points(n, d, 7 * n + d)
@@ -131,7 +131,7 @@ def test_affinities_and_symmetrisation(n, perplexity):
 
 @pytest.mark.parametrize("exaggeration", [1.0, 12.0])
 @pytest.mark.parametrize("form", ["start", "unit", "apart"])
-@pytest.mark.parametrize("n", [2, 3, 65, 257, N_LARGE])
+@pytest.mark.parametrize("n", [2, 3, 65, 257, 700, N_LARGE])
 def test_gradient_and_kl(n, form, exaggeration):
     P_host, y = _host_P(n), _embedding(n, form)
     kl_ref, g_ref, Z_ref = tsne.kl_gradient_host(P_host, y, exaggeration)
@@ -160,6 +160,43 @@ def test_gradient_and_kl(n, form, exaggeration):
     again = torch.empty_like(Y)
     tsne.kl_gradient(P, Y, exaggeration, again, True, ws)
     assert torch.equal(again, grad)
+    if n > 512:
+        _check_update_from_a_random_state(n, Y, grad, rec, ws)
+
+
+def _check_update_from_a_random_state(n, Y, grad, rec, ws):
+    """k_tsne_update is one workgroup of 1024 threads that strides over the 2 n values: at 2 n > 1024 there is a second trip.
+    From a seeded non-zero `update` and gains in [0.01, 2] (both branches of the gain rule, and its floor), Y, update and
+    gains after one step against the rule in float32 numpy on the device's own gradient: gains within one ulp; update within
+    2^-23 (|momentum u| + |lr g gain|) -- one rounding of each product and one of the difference, or fewer when the compiler
+    contracts them --; Y within that plus 2^-23 |Y|; the gradient-norm record as above."""
+    assert 2 * n > 1024
+    rng = np.random.RandomState(n + 1)
+    f32 = np.float32
+    g, y0 = grad.cpu().numpy(), Y.cpu().numpy()
+    u0 = (np.abs(g).max() * 50.0 * rng.standard_normal((n, 2))).astype(f32)     # the size of a step: lr x gradient
+    gain0 = rng.uniform(0.01, 2.0, (n, 2)).astype(f32)
+    gain0[rng.random_sample((n, 2)) < 0.05] = f32(0.01)                          # 0.8 x 0.01 is below the floor
+    momentum, lr = f32(0.8), f32(200.0)
+    inc = u0 * g < 0
+    assert 0.2 < inc.mean() < 0.8 and inc[:512].any() and inc[512:].any() and (~inc[512:]).any()   # row 512 on: the second trip
+    gain = np.maximum(np.where(inc, gain0 + f32(0.2), gain0 * f32(0.8)), f32(0.01)).astype(f32)
+    assert (gain == f32(0.01)).any() and gain.dtype == f32
+    gg = g * gain
+    u = momentum * u0 - lr * gg
+    y = y0 + u
+    assert u.dtype == f32 and y.dtype == f32
+    Yd, ud, gd = Y.clone(), torch.from_numpy(u0).to(DEV), torch.from_numpy(gain0).to(DEV)
+    tsne.update_step(Yd, ud, gd, grad, float(momentum), float(lr), False, rec, ws)
+    got_y, got_u, got_gain = Yd.cpu().numpy(), ud.cpu().numpy(), gd.cpu().numpy()
+    e = 2.0 ** -23
+    size_u = np.abs(momentum * u0).astype(np.float64) + np.abs(lr * gg)
+    err_gain = np.abs(got_gain - gain) / np.spacing(gain)
+    err_u, err_y = np.abs(got_u.astype(np.float64) - u) / (e * size_u), np.abs(got_y.astype(np.float64) - y) / (e * (size_u + np.abs(y0)))
+    print("update n=%d: gains off by %.3g ulp; update %.3g, Y %.3g of their bounds; rows of the second trip: update %.3g, Y %.3g"
+          % (n, err_gain.max(), err_u.max(), err_y.max(), err_u[512:].max(), err_y[512:].max()))
+    assert err_gain.max() <= 1 and err_u.max() <= 1 and err_y.max() <= 1
+    np.testing.assert_allclose(rec[1].item(), np.linalg.norm((g.astype(np.float64) * gain.astype(np.float64)).ravel()), rtol=1e-6)
 
 
 def test_ten_updates_through_the_c_abi(fixture):

@@ -65,6 +65,48 @@ def test_kr_meets_its_residual(name, tol):
     assert info["kept"] == c["n_bins"] - c["empty"].size and info["excluded"] == 0 and info["host_syncs"] == 0
 
 
+@pytest.mark.parametrize("tol", [1e-6, 1e-10])
+@pytest.mark.parametrize("name", HC.KR_CASES + ("n70001_tiny",))
+def test_clips_entry_agrees_with_an_independent_count(name, tol):
+    """info["clips"] against the listing written out once more (HC.kr_clip_count); the scaled cases take the upper clip, the
+    wide ones the lower one, no other case takes either; and no run comes within 1e-6 of a branch it did not take, so the
+    device's roundings cannot send it down another one"""
+    x, info = HC.host_kr(name, tol)
+    clips, margin, mvp = HC.kr_clip_count(HC.host_matrix(name), tol)
+    print("%s tol %g: clips %s, margin %.3g, %d products" % (name, tol, clips, margin, mvp))
+    assert info["clips"] == clips and info["mvp"] == mvp and info["converged"]
+    assert (clips[1] >= 1) == (name in HC.UPPER_CLIP) and (clips[0] >= 1) == (name in HC.LOWER_CLIP)
+    if name.endswith("_tiny"):
+        assert clips[1] >= 5
+    assert margin > 1e-6
+
+
+@pytest.mark.parametrize("name", ["n63_leafy", "n257", "fullrow", "n257_tiny", "n65_wide", "n257_wide"])
+def test_the_step_restatement_in_the_drivers_order_is_the_listing(name):
+    """HC.kr_step_host, which tests/test_gpu_hicnorm.py holds every operation of cgcn_hicnorm_kr_step to, run in
+    _kr_run_device's order with scipy's product: the listing's x within a few roundings, its products and its clips"""
+    mrn = 3 if name == "n63_leafy" else 1
+    xh, ih = kr_balance_host(HC.host_matrix(name), tol=1e-10, min_row_nnz=mrn, kr_retry=False)
+    x, mvp, clips = HC.kr_run_by_steps(HC.host_matrix(name), 1e-10, min_row_nnz=mrn)
+    assert np.array_equal(np.isnan(x), np.isnan(xh)) and (mvp, clips) == (ih["mvp"], ih["clips"])
+    keep = ~np.isnan(xh)
+    assert np.abs(x[keep] / xh[keep] - 1.0).max() <= 1e-13
+
+
+@pytest.mark.parametrize("name", HC.KR_LARGE)
+def test_large_cases_need_a_second_trip_of_the_vector_step(name):
+    """70 001 bins are 274 workgroups of 256: more partials than the 256 threads that fold them; 262 401 bins are 1026: more
+    than the 1024 workgroups of the vector step's grid.  The host balances each in well under 100 products."""
+    c = HC.case(name)
+    blocks = -(-c["n_bins"] // 256)
+    assert blocks > 256 and (blocks > 1024) == (name == "n262401")
+    for tol in (1e-6, 1e-10):
+        x, info = HC.host_kr(name, tol)
+        worst, k_row = HC.kr_residual(HC.host_matrix(name), x)
+        assert info["converged"] and info["mvp"] < 100 and worst <= tol + (k_row + 2) * 2.0 ** -52, (name, tol, info)
+        assert np.array_equal(np.flatnonzero(np.isnan(x)), c["empty"])
+
+
 def test_one_and_two_bins():
     x, info = kr_balance_host(sp.csr_matrix(np.array([[4.0]])))
     assert info["converged"] and x[0] == pytest.approx(0.5, abs=1e-6)   # |4 x^2 - 1| <= tol

@@ -113,6 +113,48 @@ def test_every_malformed_kind_raises_with_the_first_lines_number():
     assert empty.info["lines"] == 0 and empty.chroms == pairs.DEFAULT_CHROMS and len(pairs.DEFAULT_CHROMS) == 23
 
 
+def test_dense_files_hold_more_line_starts_per_tile_than_one_round():
+    """what tests/test_gpu_pairs.py relies on, from the bytes alone: tiles of 410 kept lines, of 4096 and 2048 empty ones,
+    slow lines and a malformed one behind the 256th line start of their tile; and the host's parse of each file"""
+    lines = PC.dense_kept()
+    data = PC.join_lines(lines)
+    tile, rank = PC.tile_ranks(data)
+    per_tile = np.bincount(tile)
+    assert len(data) == 600000 and all(len(ln) == 9 and PC.is_fast(ln) for ln in lines)
+    assert per_tile.max() == 410 <= PC.TILE_KEYS and (per_tile == 410).sum() >= 29 and (data[4096 * 5 - 1:4096 * 5] == b"\n")
+    want, tot, slow = PC.python_rule(lines, res=8, binning="nearest", min_diff=-1, chroms=["c"])
+    hp = bin_read_pairs_host(data, **PC.DENSE_RULE)
+    assert tot["kept"] == len(lines) == hp.info["kept"] and slow == [] and hp.info["slow"] == 0     # every line start is a kept line:
+    assert per_tile.max() >= 257 and rank.max() == 409                                           # 410 kept lines in one tile
+    a, b = PC.arrays(want["c"])
+    assert np.array_equal(hp.binned("c")[0], a) and np.array_equal(hp.binned("c")[1], b) and set(a.tolist()) == {0, 8}
+    for data, starts in ((b"\n" * 20000, 4096), (b"\r\n" * 10000, 2048)):
+        tile, rank = PC.tile_ranks(data)
+        hp = bin_read_pairs_host(data, chroms=["c"])
+        assert np.bincount(tile).max() == starts and hp.info["lines"] == hp.info["empty"] == data.count(b"\n")
+        assert hp.info["kept"] == hp.info["slow"] == 0 and hp.pos1.size == 0
+    lines = PC.dense_mixed()
+    data = PC.join_lines(lines)
+    tile, rank = PC.tile_ranks(data)
+    want, tot, slow = PC.python_rule(lines, chroms=["c"])
+    hp = bin_read_pairs_host(data, chroms=["c"])
+    assert all(hp.info[k] == v for k, v in tot.items()) and hp.info["slow_lines"].tolist() == slow
+    assert min(tot[k] for k in ("empty", "kept", "inter_chrom", "other_chrom", "too_close")) > 3000
+    a, b = PC.arrays(want["c"])
+    assert np.array_equal(hp.binned("c")[0], a) and np.array_equal(hp.binned("c")[1], b)
+    late = [k for k in slow if rank[k] >= PC.ROUND]
+    kept_slow = [k for k in late if int(lines[k].split(b"\t")[5]) > 1000]
+    assert np.bincount(tile).min() > PC.ROUND and len(late) >= 10 and len(kept_slow) >= 5 and len(late) - len(kept_slow) >= 5
+    good = PC.dense_kept(6000)
+    for k in (300, 2048 + 350):                                   # tile 0, and tile 5, which starts on line 2048
+        body = good[:k] + [PC.BAD_SHORT] + good[k:]
+        data = PC.join_lines(body)
+        tile, rank = PC.tile_ranks(data)
+        assert rank[k] >= 300 and tile[k] == (0 if k == 300 else 5) and body[k] == PC.BAD_SHORT
+        with pytest.raises(ValueError, match=r"^read pairs: line %d is not " % (k + 1)):
+            bin_read_pairs_host(data, **PC.DENSE_RULE)
+
+
 def test_stage_b_is_a_counter_over_canonical_bin_pairs(golden, tmp_path):
     _, data, chroms, _ = golden
     hp = bin_read_pairs_host(data, chroms=chroms)
