@@ -11,6 +11,8 @@ from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_f
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
 from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_norm_vector_host,  # noqa: F401
                       kr_balance_host)
+from .hicdist import (distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
+                      hic_expected_vector)
 from .pairs import ReadPairs, bin_read_pairs_host, pairs_to_contacts_host  # noqa: F401
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 from .thresholds import (ThresholdCounts, best_thresholds, metrics_from_counts, threshold_counts,  # noqa: F401
@@ -27,4 +29,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "roc_curve_host", "pr_curve_host", "optimal_cutoff_host", "ThresholdCounts", "threshold_counts",
            "threshold_metrics", "metrics_from_counts", "best_thresholds", "threshold_counts_host",
            "threshold_metrics_host", "HicNormError", "contact_matrix_host", "kr_balance_host",
-           "hic_norm_vector_host", "hic_norm_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host"]
+           "hic_norm_vector_host", "hic_norm_vector", "distance_sums_host", "expected_from_sums",
+           "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host"]

@@ -91,6 +91,19 @@ _HEADER = {
     "cgcn_hic_build_up": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_bp:i n_window_bins:ll "
                                   "window_start N:i K:ll capacity:ll workspace workspace_bytes:z rowptr_out col_out nnz_out "
                                   "n_survivors"),
+    "cgcn_hic_count_dist": (_c_int, "stream M:ll pos1 pos2 window_start N:i min_distance_bp:ll workspace workspace_bytes:z "
+                                    "n_survivors"),
+    "cgcn_hic_build_dist": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_start N:i K:ll "
+                                    "capacity:ll min_distance_bp:ll expected n_expected:ll workspace workspace_bytes:z rowptr_out "
+                                    "col_out nnz_out n_survivors"),
+    "cgcn_hic_count_up_dist": (_c_int, "stream M:ll pos1 pos2 window_start N:i resolution_bp:i window_bp:i n_window_bins:ll "
+                                       "min_distance_bp:ll workspace workspace_bytes:z n_survivors"),
+    "cgcn_hic_build_up_dist": (_c_int, "stream M:ll pos1 pos2 count norm n_bins:ll resolution_bp:i window_bp:i n_window_bins:ll "
+                                       "window_start N:i K:ll capacity:ll min_distance_bp:ll expected n_expected:ll workspace "
+                                       "workspace_bytes:z rowptr_out col_out nnz_out n_survivors"),
+    "cgcn_hicdist_workspace_bytes": (_c_sz, "M:ll n_bins:ll"),
+    "cgcn_hicdist_sums": (_c_int, "stream M:ll pos1 pos2 count norm n_norm:ll resolution_bp:i n_bins:ll workspace "
+                                  "workspace_bytes:z raw_out act_out sizes"),
     "cgcn_text_workspace_bytes": (_c_sz, "n_bytes:ll"),
     "cgcn_text_count": (_c_int, "stream text n_bytes:ll workspace workspace_bytes:z n_records"),
     "cgcn_text_parse": (_c_int, "stream text n_bytes:ll M:ll pos1_out pos2_out count_out flags flag_capacity:ll flag_totals "

@@ -60,15 +60,34 @@ __device__ __forceinline__ double hic_norm_at(const double* __restrict__ norm, l
   return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
 }
 
+// Distance-aware variants (DIST = true in the filter passes below): a record takes part only if
+// |pos1 - pos2| >= min_d (in 64 bits), and its value is divided once more, by ex[d], d = |pos1 // res - pos2 // res|.
+// ex[] as nv[]: NaN, 0 and negative entries read as +inf, and so does a distance outside the vector: never out of bounds.
+__device__ __forceinline__ bool hic_gap_ok(int a, int b, long long min_d) {
+  const long long g = (long long)a - (long long)b;
+  return (g < 0 ? -g : g) >= min_d;
+}
+__device__ __forceinline__ long long hic_floor_bin(int pos, int res) {   // numpy's pos // res
+  const long long q = pos / res;
+  return (pos < 0 && q * res != pos) ? q - 1 : q;
+}
+__device__ __forceinline__ double hic_expected_at(const double* __restrict__ ex, long long n_ex, int p1, int p2, int res) {
+  const long long g = hic_floor_bin(p1, res) - hic_floor_bin(p2, res), d = g < 0 ? -g : g;
+  if (d >= n_ex) return __longlong_as_double(0x7FF0000000000000ll);
+  const double x = ex[d];
+  return x > 0.0 ? x : __longlong_as_double(0x7FF0000000000000ll);
+}
+
 // Wave w of a workgroup owns the 512 consecutive records [tile + 512 w, tile + 512 (w + 1)) and walks them in 8 steps of
 // 64 (coalesced); a survivor's place is (tile offset) + (survivors of the waves before) + (of the steps before) + (of the
 // lanes before): file order.  WRITE = false only counts the tile's survivors.
-template <bool WRITE>
-__global__ __launch_bounds__(HIC_THREADS) void k_hic_filter(long long M, const int* __restrict__ pos1, const int* __restrict__ pos2,
-                                                            const double* __restrict__ count, const double* __restrict__ norm,
-                                                            long long n_bins, int res, const int* __restrict__ ws, int N,
-                                                            int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
-                                                            long long capacity, u64* __restrict__ keys, int2* __restrict__ ij) {
+template <bool WRITE, bool DIST>
+__device__ __forceinline__ void hic_filter_body(long long M, const int* __restrict__ pos1, const int* __restrict__ pos2,
+                                                const double* __restrict__ count, const double* __restrict__ norm,
+                                                long long n_bins, int res, const int* __restrict__ ws, int N,
+                                                int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
+                                                long long capacity, u64* __restrict__ keys, int2* __restrict__ ij, long long min_d,
+                                                const double* __restrict__ ex, long long n_ex) {
   __shared__ int wave_tot[HIC_THREADS / WAVE];
   const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   const long long base = (long long)blockIdx.x * HIC_TILE + (long long)w * (HIC_STEPS * WAVE);
@@ -81,7 +100,7 @@ __global__ __launch_bounds__(HIC_THREADS) void k_hic_filter(long long M, const i
     int i = -1, j = -1;
     if (r < M) {
       const int a = pos1[r], b = pos2[r];
-      if (a != b) {
+      if (a != b && (!DIST || hic_gap_ok(a, b, min_d))) {
         i = hic_rank(ws, N, a);
         if (i >= 0) j = hic_rank(ws, N, b);
       }
@@ -112,9 +131,32 @@ __global__ __launch_bounds__(HIC_THREADS) void k_hic_filter(long long M, const i
       const double d = hic_norm_at(norm, n_bins, pos1[r], res) * hic_norm_at(norm, n_bins, pos2[r], res);
       v = v / d;   // one multiply, one divide, both correctly rounded (:84)
     }
+    if (DIST && ex) v = v / hic_expected_at(ex, n_ex, pos1[r], pos2[r], res);   // observed / expected: a second division
     keys[o] = hic_value_key(v);
     ij[o] = make_int2(ri[s], rj[s]);
   }
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(HIC_THREADS) void k_hic_filter(long long M, const int* __restrict__ pos1, const int* __restrict__ pos2,
+                                                            const double* __restrict__ count, const double* __restrict__ norm,
+                                                            long long n_bins, int res, const int* __restrict__ ws, int N,
+                                                            int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
+                                                            long long capacity, u64* __restrict__ keys, int2* __restrict__ ij) {
+  hic_filter_body<WRITE, false>(M, pos1, pos2, count, norm, n_bins, res, ws, N, tile_counts, tile_off, capacity, keys, ij, 0ll, nullptr,
+                                0ll);
+}
+
+// ... with the minimum gap and the expected vector (ex may be NULL: the gap alone)
+template <bool WRITE>
+__global__ __launch_bounds__(HIC_THREADS) void k_hic_filter_dist(long long M, const int* __restrict__ pos1, const int* __restrict__ pos2,
+                                                                 const double* __restrict__ count, const double* __restrict__ norm,
+                                                                 long long n_bins, int res, const int* __restrict__ ws, int N,
+                                                                 int* __restrict__ tile_counts, const long long* __restrict__ tile_off,
+                                                                 long long capacity, u64* __restrict__ keys, int2* __restrict__ ij,
+                                                                 long long min_d, const double* __restrict__ ex, long long n_ex) {
+  hic_filter_body<WRITE, true>(M, pos1, pos2, count, norm, n_bins, res, ws, N, tile_counts, tile_off, capacity, keys, ij, min_d, ex,
+                               n_ex);
 }
 
 // exclusive scan of counts[0..nb) into off[0..nb); the total goes to total64[0] and, clamped to `clamp`, to total32[0]
@@ -344,13 +386,13 @@ __device__ __forceinline__ int hic_up_rank_of(const unsigned* bm, const int* rk,
   return rk[w] + __popc(bm[w] & ((1u << (q & 31)) - 1u));
 }
 
-template <bool WRITE, bool LDS>
-__global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
+template <bool WRITE, bool LDS, bool DIST>
+__device__ __forceinline__ void hic_filter_up_body(
     long long M, const int* __restrict__ pos1, const int* __restrict__ pos2, const double* __restrict__ count,
     const double* __restrict__ norm, long long n_bins, int res, int wbp, int up, const int* __restrict__ ws, int N,
     const unsigned* __restrict__ tab, int nwords, long long nbits, const int* __restrict__ offgrid, long long wtiles,
     int* __restrict__ tile_counts, const long long* __restrict__ tile_off, long long capacity, u64* __restrict__ keys,
-    int2* __restrict__ ij) {
+    int2* __restrict__ ij, long long min_d, const double* __restrict__ ex, long long n_ex) {
   extern __shared__ unsigned hic_up_lds[];
   const bool search = offgrid[0] != 0;
   const unsigned* bm = tab;
@@ -374,7 +416,7 @@ __global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
       unsigned m1 = 0, m2 = 0, diag = 0;
       if (r < M) {
         const int a = pos1[r], b = pos2[r];
-        m1 = hic_up_mask(search, bm, nbits, wbp, up, a, ws, N);
+        if (!DIST || hic_gap_ok(a, b, min_d)) m1 = hic_up_mask(search, bm, nbits, wbp, up, a, ws, N);   // the SOURCE record's gap
         if (m1) m2 = hic_up_mask(search, bm, nbits, wbp, up, b, ws, N);
         diag = a == b;
       }
@@ -401,6 +443,7 @@ __global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
         const double d = hic_norm_at(norm, n_bins, p1, res) * hic_norm_at(norm, n_bins, p2, res);
         v = v / d;   // one multiply, one divide: every child of the record has the record's two norm bins
       }
+      if (DIST && ex) v = v / hic_expected_at(ex, n_ex, p1, p2, res);   // ... and the record's distance
       const u64 key = hic_value_key(v);
       const unsigned m1 = pk[s] & 0xFFu, m2 = (pk[s] >> 8) & 0xFFu;
       const bool diag = (pk[s] >> 16) != 0;
@@ -424,6 +467,28 @@ __global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
       }
     }
   }
+}
+
+template <bool WRITE, bool LDS>
+__global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up(
+    long long M, const int* __restrict__ pos1, const int* __restrict__ pos2, const double* __restrict__ count,
+    const double* __restrict__ norm, long long n_bins, int res, int wbp, int up, const int* __restrict__ ws, int N,
+    const unsigned* __restrict__ tab, int nwords, long long nbits, const int* __restrict__ offgrid, long long wtiles,
+    int* __restrict__ tile_counts, const long long* __restrict__ tile_off, long long capacity, u64* __restrict__ keys,
+    int2* __restrict__ ij) {
+  hic_filter_up_body<WRITE, LDS, false>(M, pos1, pos2, count, norm, n_bins, res, wbp, up, ws, N, tab, nwords, nbits, offgrid, wtiles,
+                                        tile_counts, tile_off, capacity, keys, ij, 0ll, nullptr, 0ll);
+}
+
+template <bool WRITE, bool LDS>
+__global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up_dist(
+    long long M, const int* __restrict__ pos1, const int* __restrict__ pos2, const double* __restrict__ count,
+    const double* __restrict__ norm, long long n_bins, int res, int wbp, int up, const int* __restrict__ ws, int N,
+    const unsigned* __restrict__ tab, int nwords, long long nbits, const int* __restrict__ offgrid, long long wtiles,
+    int* __restrict__ tile_counts, const long long* __restrict__ tile_off, long long capacity, u64* __restrict__ keys,
+    int2* __restrict__ ij, long long min_d, const double* __restrict__ ex, long long n_ex) {
+  hic_filter_up_body<WRITE, LDS, true>(M, pos1, pos2, count, norm, n_bins, res, wbp, up, ws, N, tab, nwords, nbits, offgrid, wtiles,
+                                       tile_counts, tile_off, capacity, keys, ij, min_d, ex, n_ex);
 }
 
 static inline size_t hic_al(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -555,14 +620,33 @@ static int hic_up_tables(hipStream_t st, const HicUpPlan& p, char* w, const int3
   return CGCN_OK;
 }
 
+// the minimum gap and the expected vector of the distance-aware entry points; on = false: the passes as they were
+struct HicDist {
+  bool on;
+  long long min_d;
+  const double* ex;
+  long long n_ex;
+};
+
 template <bool WRITE>
 static void hic_up_filter(hipStream_t st, const HicUpPlan& p, unsigned grid, char* w, long long M, const int32_t* pos1,
                           const int32_t* pos2, const double* count, const double* norm, long long n_bins, int res, int wbp,
-                          const int32_t* ws, int N, long long nbits, long long capacity, u64* keys, int2* ij) {
+                          const int32_t* ws, int N, long long nbits, long long capacity, u64* keys, int2* ij, const HicDist& dx) {
   const unsigned* tab = (const unsigned*)(w + p.o_tab);
   const int* flag = (const int*)(w + p.o_tab + p.tab_bytes - 256);
   int* counts = (int*)(w + p.o_wcounts);
   const long long* off = (const long long*)(w + p.o_woff);
+  if (dx.on) {
+    if (p.lds)
+      hipLaunchKernelGGL((k_hic_filter_up_dist<WRITE, true>), dim3(grid), dim3(HIC_UP_THREADS), (size_t)p.nwords * 8, st, M, pos1, pos2,
+                         count, norm, n_bins, res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij,
+                         dx.min_d, dx.ex, dx.n_ex);
+    else
+      hipLaunchKernelGGL((k_hic_filter_up_dist<WRITE, false>), dim3(grid), dim3(HIC_UP_THREADS), 0, st, M, pos1, pos2, count, norm,
+                         n_bins, res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij, dx.min_d,
+                         dx.ex, dx.n_ex);
+    return;
+  }
   if (p.lds)
     hipLaunchKernelGGL((k_hic_filter_up<WRITE, true>), dim3(grid), dim3(HIC_UP_THREADS), (size_t)p.nwords * 8, st, M, pos1, pos2, count,
                        norm, n_bins, res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij);
@@ -571,16 +655,14 @@ static void hic_up_filter(hipStream_t st, const HicUpPlan& p, unsigned grid, cha
                        res, wbp, p.up, ws, N, tab, p.nwords, nbits, flag, p.wtiles, counts, off, capacity, keys, ij);
 }
 
-extern "C" {
-
-size_t cgcn_hic_workspace_bytes(long long M, int N, long long capacity, long long K) {
+extern "C" size_t cgcn_hic_workspace_bytes(long long M, int N, long long capacity, long long K) {
   HicPlan p;
   return hic_plan(M, N, capacity, K, &p) ? p.total : 0;
 }
 
-int cgcn_hic_count(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
-                   int N, void* workspace, size_t workspace_bytes, long long* n_survivors) {
-  if (M < 0 || N < 0 || !n_survivors) return CGCN_ERR_BAD_ARG;
+static int hic_count_impl(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                          int N, void* workspace, size_t workspace_bytes, long long* n_survivors, const HicDist& dx) {
+  if (M < 0 || N < 0 || !n_survivors || dx.min_d < 0) return CGCN_ERR_BAD_ARG;
   if (M > 0 && (!pos1 || !pos2 || !workspace)) return CGCN_ERR_BAD_ARG;
   if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
   HicPlan p;
@@ -591,22 +673,28 @@ int cgcn_hic_count(cgcn_stream_t stream, long long M, const int32_t* pos1, const
   char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   int* counts = (int*)(w + p.o_counts);
   long long* off = (long long*)(w + p.o_off);
-  hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, (const double*)nullptr,
-                     (const double*)nullptr, 0ll, 1, window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr,
-                     (int2*)nullptr);
+  if (dx.on)
+    hipLaunchKernelGGL(k_hic_filter_dist<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2,
+                       (const double*)nullptr, (const double*)nullptr, 0ll, 1, window_start, N, counts, (const long long*)nullptr, 0ll,
+                       (u64*)nullptr, (int2*)nullptr, dx.min_d, (const double*)nullptr, 0ll);
+  else
+    hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, (const double*)nullptr,
+                       (const double*)nullptr, 0ll, 1, window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr,
+                       (int2*)nullptr);
   hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
   return launch_status();
 }
 
-int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
-                   const double* norm, long long n_bins, int resolution_bp, const int32_t* window_start, int N, long long K,
-                   long long capacity, void* workspace, size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out,
-                   int32_t* nnz_out, long long* n_survivors) {
+static int hic_build_impl(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                          const double* norm, long long n_bins, int resolution_bp, const int32_t* window_start, int N, long long K,
+                          long long capacity, void* workspace, size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out,
+                          int32_t* nnz_out, long long* n_survivors, const HicDist& dx) {
   if (M < 0 || N < 0 || K < 0 || capacity < 0 || n_bins < 0 || !rowptr_out || !nnz_out || !n_survivors || !workspace)
     return CGCN_ERR_BAD_ARG;
   if (M > 0 && (!pos1 || !pos2 || !count)) return CGCN_ERR_BAD_ARG;
   if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
   if (norm && (resolution_bp < 1 || n_bins < 1)) return CGCN_ERR_BAD_ARG;
+  if (dx.min_d < 0 || dx.n_ex < 0 || (dx.ex && (resolution_bp < 1 || dx.n_ex < 1))) return CGCN_ERR_BAD_ARG;
   HicPlan p;
   if (!hic_plan(M, N, capacity, K, &p)) return CGCN_ERR_UNSUPPORTED;
   if (p.half > 0 && !col_out) return CGCN_ERR_BAD_ARG;
@@ -620,26 +708,35 @@ int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const
   if (hipMemsetAsync(rowptr_out, 0, ((size_t)N + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (hipMemsetAsync(nnz_out, 0, 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
-  const int res = norm ? resolution_bp : 1;
-  hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
-                     window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr, (int2*)nullptr);
+  const int res = (norm || dx.ex) ? resolution_bp : 1;
+  if (dx.on)
+    hipLaunchKernelGGL(k_hic_filter_dist<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins,
+                       res, window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr, (int2*)nullptr, dx.min_d, dx.ex,
+                       dx.n_ex);
+  else
+    hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
+                       window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr, (int2*)nullptr);
   hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
   if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
-  hipLaunchKernelGGL(k_hic_filter<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
-                     window_start, N, (int*)nullptr, (const long long*)off, capacity, keyA, ij);
+  if (dx.on)
+    hipLaunchKernelGGL(k_hic_filter_dist<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins,
+                       res, window_start, N, (int*)nullptr, (const long long*)off, capacity, keyA, ij, dx.min_d, dx.ex, dx.n_ex);
+  else
+    hipLaunchKernelGGL(k_hic_filter<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
+                       window_start, N, (int*)nullptr, (const long long*)off, capacity, keyA, ij);
   return hic_select_and_csr(st, p, w, N, K, capacity, rowptr_out, col_out, nnz_out, n_survivors);
 }
 
-size_t cgcn_hic_up_workspace_bytes(long long M, int N, long long capacity, long long K, int resolution_bp, int window_bp,
+extern "C" size_t cgcn_hic_up_workspace_bytes(long long M, int N, long long capacity, long long K, int resolution_bp, int window_bp,
                                    long long n_window_bins) {
   HicUpPlan p;
   return hic_up_plan(M, N, capacity, K, resolution_bp, window_bp, n_window_bins, &p) == CGCN_OK ? p.total : 0;
 }
 
-int cgcn_hic_count_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
-                      int N, int resolution_bp, int window_bp, long long n_window_bins, void* workspace, size_t workspace_bytes,
-                      long long* n_survivors) {
-  if (M < 0 || N < 0 || !n_survivors) return CGCN_ERR_BAD_ARG;
+static int hic_count_up_impl(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2,
+                             const int32_t* window_start, int N, int resolution_bp, int window_bp, long long n_window_bins,
+                             void* workspace, size_t workspace_bytes, long long* n_survivors, const HicDist& dx) {
+  if (M < 0 || N < 0 || !n_survivors || dx.min_d < 0) return CGCN_ERR_BAD_ARG;
   if (M > 0 && (!pos1 || !pos2 || !workspace)) return CGCN_ERR_BAD_ARG;
   if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
   HicUpPlan p;
@@ -652,21 +749,23 @@ int cgcn_hic_count_up(cgcn_stream_t stream, long long M, const int32_t* pos1, co
   unsigned grid = 1;
   if (hic_up_tables(st, p, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
   hic_up_filter<false>(st, p, grid, w, M, pos1, pos2, nullptr, nullptr, 0ll, resolution_bp, window_bp, window_start, N, n_window_bins,
-                       0ll, nullptr, nullptr);
+                       0ll, nullptr, nullptr, dx);
   hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.wtiles, (const int*)(w + p.o_wcounts), (long long*)(w + p.o_woff),
                      n_survivors, (int*)nullptr, 0ll);
   return launch_status();
 }
 
-int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
-                      const double* norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
-                      const int32_t* window_start, int N, long long K, long long capacity, void* workspace, size_t workspace_bytes,
-                      int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out, long long* n_survivors) {
+static int hic_build_up_impl(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                             const double* norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
+                             const int32_t* window_start, int N, long long K, long long capacity, void* workspace,
+                             size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out, long long* n_survivors,
+                             const HicDist& dx) {
   if (M < 0 || N < 0 || K < 0 || capacity < 0 || n_bins < 0 || !rowptr_out || !nnz_out || !n_survivors || !workspace)
     return CGCN_ERR_BAD_ARG;
   if (M > 0 && (!pos1 || !pos2 || !count)) return CGCN_ERR_BAD_ARG;
   if (N > 0 && !window_start) return CGCN_ERR_BAD_ARG;
   if (norm && n_bins < 1) return CGCN_ERR_BAD_ARG;
+  if (dx.min_d < 0 || dx.n_ex < 0 || (dx.ex && dx.n_ex < 1)) return CGCN_ERR_BAD_ARG;
   HicUpPlan u;
   const int rc = hic_up_plan(M, N, capacity, K, resolution_bp, window_bp, n_window_bins, &u);
   if (rc != CGCN_OK) return rc;
@@ -683,13 +782,82 @@ int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t* pos1, co
   unsigned grid = 1;
   if (hic_up_tables(st, u, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
   hic_up_filter<false>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,
-                       0ll, nullptr, nullptr);
+                       0ll, nullptr, nullptr, dx);
   hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)u.wtiles, (const int*)(w + u.o_wcounts), (long long*)(w + u.o_woff),
                      n_survivors, (int*)nullptr, 0ll);
   if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
   hic_up_filter<true>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,
-                      capacity, keyA, ij);
+                      capacity, keyA, ij, dx);
   return hic_select_and_csr(st, p, w, N, K, capacity, rowptr_out, col_out, nnz_out, n_survivors);
+}
+
+
+static const HicDist HIC_PLAIN = {false, 0ll, nullptr, 0ll};
+
+extern "C" {
+
+int cgcn_hic_count(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                   int N, void* workspace, size_t workspace_bytes, long long* n_survivors) {
+  return hic_count_impl(stream, M, pos1, pos2, window_start, N, workspace, workspace_bytes, n_survivors, HIC_PLAIN);
+}
+
+int cgcn_hic_build(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                   const double* norm, long long n_bins, int resolution_bp, const int32_t* window_start, int N, long long K,
+                   long long capacity, void* workspace, size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out,
+                   int32_t* nnz_out, long long* n_survivors) {
+  return hic_build_impl(stream, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_start, N, K, capacity, workspace,
+                        workspace_bytes, rowptr_out, col_out, nnz_out, n_survivors, HIC_PLAIN);
+}
+
+int cgcn_hic_count_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                      int N, int resolution_bp, int window_bp, long long n_window_bins, void* workspace, size_t workspace_bytes,
+                      long long* n_survivors) {
+  return hic_count_up_impl(stream, M, pos1, pos2, window_start, N, resolution_bp, window_bp, n_window_bins, workspace,
+                           workspace_bytes, n_survivors, HIC_PLAIN);
+}
+
+int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                      const double* norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
+                      const int32_t* window_start, int N, long long K, long long capacity, void* workspace, size_t workspace_bytes,
+                      int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out, long long* n_survivors) {
+  return hic_build_up_impl(stream, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, n_window_bins, window_start, N, K,
+                           capacity, workspace, workspace_bytes, rowptr_out, col_out, nnz_out, n_survivors, HIC_PLAIN);
+}
+
+// The distance-aware forms: the same passes with the minimum gap min_distance_bp >= 0 and, in the
+// builds, the expected vector (NULL: none).  Workspaces and sizes as for the four functions above.
+int cgcn_hic_count_dist(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const int32_t* window_start,
+                        int N, long long min_distance_bp, void* workspace, size_t workspace_bytes, long long* n_survivors) {
+  const HicDist dx = {true, min_distance_bp, nullptr, 0ll};
+  return hic_count_impl(stream, M, pos1, pos2, window_start, N, workspace, workspace_bytes, n_survivors, dx);
+}
+
+int cgcn_hic_build_dist(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                        const double* norm, long long n_bins, int resolution_bp, const int32_t* window_start, int N, long long K,
+                        long long capacity, long long min_distance_bp, const double* expected, long long n_expected,
+                        void* workspace, size_t workspace_bytes, int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out,
+                        long long* n_survivors) {
+  const HicDist dx = {true, min_distance_bp, expected, n_expected};
+  return hic_build_impl(stream, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_start, N, K, capacity, workspace,
+                        workspace_bytes, rowptr_out, col_out, nnz_out, n_survivors, dx);
+}
+
+int cgcn_hic_count_up_dist(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2,
+                           const int32_t* window_start, int N, int resolution_bp, int window_bp, long long n_window_bins,
+                           long long min_distance_bp, void* workspace, size_t workspace_bytes, long long* n_survivors) {
+  const HicDist dx = {true, min_distance_bp, nullptr, 0ll};
+  return hic_count_up_impl(stream, M, pos1, pos2, window_start, N, resolution_bp, window_bp, n_window_bins, workspace,
+                           workspace_bytes, n_survivors, dx);
+}
+
+int cgcn_hic_build_up_dist(cgcn_stream_t stream, long long M, const int32_t* pos1, const int32_t* pos2, const double* count,
+                           const double* norm, long long n_bins, int resolution_bp, int window_bp, long long n_window_bins,
+                           const int32_t* window_start, int N, long long K, long long capacity, long long min_distance_bp,
+                           const double* expected, long long n_expected, void* workspace, size_t workspace_bytes,
+                           int32_t* rowptr_out, int32_t* col_out, int32_t* nnz_out, long long* n_survivors) {
+  const HicDist dx = {true, min_distance_bp, expected, n_expected};
+  return hic_build_up_impl(stream, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, n_window_bins, window_start, N, K,
+                           capacity, workspace, workspace_bytes, rowptr_out, col_out, nnz_out, n_survivors, dx);
 }
 
 }  // extern "C"

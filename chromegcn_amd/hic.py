@@ -19,6 +19,30 @@ yields the up^2 - up ordered pairs a != b, and (p + a, p + b) and (p + b, p + a)
 pos2 are multiples of resolution_bp (checked).  expand_contacts_host writes the expanded file out; nothing else here does:
 the device filter and the host restatement both read the compact records and expand only the survivors.
 
+Distance (min_distance_bp, expected).  Contact counts fall steeply with genomic distance, so a top-K
+cut on the value above is mostly a cut on distance; the reference works around it with a minimum distance
+(data/7create_graph_old.py:167, default 1000 in data/create_data.py:28) and a division by Juicer's expected vector
+(7create_graph_old.py:124, :153-154, commented out).  Here, for one chromosome, res = resolution_bp, b1 = pos1 // res,
+b2 = pos2 // res, d = |b1 - b2|, n_bins = the largest bin + 1 unless given (a smaller one is a ValueError):
+  1. Distance sums: raw[d] = sum of count, act[d] = sum of count / (nv[b1] nv[b2]) over the records at distance d (diagonal
+     records at d = 0; nv all ones without a vector), float64 [n_bins]; the host statement is np.bincount in record order.  A
+     negative or non-finite count, or a negative position, is a ValueError, as in hicnorm.
+  2. Expected vector: poss[d] = n_bins - d; w_d = the smallest w >= 0 whose window [max(d - w, 0), min(d + w, n_bins - 1)] has
+     sum raw >= min_count (default 400, Juicer's shot-noise mark), the whole range if no window reaches it; the window is
+     chosen from the RAW sums for every kind; expected[d] = sum_window act / sum_window poss (hicdist.expected_from_sums, one
+     float64 numpy function shared by the device path and the restatement).  Not Juicer's: no scale factor is applied (as
+     for the norm vectors; the top-K selection does not see one), and the window rule is ours, in the spirit of
+     ExpectedValueCalculation but not its running-window loop.
+  3. Scoring: v = (count / (nv[b1] nv[b2])) / ex[d], two IEEE float64 divisions in that order, ex = the expected vector with
+     NaN, 0 and negative entries mapped to +inf; a distance outside the vector reads as +inf.  Without an expected vector the
+     value is the one above, bit for bit.  With window_bp all up^2 children of a record share its value: d comes from the
+     source record's two resolution_bp bins, the expected vector lives at the records' resolution.  expected = "auto": the
+     vector of rule 2 computed from the records with the norm the call scores with.
+  4. Minimum gap: a record takes part only if |pos1 - pos2| >= min_distance_bp (64-bit).  With window_bp the test is on the
+     SOURCE record, before it is expanded (7create_graph_old.py:167-169: the test stands in front of the two `residuals`
+     loops).  min_distance_bp = 0 is the rule above; everything else about survival stays; survivor counts count what
+     survives both rules.
+
 Contact TEXT (a Juicer `RAWobserved` dump, which the reference reads with int() and float(), :71-76) becomes records by one
 rule, restated by parse_contacts_text_host and run on the device by HicContacts.from_text (csrc/cgcn_text.hip):
   * a file is a sequence of lines, each ended by LF or CR LF, the last one possibly by nothing (a CR belongs to the terminator
@@ -110,9 +134,17 @@ def expand_contacts_host(pos1, pos2, count, resolution_bp, window_bp):
 _POPCOUNT8 = np.array([bin(x).count("1") for x in range(256)], dtype=np.int64)
 
 
-def _survivors_up(p1, p2, ws, wbp, up):
+def _gap(min_distance_bp) -> int:
+    g = int(min_distance_bp)
+    if g < 0:
+        raise ValueError("min_distance_bp must not be negative")
+    return g
+
+
+def _survivors_up(p1, p2, ws, wbp, up, keep=None):
     """(source record, child a, child b, i, j) of the survivors of the expanded file, in its order, from the compact records:
-    per record the two up-bit masks of its children that are windows; only records with a survivor are expanded."""
+    per record the two up-bit masks of its children that are windows; only records with a survivor are expanded.  keep: the
+    source records that take part (the minimum gap)."""
     n = ws.size
 
     def masks(p):
@@ -123,6 +155,8 @@ def _survivors_up(p1, p2, ws, wbp, up):
         return m
 
     m1, m2 = masks(p1), masks(p2)
+    if keep is not None:
+        m1 = np.where(keep, m1, np.uint8(0))
     cnt = _POPCOUNT8[m1] * _POPCOUNT8[m2] - np.where(p1 == p2, _POPCOUNT8[m1 & m2], 0)
     rec = np.flatnonzero(cnt > 0)
     bit = np.arange(up, dtype=np.uint8)
@@ -134,10 +168,14 @@ def _survivors_up(p1, p2, ws, wbp, up):
     return src, a, b, np.searchsorted(ws, p1[src] + a * wbp), np.searchsorted(ws, p2[src] + b * wbp)
 
 
-def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp=None):
+def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp=None, min_distance_bp=0, expected=None,
+                    expected_args=None):
     """(record index, i, j, value) of the surviving records in file order (rules 1 and 2).  With window_bp: of the surviving
-    records of the expanded file, the index being the position in it."""
+    records of the expanded file, the index being the position in it.  min_distance_bp, expected (None, a vector, or "auto":
+    hicdist.expected_vector_host with this norm and expected_args): the minimum gap and the observed / expected value of the
+    module docstring."""
     up = _upsample(resolution_bp, window_bp)
+    gap = _gap(min_distance_bp)
     ws = _windows(window_start).astype(np.int64)
     p1, p2 = np.asarray(pos1, dtype=np.int64), np.asarray(pos2, dtype=np.int64)
     if up > 1:
@@ -147,12 +185,12 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
         e = np.zeros(0, np.int64)
         return e, e, e, np.zeros(0, np.float64)
     if up > 1:
-        src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up)
+        src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up, (np.abs(p1 - p2) >= gap) if gap else None)
         idx = src * (up * up) + a * up + b
     else:
         i = np.minimum(np.searchsorted(ws, p1), n - 1)
         j = np.minimum(np.searchsorted(ws, p2), n - 1)
-        idx = src = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2))
+        idx = src = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2) & (np.abs(p1 - p2) >= gap))
         i, j = i[idx], j[idx]
     v = np.asarray(count)[src].astype(np.float64)
     if norm is not None:
@@ -161,24 +199,43 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
         nv[np.isnan(nv) | (nv == 0.0)] = np.inf
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             v = v / (nv[p1[src] // int(resolution_bp)] * nv[p2[src] // int(resolution_bp)])
+    if expected is not None:
+        from . import hicdist
+        if isinstance(expected, str):
+            if expected != "auto":
+                raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+            expected = hicdist.expected_vector_host(pos1, pos2, count, norm, resolution_bp, **(expected_args or {}))
+        if int(resolution_bp) < 1:
+            raise ValueError("resolution_bp must be positive")
+        ex = hicdist.clean_vector(expected)
+        d = np.abs(p1[src] // int(resolution_bp) - p2[src] // int(resolution_bp))
+        e = np.where(d < ex.size, ex[np.minimum(d, max(ex.size - 1, 0))], np.inf) if ex.size else np.full(d.shape, np.inf)
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            v = v / e
     return idx, i, j, v
 
 
 def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None,
-                         norm_args=None) -> sp.csr_matrix:
+                         norm_args=None, min_distance_bp=0, expected=None, expected_args=None) -> sp.csr_matrix:
     """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns).  With window_bp: of
     the expanded file, which is never written out (the CPU path for coarse records at full size).  norm = 'KR' / 'VC' /
-    'SQRTVC': the vector computed from the records (hicnorm.hic_norm_vector_host with norm_args)."""
+    'SQRTVC': the vector computed from the records (hicnorm.hic_norm_vector_host with norm_args).  min_distance_bp, expected
+    (None, a vector, or "auto": hicdist.expected_vector_host with the same norm and expected_args = n_bins / min_count)."""
     ws = _windows(window_start)
     n = ws.size
     k = _budget(hic_edges)
+    if isinstance(expected, str):
+        from . import hicdist
+        if expected != "auto":
+            raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+        expected = hicdist.expected_vector_host(pos1, pos2, count, norm, resolution_bp, norm_args=norm_args, **(expected_args or {}))
     if isinstance(norm, str):
         from . import hicnorm
         norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **(norm_args or {}))
         if not info.get("converged", True):
             raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
         norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
-    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp)
+    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected)
     take = np.argsort(-v, kind="stable")[:k]
     i, j = i[take], j[take]
     a = sp.coo_matrix((np.ones(2 * i.size), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(n, n)).tocsr()
@@ -506,6 +563,9 @@ class HicContacts:
         self._vectors = []   # (the caller's object, its device copy): a sweep passes the same vector again
         self._matrices = {}  # (resolution_bp, n_bins or None) -> hicnorm.DeviceContactMatrix
         self._norms = {}     # norm_vector's argument tuple -> (vector, info)
+        self._gap_survivors = {}   # of the current window set, per (min_distance_bp, resolution_bp, window_bp) with a gap > 0
+        self._dist_sums = {}       # distance_sums' argument tuple -> (raw, act, host syncs)
+        self._expected = {}        # expected_vector's argument tuple -> (vector, info)
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
 
     @classmethod
@@ -643,6 +703,102 @@ class HicContacts:
         v, info = self._norms[key]
         return (v, dict(info)) if return_info else v
 
+    def _named_norm(self, norm, resolution_bp, n_bins=None, norm_args=None):
+        """'KR' / 'VC' / 'SQRTVC' -> the vector computed from the records (HicNormError for a KR that did not converge)"""
+        from . import hicnorm
+        v, info = self.norm_vector(norm, resolution_bp, n_bins=n_bins, return_info=True, **(norm_args or {}))
+        if not info.get("converged", True):
+            raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+        return v
+
+    @staticmethod
+    def _norm_key(norm, norm_args):
+        """the part of a cache key that names the norm; None for a caller's vector (not cached)"""
+        if norm is None:
+            return ("RAW",)
+        if isinstance(norm, str):
+            return (norm,) + tuple(sorted((norm_args or {}).items()))
+        return None
+
+    def distance_sums(self, norm, resolution_bp, n_bins=None, norm_args=None):
+        """(raw, act) of the module docstring's rule 1 as float64 device tensors [n_bins] (cgcn_hicdist_sums).  norm: None
+        (RAW), a vector, or 'KR' / 'VC' / 'SQRTVC' (norm_vector with norm_args; a KR that did not converge raises
+        HicNormError).  One read-back of the bad-record flags, and one more of the largest bin when n_bins is None and no
+        contact matrix of this resolution is resident.  Kept per argument tuple for None and the three names."""
+        return self._distance_sums(norm, resolution_bp, n_bins, norm_args)[:2]
+
+    def _distance_sums(self, norm, resolution_bp, n_bins, norm_args):
+        from . import _lib, hicnorm
+        res = int(resolution_bp)
+        if res < 1:
+            raise ValueError("resolution_bp must be positive")
+        given = None if n_bins is None else int(n_bins)
+        if given is not None and given < 0:
+            raise ValueError("n_bins must not be negative")
+        nk = self._norm_key(norm, norm_args)
+        key = None if nk is None else nk + (res, given)
+        if key is not None and key in self._dist_sums:
+            return self._dist_sums[key]
+        nv = self._named_norm(norm, res, given, norm_args) if isinstance(norm, str) else self._norm(norm)
+        syncs = 0
+        with torch.cuda.device(self.device):
+            sizes = torch.zeros(2, dtype=torch.int64, device=self.device)
+            args = dict(M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
+                        n_norm=0 if nv is None else int(nv.numel()), resolution_bp=res)
+            n = given
+            if n is None and (res, None) in self._matrices:
+                n = self._matrices[(res, None)].n   # aggregate_contacts has checked the records and counted the bins
+            if n is None:
+                need = _lib.query("cgcn_hicdist_workspace_bytes", M=self.M, n_bins=0)
+                wsp = _lib._workspace(need, self.device, "Hi-C distance sums, M=%d" % self.M)
+                _lib.call("cgcn_hicdist_sums", n_bins=0, workspace=wsp, workspace_bytes=need, raw_out=None, act_out=None,
+                          sizes=sizes, **args)
+                flags, n = sizes.tolist()
+                syncs += 1
+                err = hicnorm._bad_records(flags)
+                if err is not None:
+                    raise err
+            raw = torch.zeros(n, dtype=torch.float64, device=self.device)
+            act = torch.zeros(n, dtype=torch.float64, device=self.device)
+            if n:
+                need = _lib.query("cgcn_hicdist_workspace_bytes", M=self.M, n_bins=n)
+                wsp = _lib._workspace(need, self.device, "Hi-C distance sums, M=%d n_bins=%d" % (self.M, n))
+                _lib.call("cgcn_hicdist_sums", n_bins=n, workspace=wsp, workspace_bytes=need, raw_out=raw, act_out=act, sizes=sizes,
+                          **args)
+                flags, top = sizes.tolist()
+                syncs += 1
+                err = hicnorm._bad_records(flags)
+                if err is not None:
+                    raise err
+                if flags & 4:
+                    raise ValueError("n_bins=%d but the records reach bin %d" % (n, top - 1))
+            elif self.M:
+                raise ValueError("n_bins=0 but there are records")
+        out = (raw, act, syncs)
+        if key is not None:
+            self._dist_sums[key] = out
+        return out
+
+    def expected_vector(self, norm, resolution_bp, n_bins=None, min_count=400, return_info=False, norm_args=None):
+        """The expected vector of the module docstring's rule 2 as a float64 device tensor [n_bins]: distance_sums, one
+        read-back of raw and act (2 n_bins doubles), hicdist.expected_from_sums on the host, one upload.  return_info:
+        (vector, {w_max, whole_range: the distances whose window is the whole range, host_syncs}).  Kept per argument tuple
+        for None and the three names."""
+        from . import hicdist
+        nk = self._norm_key(norm, norm_args)
+        key = None if nk is None else nk + (int(resolution_bp), None if n_bins is None else int(n_bins), float(min_count))
+        if key is None or key not in self._expected:
+            raw, act, syncs = self._distance_sums(norm, resolution_bp, n_bins, norm_args)
+            sums = torch.stack([raw, act]).cpu().numpy()
+            ex, info = hicdist.expected_from_sums(sums[0], sums[1], min_count, return_info=True)
+            info = {"w_max": info["w_max"], "whole_range": info["whole_range"], "host_syncs": syncs + 1}
+            hit = (torch.from_numpy(ex).to(self.device), info)
+            if key is None:
+                return (hit[0], dict(info)) if return_info else hit[0]
+            self._expected[key] = hit
+        v, info = self._expected[key]
+        return (v, dict(info)) if return_info else v
+
     def _norm(self, norm) -> Optional[torch.Tensor]:
         if norm is None:
             return None
@@ -659,19 +815,25 @@ class HicContacts:
         ws = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
         if self._ws_host is None or not np.array_equal(ws, self._ws_host):
             self._ws_host, self._ws_dev = ws, torch.from_numpy(ws).to(self.device)
-            self._survivors, self._survivors_up = None, {}
+            self._survivors, self._survivors_up, self._gap_survivors = None, {}, {}
 
     def _window_bins(self, wbp) -> int:
         """the extent of the window bitmap (cgcn_hic_count_up's n_window_bins)"""
         return max(0, int(self._ws_host[-1]) // wbp + 1) if self._ws_host.size else 0
 
-    def survivors(self, window_start, resolution_bp=None, window_bp=None) -> int:
+    def survivors(self, window_start, resolution_bp=None, window_bp=None, min_distance_bp=0, expected=None,
+                  expected_args=None) -> int:
         """records with pos1 != pos2 and both ends among the windows (cgcn_hic_count; one host sync per window set).  With
-        window_bp: of the expanded file (cgcn_hic_count_up; one host sync per window set and window_bp)."""
+        window_bp: of the expanded file (cgcn_hic_count_up; one host sync per window set and window_bp).  min_distance_bp:
+        of the records at least that far apart (the *_dist forms; one host sync per window set, window_bp and gap).  expected,
+        expected_args: taken like the builders' and without effect: a value does not decide survival."""
         from . import _lib
         up = _upsample(resolution_bp, window_bp)
+        gap = _gap(min_distance_bp)
         self._set_windows(window_start)
         n = int(self._ws_host.size)
+        if gap:
+            return self._survivors_with_gap(n, up, resolution_bp, window_bp, gap)
         if window_bp is None or int(window_bp) == int(resolution_bp):
             if self._survivors is None:
                 with torch.cuda.device(self.device):
@@ -702,13 +864,54 @@ class HicContacts:
             self._survivors_up[(res, wbp)] = int(s)
         return self._survivors_up[(res, wbp)]
 
-    def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None):
+    def _survivors_with_gap(self, n, up, resolution_bp, window_bp, gap) -> int:
+        from . import _lib
+        direct = window_bp is None or int(window_bp) == int(resolution_bp)
+        key = (gap, None, None) if direct else (gap, int(resolution_bp), int(window_bp))
+        if key in self._gap_survivors:
+            return self._gap_survivors[key]
+        with torch.cuda.device(self.device):
+            if direct:
+                need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=0, K=0)
+                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d" % self.M)
+                out = torch.zeros(1, dtype=torch.int64, device=self.device)
+                _lib.call("cgcn_hic_count_dist", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
+                          min_distance_bp=gap, workspace=wsp, workspace_bytes=need, n_survivors=out)
+                s = int(out.item())
+            else:
+                res, wbp = key[1], key[2]
+                bins = self._window_bins(wbp)
+                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=0, K=0, resolution_bp=res, window_bp=wbp,
+                                  n_window_bins=bins)
+                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d" % (self.M, up))
+                out = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: survivors, [1]: positions off the grid
+                if res not in self._on_grid:   # read back with the count: still one sync
+                    out[1] = ((self.pos1 % res) != 0).sum() + ((self.pos2 % res) != 0).sum()
+                _lib.call("cgcn_hic_count_up_dist", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
+                          resolution_bp=res, window_bp=wbp, n_window_bins=bins, min_distance_bp=gap, workspace=wsp,
+                          workspace_bytes=need, n_survivors=out)
+                s, off = out.tolist()
+                if off:
+                    raise ValueError("pos1 / pos2 hold %d positions that are no multiple of resolution_bp=%d" % (off, res))
+                self._on_grid.add(res)
+        self._gap_survivors[key] = int(s)
+        return self._gap_survivors[key]
+
+    def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None, min_distance_bp=0,
+                  expected=None, expected_args=None):
         """(rowptr int32 [N + 1], col int32 [>= nnz], sizes int64 [2] = (nnz, survivors)), all on the device, enqueued
         on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors() -- and, for
         norm = 'KR' / 'VC' / 'SQRTVC', those of norm_vector(norm, resolution_bp, **norm_args) when it is not cached; a KR
-        that did not converge raises HicNormError."""
+        that did not converge raises HicNormError.  min_distance_bp, expected (None, a vector, or "auto": expected_vector
+        with the same norm and expected_args = n_bins / min_count): the module docstring's rules 3 and 4; with the defaults
+        the entry points and the graph are the ones without them."""
         from . import _lib
         k = _budget(hic_edges)
+        gap = _gap(min_distance_bp)
+        if isinstance(expected, str):
+            if expected != "auto":
+                raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+            expected = self.expected_vector(norm, resolution_bp, norm_args=norm_args, **(expected_args or {}))
         if isinstance(norm, str):
             from . import hicnorm
             norm, info = self.norm_vector(norm, resolution_bp, return_info=True, **(norm_args or {}))
@@ -718,11 +921,20 @@ class HicContacts:
             norm = hicnorm.pad_vector(norm, int(ws_last[-1]) // int(resolution_bp) + 1 if ws_last.size else 0)
         up = _upsample(resolution_bp, window_bp)
         direct = window_bp is None or int(window_bp) == int(resolution_bp)
-        cap = self.survivors(window_start) if direct else self.survivors(window_start, resolution_bp, window_bp)
+        cap = (self.survivors(window_start, min_distance_bp=gap) if direct
+               else self.survivors(window_start, resolution_bp, window_bp, min_distance_bp=gap))
         ws, n = self._ws_dev, int(self._ws_host.size)
         nv = self._norm(norm)
         if nv is not None:
             _check_norm(nv, resolution_bp, self._ws_host)
+        ex = self._norm(expected)
+        if ex is not None and (ex.ndim != 1 or int(resolution_bp) < 1):
+            raise ValueError("expected must be a vector and resolution_bp positive")
+        dist = {}
+        if gap or ex is not None:   # the *_dist entry points; an empty vector scores as +inf everywhere, like one of NaN
+            if ex is not None and ex.numel() == 0:
+                ex = torch.full((1,), float("nan"), dtype=torch.float64, device=self.device)
+            dist = dict(min_distance_bp=gap, expected=ex, n_expected=0 if ex is None else int(ex.numel()))
         with torch.cuda.device(self.device):
             rowptr = torch.empty(n + 1, dtype=torch.int32, device=self.device)
             col = torch.empty(max(2 * min(k, cap), 1), dtype=torch.int32, device=self.device)
@@ -730,29 +942,31 @@ class HicContacts:
             if direct:
                 need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=cap, K=k)
                 wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d capacity=%d K=%d" % (self.M, cap, k))
-                _lib.call("cgcn_hic_build", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
+                _lib.call("cgcn_hic_build_dist" if dist else "cgcn_hic_build", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
                           n_bins=0 if nv is None else int(nv.numel()), resolution_bp=int(resolution_bp), window_start=ws, N=n,
                           K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr, col_out=col,
-                          nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
+                          nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8, **dist)
             else:
                 res, wbp = int(resolution_bp), int(window_bp)
                 bins = self._window_bins(wbp)
                 need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=cap, K=k, resolution_bp=res,
                                   window_bp=wbp, n_window_bins=bins)
                 wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d capacity=%d K=%d" % (self.M, up, cap, k))
-                _lib.call("cgcn_hic_build_up", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
+                _lib.call("cgcn_hic_build_up_dist" if dist else "cgcn_hic_build_up", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
                           n_bins=0 if nv is None else int(nv.numel()), resolution_bp=res, window_bp=wbp, n_window_bins=bins,
                           window_start=ws, N=n, K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr,
-                          col_out=col, nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8)
+                          col_out=col, nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8, **dist)
         return rowptr, col, sizes
 
     def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
-              norm_args=None):
+              norm_args=None, min_distance_bp=0, expected=None, expected_args=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
         host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back.  norm: a vector,
-        None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords)."""
+        None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords).  min_distance_bp,
+        expected, expected_args: build_raw's."""
         rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
-                                            norm_args=norm_args)
+                                            norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected,
+                                            expected_args=expected_args)
         n = int(rowptr.numel()) - 1
         g = G.normalize_device_csr(adj_type, n, rowptr, col, None, self.device)
         if not return_raw:
@@ -763,14 +977,15 @@ class HicContacts:
 
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
-                    return_raw=False, window_bp=None, norm_args=None):
+                    return_raw=False, window_bp=None, norm_args=None, min_distance_bp=0, expected=None, expected_args=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
     `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
-    coarser than the windows and stand for their expanded file (the module's docstring)."""
+    coarser than the windows and stand for their expanded file (the module's docstring).  min_distance_bp, expected (None, a
+    vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring)."""
     _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
     return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp,
-                   norm_args=norm_args)
+                   norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args)
 
 
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
@@ -784,12 +999,16 @@ def contact_cache_path(root: str, chrom: str) -> str:
 
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",
                                sizes: Optional[Dict[str, int]] = None, window_bp=None,
-                               compute_norm: bool = False) -> Dict[str, G.ChromGraph]:
+                               compute_norm: bool = False, min_distance_bp=0, expected=None,
+                               expected_args=None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
     (`-hic_upsample`): the window size; a cache whose resolution_bp is coarser is built as its expanded file.  compute_norm
-    (`-hic_compute_norm`): a `hicnorm` of 'KR' / 'VC' / 'SQRTVC' that the cache lacks is computed from its records."""
+    (`-hic_compute_norm`): a `hicnorm` of 'KR' / 'VC' / 'SQRTVC' that the cache lacks is computed from its records.
+    min_distance_bp (`-hic_min_distance`), expected (`-hic_expected`: "auto", the vector computed from each cache's records
+    with the vector the call scores with; any other name: the vector the cache stores under it, tools/hic_ingest.py
+    --compute-expected writes eRAW / eKR / eVC / eSQRTVC), expected_args: build_hic_graph's."""
     from . import hicnorm as HN
     out = {}
     for chrom in chroms:
@@ -805,6 +1024,13 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                              % (contact_cache_path(root, chrom), c.window_start.size, sizes[chrom]))
         up = {"window_bp": int(window_bp)} if window_bp is not None and c.resolution_bp > int(window_bp) else {}
         norm = hicnorm if computed else c.norms[hicnorm] if hicnorm else None
+        ex = expected
+        if isinstance(expected, str) and expected != "auto":
+            if expected not in c.norms:
+                raise ValueError("%s holds no %r vector (has: %s)" % (contact_cache_path(root, chrom), expected,
+                                                                     ", ".join(sorted(c.norms)) or "none"))
+            ex = c.norms[expected]
         out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, norm, c.resolution_bp,
-                                     c.window_start, int(hicsize), adj_type=adj_type, device=device, **up)
+                                     c.window_start, int(hicsize), adj_type=adj_type, device=device,
+                                     min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args, **up)
     return out

@@ -37,6 +37,12 @@ def parse(argv=None):
     ap.add_argument("-hic_upsample", action="store_true",
                     help="-hic_contacts: a cache whose records are coarser than -window_size (K562: 5 kb) stands for its "
                          "expanded file, every record for the window pairs it covers (data/extras/upsample_hic.py)")
+    ap.add_argument("-hic_min_distance", type=int, default=0, metavar="BP",
+                    help="-hic_contacts: keep a contact only if its two positions are at least BP apart "
+                         "(data/7create_graph_old.py:167; the reference's graphs use 1000)")
+    ap.add_argument("-hic_expected", action="store_true",
+                    help="-hic_contacts: score a contact by observed / expected, the expected vector computed from the cache's "
+                         "records on the GPU with the run's -hicnorm")
     ap.add_argument("-window_size", type=int, default=1000)          # config_args.py:9
     ap.add_argument("-adj_type", type=str, default="hic", choices=["constant", "hic", "both", "none"])
     ap.add_argument("-gcn_layers", type=int, default=2)              # config_args.py:40
@@ -81,7 +87,9 @@ def load_inputs(opt):
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
                                                         window_bp=opt.window_size if opt.hic_upsample else None,
-                                                        compute_norm=opt.hic_compute_norm)
+                                                        compute_norm=opt.hic_compute_norm,
+                                                        min_distance_bp=opt.hic_min_distance,
+                                                        expected="auto" if opt.hic_expected else None)
         elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:

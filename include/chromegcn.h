@@ -697,6 +697,61 @@ int cgcn_hic_build_up(cgcn_stream_t stream, long long M, const int32_t *pos1, co
                       long long *n_survivors);
 
 /*
+ * Distance-aware graphs (chromegcn_amd/hicdist.py).  These six functions are additions to ABI 26:
+ * CGCN_ABI_VERSION stays 26, nothing above changes.
+ *
+ * The four *_dist functions are cgcn_hic_count / cgcn_hic_build / cgcn_hic_count_up / cgcn_hic_build_up with two more rules:
+ *   min_distance_bp >= 0: a record takes part only if |pos1 - pos2| >= min_distance_bp (computed in 64 bits); with window_bp
+ *       the test is on the SOURCE record, before it is expanded.  Everything else about survival stays, and n_survivors and
+ *       capacity count what survives both rules.
+ *   expected fp64 [n_expected] or NULL: the value becomes (count / (nv[b1] * nv[b2])) / ex[d], two fp64 divisions in that
+ *       order, d = |pos1 / resolution_bp - pos2 / resolution_bp| (floor division; the source record's bins with window_bp),
+ *       ex = expected with NaN, 0 and negative entries read as +inf, and so does a distance outside the vector.
+ * min_distance_bp = 0 and expected = NULL give byte for byte what the functions above give.  Workspaces: those of
+ * cgcn_hic_workspace_bytes / cgcn_hic_up_workspace_bytes.  CGCN_ERR_BAD_ARG also for min_distance_bp < 0, n_expected < 0 and
+ * expected with n_expected < 1 or resolution_bp < 1.
+ */
+int cgcn_hic_count_dist(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2,
+                        const int32_t *window_start, int N, long long min_distance_bp, void *workspace,
+                        size_t workspace_bytes, long long *n_survivors);
+
+int cgcn_hic_build_dist(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                        const double *norm, long long n_bins, int resolution_bp, const int32_t *window_start, int N,
+                        long long K, long long capacity, long long min_distance_bp, const double *expected,
+                        long long n_expected, void *workspace, size_t workspace_bytes, int32_t *rowptr_out,
+                        int32_t *col_out, int32_t *nnz_out, long long *n_survivors);
+
+int cgcn_hic_count_up_dist(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2,
+                           const int32_t *window_start, int N, int resolution_bp, int window_bp, long long n_window_bins,
+                           long long min_distance_bp, void *workspace, size_t workspace_bytes, long long *n_survivors);
+
+int cgcn_hic_build_up_dist(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2,
+                           const double *count, const double *norm, long long n_bins, int resolution_bp, int window_bp,
+                           long long n_window_bins, const int32_t *window_start, int N, long long K, long long capacity,
+                           long long min_distance_bp, const double *expected, long long n_expected, void *workspace,
+                           size_t workspace_bytes, int32_t *rowptr_out, int32_t *col_out, int32_t *nnz_out,
+                           long long *n_survivors);
+
+/*
+ * Distance sums: raw_out[d] = sum of count and act_out[d] = sum of count / (nv[b1] * nv[b2]) over the records with
+ * |b1 - b2| = d, b = pos / resolution_bp; both fp64 [n_bins], every entry written.  norm fp64 [n_norm] or NULL (act = raw)
+ * reads as in cgcn_hic_build: NaN, 0 and a bin outside the vector are +inf, such a record adds 0 to act.  The sums are
+ * ordered (a stable sort by distance, fixed tiles of 64 sorted records, one ordered fold of the tile partials): the same
+ * bits in every run, exact for integer counts below 2^53, no floating-point atomics.
+ * sizes (device uint64 [2]) is written by the call: [0] flags -- 1: a count that is negative or not finite, 2: a negative
+ * position, 4: a bin >= n_bins; a flagged record is left out and the caller is expected to refuse the result -- [1]: the
+ * largest bin + 1.  n_bins = 0: only `sizes` is computed (raw_out, act_out may be NULL), so that a caller can size n_bins.
+ * Enqueue only, no allocation, no sync.  CGCN_ERR_BAD_ARG: a negative size, resolution_bp < 1, a NULL buffer that would be
+ * read or written, norm with n_norm < 1; CGCN_ERR_UNSUPPORTED: M >= 2^31 or n_bins >= 2^31 - 1; CGCN_ERR_WORKSPACE:
+ * workspace_bytes below cgcn_hicdist_workspace_bytes(M, n_bins), which is 0 for unsupported sizes.
+ */
+size_t cgcn_hicdist_workspace_bytes(long long M, long long n_bins);
+
+int cgcn_hicdist_sums(cgcn_stream_t stream, long long M, const int32_t *pos1, const int32_t *pos2, const double *count,
+                      const double *norm, long long n_norm, int resolution_bp, long long n_bins, void *workspace,
+                      size_t workspace_bytes, double *raw_out, double *act_out, unsigned long long *sizes);
+
+/*
  * Hi-C contact text (a Juicer `RAWobserved` dump: data/7create_graph_new.py:71-76 reads it with int() and float()) parsed
  * on the device into pos1 / pos2 / count, the arrays cgcn_hic_count and cgcn_hic_build take (chromegcn_amd/hic.py,
  * DESIGN.md section 4.6).  Additions to ABI 26 like the Hi-C functions above; nothing above changes.

@@ -9,6 +9,11 @@ chromosome's windows with peaks, create_bin_dict :14-47).  Per chromosome the co
 --compute-norms KR,VC,SQRTVC also computes those vectors from the records on the device (chromegcn_amd/hicnorm.py) and
 stores them as cKR / cVC / cSQRTVC -- names Juicer's files never take -- so that `-hicnorm cKR` finds them; the line then
 carries what the KR run reports.  A KR that did not converge is not stored.
+--compute-expected RAW,KR,VC,SQRTVC also computes the expected vectors of those kinds from the records on the device
+(chromegcn_amd/hicdist.py; KR, VC, SQRTVC: with the vector computed from the records) and stores them beside the norm vectors
+as eRAW / eKR / eVC / eSQRTVC: the cache's named-vector section takes any name of at most 16 bytes, so files already written
+stay readable and a reader that does not know these names sees four more vectors.  `graphs_from_contact_caches(...,
+expected="eKR")` scores with a stored one.
 --pairs FILE [--pairs-binning floor|nearest] starts one step earlier, for data that has no Juicer output: FILE is a HiC-Pro
 `allValidPairs` file (one line per read pair); its pairs are binned at --resolution-kb and turned into contact records on the
 device (chromegcn_amd/pairs.py) for every chromosome of --chroms, and the same caches are written.  --hic-root and --cell are
@@ -25,13 +30,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from chromegcn_amd import hic  # noqa: E402
 
 NORMS = ("KR", "VC", "SQRTVC")
+EXPECTED = ("RAW",) + NORMS
+
+
+def expected_vectors(c, kinds, res):
+    """{'e' + kind: the expected vector of the records} (a KR that did not converge is left out)"""
+    from chromegcn_amd.hicnorm import HicNormError
+    out = {}
+    for kind in kinds:
+        try:
+            out["e" + kind] = c.expected_vector(None if kind == "RAW" else kind, res).cpu().numpy()
+        except HicNormError:
+            pass
+    return out
 
 
 def chrom_dir(hic_root, cell, res_kb, chrom):
     return os.path.join(hic_root, "%s_combined" % cell, "%skb_resolution_intrachromosomal" % res_kb, chrom, "MAPQGE30")
 
 
-def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=None, compute_norms=()):
+def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=None, compute_norms=(), compute_expected=()):
     """writes <out>/<chrom>.cghic for every chromosome of `chroms`; returns one dict per chromosome"""
     windows = hic.windows_from_bed(bed, chroms)
     os.makedirs(out, exist_ok=True)
@@ -56,6 +74,7 @@ def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=
                 computed["KR"] = info
             if info.get("converged", True):
                 norms["c" + name] = v.cpu().numpy()
+        norms.update(expected_vectors(c, compute_expected, int(res_kb) * 1000))
         path = hic.contact_cache_path(out, chrom)
         hic.save_contacts_cache(path, c.to_host(norms=norms, resolution_bp=int(res_kb) * 1000, window_start=windows[chrom]))
         lines.append({"chrom": chrom, "records": c.M, "text_bytes": c.text_info["n_bytes"],
@@ -66,7 +85,8 @@ def ingest(hic_root, cell, res_kb, bed, chroms, out, device="cuda", chunk_bytes=
     return lines
 
 
-def ingest_pairs(pairs_file, res_kb, bed, chroms, out, binning="nearest", device="cuda", chunk_bytes=None, compute_norms=()):
+def ingest_pairs(pairs_file, res_kb, bed, chroms, out, binning="nearest", device="cuda", chunk_bytes=None, compute_norms=(),
+                 compute_expected=()):
     """writes <out>/<chrom>.cghic for every chromosome of `chroms` from a read-pair file; returns one dict per chromosome"""
     from chromegcn_amd.pairs import ReadPairs
     windows = hic.windows_from_bed(bed, chroms)
@@ -87,6 +107,7 @@ def ingest_pairs(pairs_file, res_kb, bed, chroms, out, binning="nearest", device
                 computed["KR"] = info
             if info.get("converged", True):
                 norms["c" + name] = v.cpu().numpy()
+        norms.update(expected_vectors(c, compute_expected, res))
         path = hic.contact_cache_path(out, chrom)
         hic.save_contacts_cache(path, c.to_host(norms=norms, resolution_bp=res, window_start=windows[chrom]))
         lines.append({"chrom": chrom, "records": c.M, "kept_pairs": rp.info["kept_per_chrom"][chrom],
@@ -111,6 +132,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="the directory of the caches (train's -hic_contacts)")
     ap.add_argument("--chunk-bytes", type=int, default=None)
     ap.add_argument("--compute-norms", default="", help="comma-separated subset of KR,VC,SQRTVC: stored as cKR, cVC, cSQRTVC")
+    ap.add_argument("--compute-expected", default="", help="comma-separated subset of RAW,KR,VC,SQRTVC: stored as eRAW, eKR, ...")
     opt = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
@@ -118,13 +140,16 @@ def main(argv=None):
     kinds = [k for k in opt.compute_norms.split(",") if k]
     if any(k not in NORMS for k in kinds):
         raise SystemExit("--compute-norms takes a subset of %s" % ",".join(NORMS))
+    expected = [k for k in opt.compute_expected.split(",") if k]
+    if any(k not in EXPECTED for k in expected):
+        raise SystemExit("--compute-expected takes a subset of %s" % ",".join(EXPECTED))
     if opt.pairs:
         return ingest_pairs(opt.pairs, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, binning=opt.pairs_binning,
-                            chunk_bytes=opt.chunk_bytes, compute_norms=kinds)
+                            chunk_bytes=opt.chunk_bytes, compute_norms=kinds, compute_expected=expected)
     if not opt.hic_root or not opt.cell:
         raise SystemExit("--hic-root and --cell are needed unless --pairs is given")
     return ingest(opt.hic_root, opt.cell, opt.resolution_kb, opt.bed, opt.chroms.split(","), opt.out, chunk_bytes=opt.chunk_bytes,
-                  compute_norms=kinds)
+                  compute_norms=kinds, compute_expected=expected)
 
 
 if __name__ == "__main__":
