@@ -6,6 +6,7 @@ from .curves import (Curves, optimal_cutoff_host, optimal_cutoffs, pr_curve_host
                      roc_curves)
 from .embed import class_embeddings  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
+from .compare import compare_labels  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
@@ -13,6 +14,7 @@ from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_no
                       kr_balance_host)
 from .hicdist import (distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
                       hic_expected_vector)
+from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
 from .pairs import ReadPairs, bin_read_pairs_host, pairs_to_contacts_host  # noqa: F401
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 from .thresholds import (ThresholdCounts, best_thresholds, metrics_from_counts, threshold_counts,  # noqa: F401
@@ -30,4 +32,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "threshold_metrics", "metrics_from_counts", "best_thresholds", "threshold_counts_host",
            "threshold_metrics_host", "HicNormError", "contact_matrix_host", "kr_balance_host",
            "hic_norm_vector_host", "hic_norm_vector", "distance_sums_host", "expected_from_sums",
-           "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host"]
+           "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host",
+           "LabelStats", "label_stats", "label_stats_split", "label_stats_host", "compare_labels"]

@@ -20,7 +20,8 @@ SRC = [os.path.join(PKG, "csrc", "cgcn_kernels.hip"), os.path.join(PKG, "csrc", 
        os.path.join(PKG, "csrc", "cgcn_ablation.hip"), os.path.join(PKG, "csrc", "cgcn_hic.hip"),
        os.path.join(PKG, "csrc", "cgcn_text.hip"), os.path.join(PKG, "csrc", "cgcn_tsne.hip"),
        os.path.join(PKG, "csrc", "cgcn_threshold.hip"), os.path.join(PKG, "csrc", "cgcn_hicnorm.hip"),
-       os.path.join(PKG, "csrc", "cgcn_pairs.hip"), os.path.join(PKG, "csrc", "cgcn_hicdist.hip")]
+       os.path.join(PKG, "csrc", "cgcn_pairs.hip"), os.path.join(PKG, "csrc", "cgcn_hicdist.hip"),
+       os.path.join(PKG, "csrc", "cgcn_labelstats.hip")]
 HDR = [os.path.join(ROOT, "include", "chromegcn.h"), os.path.join(PKG, "csrc", "cgcn_common.hpp")]
 LIB = os.path.join(PKG, "libchromegcn_hip.so")
 HASH = LIB + ".srchash"

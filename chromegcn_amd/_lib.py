@@ -138,6 +138,11 @@ _HEADER = {
     "cgcn_pairs_reduce_workspace_bytes": (_c_sz, "n_keys:ll"),
     "cgcn_pairs_reduce": (_c_int, "stream n_keys:ll keys n_chroms:i resolution_bp:i pos1_out pos2_out count_out chrom_offsets "
                                   "n_records workspace workspace_bytes:z"),
+    "cgcn_labelstats_workspace_bytes": (_c_sz, "n:i C:i"),
+    "cgcn_labelstats_windows": (_c_int, "stream n:i C:i targets workspace workspace_bytes:z label_count labels_hist "
+                                        "cooccurrence accumulate:i"),
+    "cgcn_labelstats_graph": (_c_int, "stream n:i C:i nnz:ll rowptr col val label_bits label_bits_bytes:z degree_sum "
+                                      "contact_pairs n_entries accumulate:i"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -118,3 +118,25 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
         print("meanAUPR: " + str(round(out["meanAUPR"], 3)))
         print("meanFDR:  " + str(round(out["meanFDR"], 3)))
     return out
+
+
+def per_chromosome_metrics(probs, targets, lengths, names=None, loss=0.0, device="cuda", **kwargs):
+    """{chromosome: compute_metrics of that chromosome's rows} for predictions and targets that hold the chromosomes one after
+    the other: lengths[i] rows for chromosome names[i] (default names: "0", "1", ...).  The slices are views of the device
+    tensors, so the existing kernels run on them without a copy.  The reference's per-chromosome loop
+    (scripts/analyze_results.py:288-307) selects every chromosome's rows and then hands the UNSLICED arrays to compute_metrics
+    (:304), a slip that gives every chromosome the whole split's metrics; this slices.  `loss` and kwargs go to
+    compute_metrics."""
+    lengths = [int(k) for k in lengths]
+    names = [str(i) for i in range(len(lengths))] if names is None else [str(c) for c in names]
+    if len(names) != len(lengths) or len(set(names)) != len(names):
+        raise ValueError("per_chromosome_metrics: one distinct name per length is needed")
+    p = torch.as_tensor(probs).to(device=device, dtype=torch.float32)
+    t = torch.as_tensor(targets).to(device=device, dtype=torch.float32)
+    if min(lengths, default=0) < 0 or sum(lengths) != p.shape[0] or t.shape != p.shape:
+        raise ValueError("per_chromosome_metrics: the lengths sum to %d but there are %d rows" % (sum(lengths), p.shape[0]))
+    out, at = {}, 0
+    for c, k in zip(names, lengths):
+        out[c] = compute_metrics(p[at:at + k], t[at:at + k], loss, device=device, **kwargs)
+        at += k
+    return out

@@ -63,7 +63,24 @@ def parse(argv=None):
     ap.add_argument("-gpu_id", type=int, default=0)
     ap.add_argument("-br_threshold", type=float, default=None,       # config_args.py:28 (there 0.5; here off unless given)
                     help="also report ACC, HA, ebF1, miF1, maF1 of the decisions p >= this (chromegcn_amd.thresholds)")
+    ap.add_argument("-summarize_data", action="store_true",     # config_args.py:35
+                    help="print labels per window and windows per label (mean, median, max) of train + valid before the "
+                         "first epoch (utils/util_methods.py:64-74; chromegcn_amd.labelstats)")
     return ap.parse_args(argv)
+
+
+def summarize_data(data, dev, out=None):
+    """The six numbers of the reference's summarize_data (utils/util_methods.py:64-74) for train + valid, counted on the
+    device (chromegcn_amd.labelstats); returns the pooled LabelStats."""
+    from . import labelstats
+    targets = [f["target"].to(dev) for sp in ("train", "valid") for f in data[sp].values()]
+    stats = labelstats.label_stats_split(targets)
+    lw, sl = stats.labels_per_window(), stats.samples_per_label()
+    for text, v in (("Mean Labels Per Sample", lw["mean"]), ("Median Labels Per Sample", lw["median"]),
+                    ("Max Labels Per Sample", lw["max"]), ("Mean Samples Per Label", sl["mean"]),
+                    ("Median Samples Per Label", sl["median"]), ("Max Samples Per Label", sl["max"])):
+        print("%s: %s" % (text, round(v, 4)), file=out)
+    return stats
 
 
 def load_inputs(opt):
@@ -104,6 +121,8 @@ def main(argv=None):
     torch.cuda.set_device(opt.gpu_id)
     dev = torch.device("cuda", opt.gpu_id)
     data, graphs = load_inputs(opt)
+    if opt.summarize_data:
+        summarize_data(data, dev)
     first = next(iter(data["train"].values())) if data["train"] else next(iter(data["test"].values()))
     d, n_class = first["forward"].shape[1], first["target"].shape[1]
     model = ChromeGCN(d, d, n_class, opt.gcn_dropout, opt.gate, opt.gcn_layers)       # main.py:62

@@ -1077,6 +1077,45 @@ int cgcn_pairs_reduce(cgcn_stream_t stream, long long n_keys, const unsigned lon
                       int32_t *pos1_out, int32_t *pos2_out, double *count_out, long long *chrom_offsets,
                       long long *n_records, void *workspace, size_t workspace_bytes);
 
+/*
+ * Label and Hi-C neighbourhood statistics (chromegcn_amd/labelstats.py): what
+ * scripts/analyze_results.py:226-266 (get_label_weights) and utils/util_methods.py:24-74 (summarize_data) count, as exact
+ * integers, from tensors that are already on the device.  Additions to ABI 26 like the functions above: CGCN_ABI_VERSION stays
+ * 26, nothing above changes.
+ *
+ * targets: float32 [n, C], 1 <= C <= CGCN_LABELSTATS_MAX_C.  Window u is positive for label c iff targets[u, c] != 0 (the
+ * ablation's rule; NaN is positive); P_c is the set of such windows.
+ *
+ * cgcn_labelstats_windows packs the label bits into `workspace` (uint64 [n][W], W = (C + 63) / 64, bit l of word w = label
+ * 64 w + l; at least cgcn_labelstats_workspace_bytes(n, C) bytes, 0 = unsupported) and writes, all int64:
+ *   label_count  [C]       |P_c|
+ *   labels_hist  [C + 1]   windows with exactly k positive labels
+ *   cooccurrence [C, C]    |P_a and P_b|
+ * cgcn_labelstats_graph takes one chromosome's CSR (n rows, int32, nnz entries; val NULL = every value is 1) and the packed
+ * bits the window call left in its workspace (label_bits, label_bits_bytes of them).  A neighbour entry is a stored entry
+ * (u, v) with u != v and, where val is given, val > 0; deg[u] is their number in row u.  A column outside [0, n) is never
+ * dereferenced and not counted.  It writes, all int64:
+ *   degree_sum    [C]      sum of deg[u] over P_c
+ *   contact_pairs [C, C]   neighbour entries (u, v) with u in P_a and v in P_b (directed entries)
+ *   n_entries     [1]      sum of deg[u] over every row
+ * accumulate: 0 zeroes the outputs first, 1 adds into them (the statistics of several chromosomes add element-wise).
+ *
+ * Enqueue only, no allocation, no sync.  Integer arithmetic only: results are exact and identical from call to call.
+ * CGCN_ERR_UNSUPPORTED (decided before any pointer is looked at): C < 1, C > CGCN_LABELSTATS_MAX_C, nnz >= 2^31;
+ * CGCN_ERR_BAD_ARG: a negative size, a NULL buffer that would be read or written; CGCN_ERR_WORKSPACE: workspace_bytes /
+ * label_bits_bytes below the queried size.  n = 0 launches nothing and still zeroes the outputs when accumulate = 0.
+ */
+#define CGCN_LABELSTATS_MAX_C 256
+
+size_t cgcn_labelstats_workspace_bytes(int n, int C);
+
+int cgcn_labelstats_windows(cgcn_stream_t stream, int n, int C, const float *targets, void *workspace, size_t workspace_bytes,
+                            long long *label_count, long long *labels_hist, long long *cooccurrence, int accumulate);
+
+int cgcn_labelstats_graph(cgcn_stream_t stream, int n, int C, long long nnz, const int32_t *rowptr, const int32_t *col,
+                          const float *val, const void *label_bits, size_t label_bits_bytes, long long *degree_sum,
+                          long long *contact_pairs, long long *n_entries, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif
