@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_graph_count(int n, int adj_type, const 
   counts[i] = cnt;
 }
 
-// exclusive scan of counts[0..n) into out[0..n], out[n] = total.  One workgroup of 1024 threads.
+// exclusive scan of counts[0..n) into out[0..n], out[n] = total.  One workgroup of 1024 threads (k_tile_scan's skeleton over int).
 __global__ __launch_bounds__(1024) void k_graph_scan(int n, const int* __restrict__ counts, int* __restrict__ out) {
   __shared__ long long part[1024];
   const int t = threadIdx.x;

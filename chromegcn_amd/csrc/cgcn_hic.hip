@@ -5,17 +5,17 @@
 // get_top_contact_locs (:93-104), create_adj_mat (:108-120) -- for any edge budget and any normalisation vector.
 //
 //   k_hic_filter<false>  one streaming pass over the M records (pos1, pos2 only): survivors per 2048-record tile
-//   k_hic_scan           exclusive scan of the tile counts (one workgroup); the survivor count S stays on the device
+//   k_tile_scan          exclusive scan of the tile counts (one workgroup); the survivor count S stays on the device
 //   k_hic_filter<true>   the same pass again, now writing the survivors IN FILE ORDER: the sort key of the fp64 value
 //                        count / (nv[pos1 / res] * nv[pos2 / res]) and its window ranks (i, j)
 //   rocprim::radix_sort_keys    a copy of the keys, ascending (= values descending)
 //   k_hic_threshold      t = the K-th sorted key and how many survivors with key t are taken: K - #{keys < t}
-//   k_hic_take<false> / k_hic_scan / k_hic_take<true>   a survivor is taken iff key < t, or key == t and fewer than that many
+//   k_hic_take<false> / k_tile_scan / k_hic_take<true>  a survivor is taken iff key < t, or key == t and fewer than that many
 //                        survivors with key t precede it IN FILE ORDER (an ordered prefix count): the reference's stable
 //                        sorted(reverse=True) cut at K, without ordering the survivors; the taken ones leave as edge keys
 //                        (i << b | j) and (j << b | i), b = bits of N, the others as padding
 //   rocprim::radix_sort_keys    the 2 b low bits of the edge keys (the padding sorts last)
-//   k_hic_unique<false> / k_hic_scan / k_hic_unique<true>   duplicates dropped ((a, b) and (b, a) records merge), columns,
+//   k_hic_unique<false> / k_tile_scan / k_hic_unique<true>   duplicates dropped ((a, b) and (b, a) records merge), columns,
 //                        row pointers and nnz
 // Integer keys, integer counts and ordered writes only: the result does not depend on scheduling.  Nothing is allocated,
 // nothing synchronises, nothing is retained; every size the host cannot know (S, min(K, S), nnz) is read from device
@@ -23,14 +23,12 @@
 #include <cstring>  // rocprim 4.x headers use memset without including it
 #include <rocprim/rocprim.hpp>
 
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
 #define HIC_THREADS 256
 #define HIC_STEPS 8                                    // records per lane of the filter pass
 #define HIC_TILE (HIC_THREADS * HIC_STEPS)             // records per workgroup: 4 waves x 8 steps x 64 lanes
 #define HIC_PAD_KEY 0xFFFFFFFFFFFFFFFFull              // sorts behind every real key in both sorts
-
-typedef unsigned long long u64;
 
 // rank of x in the strictly increasing ws[0..N), or -1.  Branch-free descent to the last element <= x.
 __device__ __forceinline__ int hic_rank(const int* __restrict__ ws, int N, int x) {
@@ -159,36 +157,6 @@ __global__ __launch_bounds__(HIC_THREADS) void k_hic_filter_dist(long long M, co
                                n_ex);
 }
 
-// exclusive scan of counts[0..nb) into off[0..nb); the total goes to total64[0] and, clamped to `clamp`, to total32[0]
-// (either may be NULL).  One workgroup of 1024 threads.
-__global__ __launch_bounds__(1024) void k_hic_scan(int nb, const int* __restrict__ counts, long long* __restrict__ off,
-                                                   long long* __restrict__ total64, int* __restrict__ total32, long long clamp) {
-  __shared__ long long part[1024];
-  const int t = threadIdx.x;
-  const int per = (nb + 1023) / 1024;
-  const int i0 = min(nb, t * per), i1 = min(nb, i0 + per);
-  long long s = 0;
-  for (int i = i0; i < i1; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  long long run = t ? part[t - 1] : 0;
-  for (int i = i0; i < i1; ++i) {
-    off[i] = run;
-    run += counts[i];
-  }
-  if (t == 1023) {
-    const long long tot = part[1023];
-    if (total64) total64[0] = tot;
-    if (total32) total32[0] = (int)(tot < clamp ? tot : clamp);
-  }
-}
-
 // slots [S, capacity) of the sort input, when the caller's capacity exceeds the survivor count
 __global__ __launch_bounds__(256) void k_hic_pad(const long long* __restrict__ n_surv, long long capacity, u64* __restrict__ keys) {
   const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -226,20 +194,16 @@ __global__ __launch_bounds__(256) void k_hic_take(const long long* __restrict__ 
   __shared__ int wave_tot[4];
   const long long S = min(n_surv[0], capacity);
   const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   const u64 t = thr[0];
   const u64 key = o < S ? keys[o] : HIC_PAD_KEY;
   const bool eq = o < S && key == t;
-  const u64 m = __ballot(eq);
-  if (lane == 0) wave_tot[w] = __popcll(m);
-  __syncthreads();
+  const WgFlags<> eqs(eq, wave_tot);
   if (!WRITE) {
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = eqs.count();
     return;
   }
   if (o >= capacity) return;
-  long long rank = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int k = 0; k < w; ++k) rank += wave_tot[k];
+  const long long rank = eqs.before(tile_off[blockIdx.x]);
   u64 e0 = HIC_PAD_KEY, e1 = HIC_PAD_KEY;
   if (o < S && (key < t || (eq && (u64)rank < thr[1]))) {
     const int2 p = ij[o];
@@ -260,7 +224,6 @@ __global__ __launch_bounds__(256) void k_hic_unique(const long long* __restrict_
   __shared__ int wave_tot[4];
   const long long n = 2 * taken[0];
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   u64 e = 0, prev = 0;
   bool head = false;
   if (p < n) {
@@ -268,18 +231,15 @@ __global__ __launch_bounds__(256) void k_hic_unique(const long long* __restrict_
     prev = p > 0 ? edges[p - 1] : 0;
     head = p == 0 || e != prev;
   }
-  const u64 m = __ballot(head);
-  if (lane == 0) wave_tot[w] = __popcll(m);
-  __syncthreads();
+  const WgFlags<> heads(head, wave_tot);
   if (!WRITE) {
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = heads.count();
     return;
   }
   if (p >= n) return;
   const int row = (int)(e >> b);
   if (head) {
-    long long q = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) q += wave_tot[k];
+    const long long q = heads.before(tile_off[blockIdx.x]);
     col[q] = (int)(e & ((1ull << b) - 1ull));
     const int prow = p > 0 ? (int)(prev >> b) : -1;
     for (int r = prow + 1; r <= row; ++r) rowptr[r] = (int)q;
@@ -303,7 +263,7 @@ __global__ __launch_bounds__(256) void k_hic_unique(const long long* __restrict_
 //                        read each); it has popc(m1) popc(m2) - (pos1 == pos2 ? popc(m1 & m2) : 0) survivors.  A wave owns
 //                        512 consecutive records and walks them in 8 steps of 64; the counts are scanned across the wave
 //                        with DPP row shifts.  One count per 512-record wave tile: no barrier between the waves.
-//   k_hic_scan           as above, over the wave tiles
+//   k_tile_scan          as above, over the wave tiles
 //   k_hic_filter_up<true>   the same pass, writing: the value key once per record, (i, j) from the rank table
 // The workgroups are persistent (a wave strides over the wave tiles) so that the copy of the tables into LDS -- up to
 // 2 x 32 KB -- is paid once per workgroup; larger tables are read from global memory (L2) by the same code.
@@ -323,7 +283,7 @@ __global__ __launch_bounds__(256) void k_hic_up_bits(const int* __restrict__ ws,
   if (q < nbits) atomicOr(&bitmap[q >> 5], 1u << (q & 31));   // a start beyond the caller's extent is ignored
 }
 
-// rank[w] = set bits of bitmap[0..w).  One workgroup of 1024 threads.
+// rank[w] = set bits of bitmap[0..w).  One workgroup of 1024 threads (the skeleton of k_tile_scan, cgcn_compact.hpp).
 __global__ __launch_bounds__(1024) void k_hic_up_rank(int nwords, const unsigned* __restrict__ bitmap, int* __restrict__ rank) {
   __shared__ int part[1024];
   const int t = threadIdx.x;
@@ -491,14 +451,6 @@ __global__ __launch_bounds__(HIC_UP_THREADS) void k_hic_filter_up_dist(
                                        tile_counts, tile_off, capacity, keys, ij, min_d, ex, n_ex);
 }
 
-static inline size_t hic_al(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int hic_bits(int N) {
-  int b = 1;
-  while (b < 31 && (1ll << b) < (long long)N) ++b;
-  return b;
-}
-static inline long long hic_tiles(long long n, int tile) { const long long k = (n + tile - 1) / tile; return k < 1 ? 1 : k; }
-
 struct HicPlan {
   long long cap, half, E;      // survivor slots, the most records taken = min(K, capacity), edge slots = 2 cap
   long long tilesM, tilesS, tilesE;
@@ -512,28 +464,28 @@ static bool hic_plan(long long M, int N, long long capacity, long long K, HicPla
   p->cap = capacity < 1 ? 1 : capacity;
   p->half = K < capacity ? K : capacity;
   p->E = 2 * p->cap;
-  p->tilesM = hic_tiles(M, HIC_TILE);
-  p->tilesS = hic_tiles(p->cap, 256);
-  p->tilesE = hic_tiles(p->E, 256);
-  p->b = hic_bits(N);
+  p->tilesM = tiles_of(M, HIC_TILE);
+  p->tilesS = tiles_of(p->cap, 256);
+  p->tilesE = tiles_of(p->E, 256);
+  p->b = bits_for(N);
   size_t t1 = 0, t2 = 0;
   (void)rocprim::radix_sort_keys(nullptr, t1, (const u64*)nullptr, (u64*)nullptr, (size_t)p->cap, 0u, 64u);
   (void)rocprim::radix_sort_keys(nullptr, t2, (const u64*)nullptr, (u64*)nullptr, (size_t)p->E, 0u, (unsigned)(2 * p->b));
   p->temp = t1 > t2 ? t1 : t2;
   const long long tiles = p->tilesM > p->tilesE ? p->tilesM : p->tilesE;
   const size_t e = (size_t)p->E;
-  size_t o = 0;
-  p->o_counts = o; o += hic_al((size_t)tiles * 4);
-  p->o_off = o; o += hic_al((size_t)tiles * 8);
-  p->o_taken = o; o += 256;
-  p->o_thr = o; o += 256;
-  p->o_keyA = o; o += hic_al((size_t)p->cap * 8);
-  p->o_keyB = o; o += hic_al((size_t)p->cap * 8);
-  p->o_ij = o; o += hic_al((size_t)p->cap * 8);
-  p->o_edgeA = o; o += hic_al(e * 8);
-  p->o_edgeB = o; o += hic_al(e * 8);
-  p->o_temp = o; o += hic_al(p->temp);
-  p->total = o + 256;   // the base is rounded up to 256 bytes
+  WsBump w = {0};
+  p->o_counts = w.take((size_t)tiles * 4);
+  p->o_off = w.take((size_t)tiles * 8);
+  p->o_taken = w.take(256);
+  p->o_thr = w.take(256);
+  p->o_keyA = w.take((size_t)p->cap * 8);
+  p->o_keyB = w.take((size_t)p->cap * 8);
+  p->o_ij = w.take((size_t)p->cap * 8);
+  p->o_edgeA = w.take(e * 8);
+  p->o_edgeB = w.take(e * 8);
+  p->o_temp = w.take(p->temp);
+  p->total = w.o + 256;   // the base is rounded up to 256 bytes
   return true;
 }
 
@@ -557,7 +509,7 @@ static int hic_select_and_csr(hipStream_t st, const HicPlan& p, char* w, int N, 
   hipLaunchKernelGGL(k_hic_threshold, dim3(1), dim3(64), 0, st, K, capacity, (const long long*)n_survivors, (const u64*)keyB, taken, thr);
   hipLaunchKernelGGL(k_hic_take<false>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
                      (const u64*)keyA, (const u64*)thr, counts, (const long long*)nullptr, (const int2*)nullptr, p.b, (u64*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesS, (const int*)counts, off, (long long*)nullptr, (int*)nullptr, 0ll);
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tilesS, (const int*)counts, off, (long long*)nullptr, (int*)nullptr, 0ll);
   hipLaunchKernelGGL(k_hic_take<true>, dim3((unsigned)p.tilesS), dim3(256), 0, st, (const long long*)n_survivors, capacity,
                      (const u64*)keyA, (const u64*)thr, (int*)nullptr, (const long long*)off, (const int2*)ij, p.b, edgeA);
   if (rocprim::radix_sort_keys((void*)(w + p.o_temp), temp, (const u64*)edgeA, edgeB, (size_t)p.E, 0u, (unsigned)(2 * p.b), st) !=
@@ -565,7 +517,7 @@ static int hic_select_and_csr(hipStream_t st, const HicPlan& p, char* w, int N, 
     return CGCN_ERR_LAUNCH;
   hipLaunchKernelGGL(k_hic_unique<false>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
                      counts, (const long long*)nullptr, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesE, (const int*)counts, off, (long long*)nullptr, nnz_out,
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tilesE, (const int*)counts, off, (long long*)nullptr, nnz_out,
                      2147483647ll);
   hipLaunchKernelGGL(k_hic_unique<true>, dim3((unsigned)p.tilesE), dim3(256), 0, st, (const long long*)taken, (const u64*)edgeB, p.b, N,
                      (int*)nullptr, (const long long*)off, (const int*)nnz_out, rowptr_out, col_out);
@@ -592,14 +544,13 @@ static int hic_up_plan(long long M, int N, long long capacity, long long K, int 
   if (!hic_plan(M, N, capacity, K, &p->base)) return CGCN_ERR_UNSUPPORTED;
   p->nwords = (int)((n_window_bins + 31) / 32) + 1;   // one zero word behind the last bit
   p->lds = p->nwords <= HIC_UP_LDS_WORDS;
-  p->wtiles = hic_tiles(M, HIC_UP_WTILE);
-  size_t o = p->base.total - 256;   // behind the sibling's buffers
-  p->o_wcounts = o; o += hic_al((size_t)p->wtiles * 4);
-  p->o_woff = o; o += hic_al((size_t)p->wtiles * 8);
-  p->o_tab = o;
-  p->tab_bytes = hic_al((size_t)p->nwords * 8) + 256;   // bitmap, rank table, the off-grid flag
-  o += p->tab_bytes;
-  p->total = o + 256;
+  p->wtiles = tiles_of(M, HIC_UP_WTILE);
+  WsBump w = {p->base.total - 256};   // behind the sibling's buffers
+  p->o_wcounts = w.take((size_t)p->wtiles * 4);
+  p->o_woff = w.take((size_t)p->wtiles * 8);
+  p->tab_bytes = ws_align((size_t)p->nwords * 8) + 256;   // bitmap, rank table, the off-grid flag
+  p->o_tab = w.take(p->tab_bytes);
+  p->total = w.o + 256;
   return CGCN_OK;
 }
 
@@ -614,7 +565,7 @@ static int hic_up_tables(hipStream_t st, const HicUpPlan& p, char* w, const int3
   unsigned* tab = (unsigned*)(w + p.o_tab);
   if (hipMemsetAsync(tab, 0, p.tab_bytes, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (N > 0)
-    hipLaunchKernelGGL(k_hic_up_bits, dim3((unsigned)hic_tiles(N, 256)), dim3(256), 0, st, window_start, N, window_bp, n_window_bins,
+    hipLaunchKernelGGL(k_hic_up_bits, dim3((unsigned)tiles_of(N, 256)), dim3(256), 0, st, window_start, N, window_bp, n_window_bins,
                        tab, (int*)(w + p.o_tab + p.tab_bytes - 256));
   hipLaunchKernelGGL(k_hic_up_rank, dim3(1), dim3(1024), 0, st, p.nwords, (const unsigned*)tab, (int*)(tab + p.nwords));
   return CGCN_OK;
@@ -670,7 +621,7 @@ static int hic_count_impl(cgcn_stream_t stream, long long M, const int32_t* pos1
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   int* counts = (int*)(w + p.o_counts);
   long long* off = (long long*)(w + p.o_off);
   if (dx.on)
@@ -681,7 +632,7 @@ static int hic_count_impl(cgcn_stream_t stream, long long M, const int32_t* pos1
     hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, (const double*)nullptr,
                        (const double*)nullptr, 0ll, 1, window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr,
                        (int2*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
   return launch_status();
 }
 
@@ -700,7 +651,7 @@ static int hic_build_impl(cgcn_stream_t stream, long long M, const int32_t* pos1
   if (p.half > 0 && !col_out) return CGCN_ERR_BAD_ARG;
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   int* counts = (int*)(w + p.o_counts);
   long long* off = (long long*)(w + p.o_off);
   u64* keyA = (u64*)(w + p.o_keyA);
@@ -716,7 +667,7 @@ static int hic_build_impl(cgcn_stream_t stream, long long M, const int32_t* pos1
   else
     hipLaunchKernelGGL(k_hic_filter<false>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins, res,
                        window_start, N, counts, (const long long*)nullptr, 0ll, (u64*)nullptr, (int2*)nullptr);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tilesM, (const int*)counts, off, n_survivors, (int*)nullptr, 0ll);
   if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
   if (dx.on)
     hipLaunchKernelGGL(k_hic_filter_dist<true>, dim3((unsigned)p.tilesM), dim3(HIC_THREADS), 0, st, M, pos1, pos2, count, norm, n_bins,
@@ -745,12 +696,12 @@ static int hic_count_up_impl(cgcn_stream_t stream, long long M, const int32_t* p
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) return hipMemsetAsync(n_survivors, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   unsigned grid = 1;
   if (hic_up_tables(st, p, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
   hic_up_filter<false>(st, p, grid, w, M, pos1, pos2, nullptr, nullptr, 0ll, resolution_bp, window_bp, window_start, N, n_window_bins,
                        0ll, nullptr, nullptr, dx);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)p.wtiles, (const int*)(w + p.o_wcounts), (long long*)(w + p.o_woff),
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.wtiles, (const int*)(w + p.o_wcounts), (long long*)(w + p.o_woff),
                      n_survivors, (int*)nullptr, 0ll);
   return launch_status();
 }
@@ -773,7 +724,7 @@ static int hic_build_up_impl(cgcn_stream_t stream, long long M, const int32_t* p
   if (p.half > 0 && !col_out) return CGCN_ERR_BAD_ARG;
   if (workspace_bytes < u.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   u64* keyA = (u64*)(w + p.o_keyA);
   int2* ij = (int2*)(w + p.o_ij);
   if (hipMemsetAsync(rowptr_out, 0, ((size_t)N + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
@@ -783,7 +734,7 @@ static int hic_build_up_impl(cgcn_stream_t stream, long long M, const int32_t* p
   if (hic_up_tables(st, u, w, window_start, N, window_bp, n_window_bins, &grid) != CGCN_OK) return CGCN_ERR_LAUNCH;
   hic_up_filter<false>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,
                        0ll, nullptr, nullptr, dx);
-  hipLaunchKernelGGL(k_hic_scan, dim3(1), dim3(1024), 0, st, (int)u.wtiles, (const int*)(w + u.o_wcounts), (long long*)(w + u.o_woff),
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)u.wtiles, (const int*)(w + u.o_wcounts), (long long*)(w + u.o_woff),
                      n_survivors, (int*)nullptr, 0ll);
   if (p.half == 0) return launch_status();   // no room for a record (capacity or K is 0): the empty graph
   hic_up_filter<true>(st, u, grid, w, M, pos1, pos2, count, norm, n_bins, resolution_bp, window_bp, window_start, N, n_window_bins,

@@ -21,20 +21,16 @@
 #include <cstring>  // rocprim 4.x headers use memset without including it
 #include <rocprim/rocprim.hpp>
 
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
 #define HD_THREADS 256
 #define HD_NONE 0xFFFFFFFFu                            // no distance: the lanes behind the last key, a tile without a second partial
 
-typedef unsigned long long u64;
-
-static inline size_t hd_al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int hd_bits(long long n) {
   int b = 1;
   while (b < 32 && (1ll << b) < n) ++b;
   return b;
 }
-static inline long long hd_tiles(long long n, int tile) { const long long k = (n + tile - 1) / tile; return k < 1 ? 1 : k; }
 
 __device__ __forceinline__ double hd_norm_at(const double* __restrict__ norm, long long n_norm, long long b) {
   if (b < 0 || b >= n_norm) return __longlong_as_double(0x7FF0000000000000ll);
@@ -200,20 +196,20 @@ static bool hd_plan(long long M, long long n_bins, HdPlan* p) {
   if (M < 0 || n_bins < 0 || M >= 2147483648ll || n_bins >= 2147483647ll) return false;
   p->rb = hd_bits(M);
   p->bits = p->rb + hd_bits(n_bins + 1);
-  p->tiles = hd_tiles(M, WAVE);
+  p->tiles = tiles_of(M, WAVE);
   p->temp = 0;
-  size_t o = 0;
+  WsBump w = {0};
   p->o_keyA = p->o_keyB = p->o_tkey = p->o_tsum = p->o_temp = 0;
   if (n_bins > 0) {
     const size_t m = (size_t)(M < 1 ? 1 : M);
     (void)rocprim::radix_sort_keys(nullptr, p->temp, (const u64*)nullptr, (u64*)nullptr, m, 0u, (unsigned)p->bits);
-    p->o_keyA = o; o += hd_al(m * 8);
-    p->o_keyB = o; o += hd_al(m * 8);
-    p->o_tkey = o; o += hd_al((size_t)p->tiles * 8);
-    p->o_tsum = o; o += hd_al((size_t)p->tiles * 32);
-    p->o_temp = o; o += hd_al(p->temp);
+    p->o_keyA = w.take(m * 8);
+    p->o_keyB = w.take(m * 8);
+    p->o_tkey = w.take((size_t)p->tiles * 8);
+    p->o_tsum = w.take((size_t)p->tiles * 32);
+    p->o_temp = w.take(p->temp);
   }
-  p->total = o + 256;   // the base is rounded up to 256 bytes
+  p->total = w.o + 256;   // the base is rounded up to 256 bytes
   return true;
 }
 
@@ -242,10 +238,10 @@ int cgcn_hicdist_sums(cgcn_stream_t stream, long long M, const int32_t* pos1, co
       return CGCN_ERR_LAUNCH;
     return CGCN_OK;
   }
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   u64* keyA = (u64*)(w + p.o_keyA);
   u64* keyB = (u64*)(w + p.o_keyB);
-  const unsigned blocksM = (unsigned)hd_tiles(M, HD_THREADS);
+  const unsigned blocksM = (unsigned)tiles_of(M, HD_THREADS);
   hipLaunchKernelGGL(k_hd_keys, dim3(blocksM), dim3(HD_THREADS), 0, st, M, pos1, pos2, count, resolution_bp, n_bins, p.rb,
                      n_bins > 0 ? keyA : (u64*)nullptr, (u64*)sizes);
   if (n_bins == 0) return launch_status();
@@ -254,9 +250,9 @@ int cgcn_hicdist_sums(cgcn_stream_t stream, long long M, const int32_t* pos1, co
     return CGCN_ERR_LAUNCH;
   unsigned* tkey = (unsigned*)(w + p.o_tkey);
   double* tsum = (double*)(w + p.o_tsum);
-  hipLaunchKernelGGL(k_hd_tiles, dim3((unsigned)hd_tiles(p.tiles, HD_THREADS / WAVE)), dim3(HD_THREADS), 0, st, M, (const u64*)keyB,
+  hipLaunchKernelGGL(k_hd_tiles, dim3((unsigned)tiles_of(p.tiles, HD_THREADS / WAVE)), dim3(HD_THREADS), 0, st, M, (const u64*)keyB,
                      p.rb, pos1, pos2, count, norm, n_norm, resolution_bp, n_bins, tkey, tsum, raw_out, act_out);
-  hipLaunchKernelGGL(k_hd_fold, dim3((unsigned)hd_tiles(n_bins, HD_THREADS / WAVE)), dim3(HD_THREADS), 0, st, M, (const u64*)keyB, p.rb,
+  hipLaunchKernelGGL(k_hd_fold, dim3((unsigned)tiles_of(n_bins, HD_THREADS / WAVE)), dim3(HD_THREADS), 0, st, M, (const u64*)keyB, p.rb,
                      n_bins, (const unsigned*)tkey, (const double*)tsum, raw_out, act_out);
   return launch_status();
 }

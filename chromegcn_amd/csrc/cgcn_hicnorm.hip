@@ -10,7 +10,7 @@
 //                        record order (keys alone: the (u64, u32) pair sort of rocprim 4 uses 80 B of scratch memory per
 //                        lane on gfx950, which tests/test_kernel_resources.py does not let into the library);
 //                        2 b + rb + 1 <= 64 is the price
-//   k_hn_heads<false> / k_hn_scan / k_hn_heads<true>   an element starts an entry iff its key differs from the one before;
+//   k_hn_heads<false> / k_tile_scan / k_hn_heads<true>   an element starts an entry iff its key differs from the one before;
 //                        the thread of a start walks its run and adds the counts IN RECORD ORDER: one ordered pass, the
 //                        same bits in every run; columns, values, row pointers, the entry count
 //   k_hn_spmv<STATS>     y = m o (A (m o x o p)) in fp64; a workgroup owns 16 consecutive rows: a row of at most
@@ -23,7 +23,7 @@
 #include <cstring>  // rocprim 4.x headers use memset without including it
 #include <rocprim/rocprim.hpp>
 
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
 #define HN_THREADS 256
 #define HN_ROWS 16                  // rows per workgroup of the product
@@ -36,15 +36,6 @@
 #define HN_DELTA 0.1
 #define HN_DELTA_UP 3.0
 
-typedef unsigned long long u64;
-
-static inline size_t hn_al(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int hn_bits(long long n) {
-  int b = 1;
-  while (b < 31 && (1ll << b) < n) ++b;
-  return b;
-}
-static inline long long hn_tiles(long long n) { const long long k = (n + HN_THREADS - 1) / HN_THREADS; return k < 1 ? 1 : k; }
 static inline size_t hn_stride(int n) { return ((size_t)(n < 1 ? 1 : n) + 31) & ~(size_t)31; }
 
 // sizes[1] |= 1: a count that is negative or not finite; |= 2: a negative position; |= 4: a bin >= n_bins (n_bins > 0).
@@ -92,35 +83,6 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_keys(long long M, const int* 
   if (bad) atomicOr(&sizes[1], (u64)bad);
 }
 
-// exclusive scan of counts[0..nb) into off[0..nb); the total goes to total64[0] and to total32[0] (either may be NULL)
-__global__ __launch_bounds__(1024) void k_hn_scan(int nb, const int* __restrict__ counts, long long* __restrict__ off,
-                                                  u64* __restrict__ total64, int* __restrict__ total32) {
-  __shared__ long long part[1024];
-  const int t = threadIdx.x;
-  const int per = (nb + 1023) / 1024;
-  const int i0 = min(nb, t * per), i1 = min(nb, i0 + per);
-  long long s = 0;
-  for (int i = i0; i < i1; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  long long run = t ? part[t - 1] : 0;
-  for (int i = i0; i < i1; ++i) {
-    off[i] = run;
-    run += counts[i];
-  }
-  if (t == 1023) {
-    const long long tot = part[1023];
-    if (total64) total64[0] = (u64)tot;
-    if (total32) total32[0] = (int)(tot < 2147483647ll ? tot : 2147483647ll);
-  }
-}
-
 // sorted keys [0, E), (row, col) = key >> rb: element e starts an entry iff it is no pad and its (row, col) differs from that
 // of e - 1.  WRITE = false counts the starts per 256-element tile.  WRITE = true: the start at output place q < capacity writes its column and the sum of its run's counts
 // in record order; it closes every row after the previous entry's up to its own (rowptr[r] = q); the last entry closes the
@@ -134,7 +96,6 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_heads(long long E, const u64*
   __shared__ int wave_tot[HN_THREADS / WAVE];
   const u64 pad = 1ull << (2 * b);
   const long long e = (long long)blockIdx.x * HN_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   u64 k = pad, prev = pad;   // (row, col) of this element and of the one before
   bool head = false;
   if (e < E) {
@@ -142,16 +103,13 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_heads(long long E, const u64*
     if (e > 0) prev = keys[e - 1] >> rb;
     head = k < pad && (e == 0 || k != prev);
   }
-  const u64 m = __ballot(head);
-  if (lane == 0) wave_tot[w] = __popcll(m);
-  __syncthreads();
+  const WgFlags<> heads(head, wave_tot);
   if (!WRITE) {
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = heads.count();
     return;
   }
   if (!head) return;
-  long long q = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int t = 0; t < w; ++t) q += wave_tot[t];
+  const long long q = heads.before(tile_off[blockIdx.x]);
   const long long row = (long long)(k >> b);
   if (row >= n_bins) return;   // never: k_hn_keys pads such a record
   double s = 0.0;
@@ -433,21 +391,21 @@ struct HnPlan {
 static bool hn_plan(long long M, long long n_bins, HnPlan* p) {
   if (M < 0 || n_bins < 0 || M >= 2147483647ll || n_bins >= 2147483647ll) return false;
   p->E = 2 * (M < 1 ? 1 : M);
-  p->tiles = hn_tiles(p->E);
-  p->b = n_bins > 0 ? hn_bits(n_bins) : 31;
-  p->rb = n_bins > 0 ? hn_bits(M) : 0;
+  p->tiles = tiles_of(p->E, HN_THREADS);
+  p->b = n_bins > 0 ? bits_for(n_bins) : 31;
+  p->rb = n_bins > 0 ? bits_for(M) : 0;
   if (2 * p->b + p->rb + 1 > 64) return false;
   size_t t = 0;
   (void)rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (size_t)p->E, 0u, (unsigned)(2 * p->b + p->rb + 1));
   p->temp = t;
-  size_t o = 0;
-  p->o_sizes = o; o += 256;
-  p->o_counts = o; o += hn_al((size_t)p->tiles * 4);
-  p->o_off = o; o += hn_al((size_t)p->tiles * 8);
-  p->o_keyA = o; o += hn_al((size_t)p->E * 8);
-  p->o_keyB = o; o += hn_al((size_t)p->E * 8);
-  p->o_temp = o; o += hn_al(p->temp);
-  p->total = o + 256;   // the base is rounded up to 256 bytes
+  WsBump w = {0};
+  p->o_sizes = w.take(256);
+  p->o_counts = w.take((size_t)p->tiles * 4);
+  p->o_off = w.take((size_t)p->tiles * 8);
+  p->o_keyA = w.take((size_t)p->E * 8);
+  p->o_keyB = w.take((size_t)p->E * 8);
+  p->o_temp = w.take(p->temp);
+  p->total = w.o + 256;   // the base is rounded up to 256 bytes
   return true;
 }
 
@@ -460,21 +418,22 @@ static int hn_sorted(hipStream_t st, const HnPlan& p, char* w, long long M, cons
   long long* off = (long long*)(w + p.o_off);
   const long long E = 2 * M;
   if (hipMemsetAsync(sizes, 0, 32, st) != hipSuccess) return CGCN_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_hn_keys, dim3((unsigned)hn_tiles(M)), dim3(HN_THREADS), 0, st, M, pos1, pos2, count, res, n_bins, p.b, p.rb, keyA,
-                     sizes);
+  hipLaunchKernelGGL(k_hn_keys, dim3((unsigned)tiles_of(M, HN_THREADS)), dim3(HN_THREADS), 0, st, M, pos1, pos2, count, res, n_bins, p.b,
+                     p.rb, keyA, sizes);
   size_t temp = p.temp;
   if (rocprim::radix_sort_keys((void*)(w + p.o_temp), temp, (const u64*)keyA, keyB, (size_t)E, 0u, (unsigned)(2 * p.b + p.rb + 1), st) !=
       hipSuccess)
     return CGCN_ERR_LAUNCH;
-  hipLaunchKernelGGL(k_hn_heads<false>, dim3((unsigned)hn_tiles(E)), dim3(HN_THREADS), 0, st, E, (const u64*)keyB, count, p.b, p.rb,
-                     n_bins, counts, (const long long*)nullptr, (const int*)nullptr, 0ll, (int*)nullptr, (int*)nullptr,
+  hipLaunchKernelGGL(k_hn_heads<false>, dim3((unsigned)tiles_of(E, HN_THREADS)), dim3(HN_THREADS), 0, st, E, (const u64*)keyB, count, p.b,
+                     p.rb, n_bins, counts, (const long long*)nullptr, (const int*)nullptr, 0ll, (int*)nullptr, (int*)nullptr,
                      (double*)nullptr);
-  hipLaunchKernelGGL(k_hn_scan, dim3(1), dim3(1024), 0, st, (int)hn_tiles(E), (const int*)counts, off, sizes, total32);
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)tiles_of(E, HN_THREADS), (const int*)counts, off,
+                     (long long*)sizes, total32, 2147483647ll);
   return CGCN_OK;
 }
 
 static int hn_blocks(int n) {
-  const long long k = hn_tiles(n);
+  const long long k = tiles_of(n, HN_THREADS);
   return (int)(k < HN_MAX_BLOCKS ? k : HN_MAX_BLOCKS);
 }
 
@@ -494,7 +453,7 @@ int cgcn_hicnorm_count(cgcn_stream_t stream, long long M, const int32_t* pos1, c
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   if (M == 0) return hipMemsetAsync(sizes, 0, 32, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   const int rc = hn_sorted(st, p, w, M, pos1, pos2, count, resolution_bp, n_bins, (u64*)sizes, (int*)nullptr);
   return rc != CGCN_OK ? rc : launch_status();
 }
@@ -510,7 +469,7 @@ int cgcn_hicnorm_fill(cgcn_stream_t stream, long long M, const int32_t* pos1, co
   if (!hn_plan(M, n_bins, &p) || capacity >= 2147483647ll) return CGCN_ERR_UNSUPPORTED;
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   const int n = (int)n_bins;
   if (hipMemsetAsync(rowptr, 0, ((size_t)n + 1) * 4, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (M == 0) {
@@ -520,8 +479,8 @@ int cgcn_hicnorm_fill(cgcn_stream_t stream, long long M, const int32_t* pos1, co
     const int rc = hn_sorted(st, p, w, M, pos1, pos2, count, resolution_bp, n_bins, (u64*)sizes, total32);
     if (rc != CGCN_OK) return rc;
     const long long E = 2 * M;
-    hipLaunchKernelGGL(k_hn_heads<true>, dim3((unsigned)hn_tiles(E)), dim3(HN_THREADS), 0, st, E, (const u64*)(w + p.o_keyB),
-                       count, p.b, p.rb, n_bins, (int*)nullptr, (const long long*)(w + p.o_off),
+    hipLaunchKernelGGL(k_hn_heads<true>, dim3((unsigned)tiles_of(E, HN_THREADS)), dim3(HN_THREADS), 0, st, E,
+                       (const u64*)(w + p.o_keyB), count, p.b, p.rb, n_bins, (int*)nullptr, (const long long*)(w + p.o_off),
                        (const int*)total32, capacity, rowptr, col, val);
   }
   hipLaunchKernelGGL(k_hn_spmv<true>, dim3((unsigned)((n + HN_ROWS - 1) / HN_ROWS)), dim3(HN_THREADS), 0, st, n, (const int*)rowptr,
@@ -564,8 +523,8 @@ int cgcn_hicnorm_vector(cgcn_stream_t stream, int n, int kind, const double* vc,
   if (n < 0 || kind < 0 || kind > 2) return CGCN_ERR_BAD_ARG;
   if (n == 0) return CGCN_OK;
   if (!out || (kind == 2 ? !state : !vc)) return CGCN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(k_hn_vector, dim3((unsigned)hn_tiles(n)), dim3(HN_THREADS), 0, (hipStream_t)stream, n, kind, vc, (const double*)state,
-                     hn_stride(n), out);
+  hipLaunchKernelGGL(k_hn_vector, dim3((unsigned)tiles_of(n, HN_THREADS)), dim3(HN_THREADS), 0, (hipStream_t)stream, n, kind, vc,
+                     (const double*)state, hn_stride(n), out);
   return launch_status();
 }
 

@@ -17,7 +17,7 @@
 #include <cstring>  // rocprim 4.x headers use memset without including it
 #include <rocprim/rocprim.hpp>
 
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
 // Sort key of one (window i, label c) pair: [label c][~ordered(score)][target bit].  ordered() is the usual
 // order-preserving map of IEEE floats to unsigned; complemented so that an ascending sort lists each label's scores in
@@ -673,7 +673,7 @@ int cgcn_multilabel_metrics_nonneg(cgcn_stream_t stream, long long n, int C, con
   hipStream_t st = (hipStream_t)stream;
   const size_t items = (size_t)n * C;
   const int T = rs_tiles(n), nch = metric_chunks(n);
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   unsigned* k_a = (unsigned*)w; w += al(items * 4);
   unsigned* k_b = (unsigned*)w; w += al(items * 4);
   unsigned* hist = (unsigned*)w; w += al((size_t)C * T * 256 * 4);
@@ -699,7 +699,7 @@ int cgcn_multilabel_metrics(cgcn_stream_t stream, long long n, int C, const floa
   if (workspace_bytes < cgcn_metrics_workspace_bytes(n, C)) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const size_t items = (size_t)n * C;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   unsigned long long* k_in = (unsigned long long*)w; w += al(items * 8);
   unsigned long long* k_out = (unsigned long long*)w; w += al(items * 8);
   float* keys_out = (float*)k_in;                                  // 4 bytes per item of the 8 ...
@@ -753,7 +753,7 @@ struct CurveWs {
 };
 static size_t curve_ws_layout(void* workspace, long long n, int C, CurveWs& L) {
   const size_t items = (size_t)n * C, nrec = (size_t)C * metric_chunks(n);
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   char* w0 = w;
   L.k_a = (unsigned*)w; w += al(items * 4);
   L.k_b = (unsigned*)w; L.pidx = (int*)w; w += al(items * 4);

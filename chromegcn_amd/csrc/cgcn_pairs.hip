@@ -6,7 +6,7 @@
 //
 // cgcn_pairs_parse, one chunk:
 //   k_pairs_starts<false>  one pass over the bytes, 16 per lane: line starts per 4 KiB tile (as k_text_starts of cgcn_text.hip)
-//   k_pairs_scan           exclusive scan of the tile counts (one workgroup): the line number of every tile's first line
+//   k_tile_scan            exclusive scan of the tile counts (one workgroup): the line number of every tile's first line
 //   k_pairs_starts<true>   the tile and the 272 bytes behind it in LDS with the table of chromosome names; the line starts of the
 //                          tile are listed in LDS in order and handed out to consecutive lanes, so that the lanes that walk lines
 //                          sit in as few waves as the tile allows.  The lane that owns a line start walks its line (the line is
@@ -15,14 +15,14 @@
 //                          integers, bins them, applies min_diff.  A kept pair's key goes to the tile's slot of a temporary at
 //                          its rank among the tile's kept pairs; a line that is not FAST goes to the flag list as (line, byte
 //                          offset, kind, rank among the kept pairs in front of it).
-//   k_pairs_scan           exclusive scan of the kept counts per tile
+//   k_tile_scan            exclusive scan of the kept counts per tile
 //   k_pairs_compact        the tiles' keys, in order, behind the keys of the earlier chunks: keys[kept so far + ...]
 //   k_pairs_finish         ranks of the flag list made global; the chunk's class totals added to the running totals
 // The running totals (device int64 [8]) are read once at the start of a call (copied into the workspace: the line number and
 // the key index this chunk starts at) and written once at its end; nothing else is kept between calls.
 //
 // cgcn_pairs_reduce, once: rocprim::radix_sort_keys over bits 1..62 of the keys (the swap bit is not sorted on),
-//   k_pairs_heads<false> / k_pairs_scan / k_pairs_heads<true> (a key starts a record iff it differs from the one before above
+//   k_pairs_heads<false> / k_tile_scan / k_pairs_heads<true> (a key starts a record iff it differs from the one before above
 //   bit 0; the record's positions, its first key and the chromosome offsets), k_pairs_counts (count = distance to the next
 //   record's first key, as fp64).
 //
@@ -33,11 +33,11 @@
 #include <cstring>  // rocprim 4.x headers use memset without including it
 #include <rocprim/rocprim.hpp>
 
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
-#define PAIRS_THREADS 256
-#define PAIRS_CHUNK 16                                   // bytes per lane
-#define PAIRS_TILE (PAIRS_THREADS * PAIRS_CHUNK)         // bytes per workgroup
+#define PAIRS_THREADS LINES_THREADS
+#define PAIRS_CHUNK LINES_CHUNK                          // bytes per lane
+#define PAIRS_TILE LINES_TILE                            // bytes per workgroup
 #define PAIRS_LINE_MAX CGCN_PAIRS_LINE_MAX               // bytes of a fast line, terminator excluded
 #define PAIRS_SCAN (PAIRS_LINE_MAX + 2)                  // a line start looks this far for its LF: the line, CR, LF
 #define PAIRS_OVER 272                                   // bytes behind the tile kept in LDS (>= PAIRS_SCAN - 1, a multiple of 16)
@@ -47,8 +47,6 @@
 #define RED_THREADS 256
 #define RED_ITEMS 4
 #define RED_TILE (RED_THREADS * RED_ITEMS)
-
-typedef unsigned long long u64;
 
 // the class of a line: its index in the totals
 enum { LINE_EMPTY = CGCN_PAIRS_T_EMPTY, LINE_KEPT = CGCN_PAIRS_T_KEPT, LINE_INTER = CGCN_PAIRS_T_INTER_CHROM,
@@ -61,37 +59,6 @@ struct PairsRule {
   u64 magic;            // floor(2^64 / res) + 1
   long long min_diff;
 };
-
-// the 16 bytes at g (g a multiple of 16, g < n); bytes at or behind n read as 0.  The text base is 16-byte aligned.
-__device__ __forceinline__ u32x4 pairs_load16(const unsigned char* __restrict__ text, long long n, long long g) {
-  if (g + PAIRS_CHUNK <= n) return *(const u32x4*)(text + g);
-  u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int k = 0; k < PAIRS_CHUNK; ++k)
-    if (g + k < n) v[k >> 2] |= (uint32_t)text[g + k] << ((k & 3) * 8);
-  return v;
-}
-
-// bit k: byte g + k starts a line (it exists, and it is byte 0 or follows an LF)
-__device__ __forceinline__ unsigned pairs_start_mask(const u32x4 v, bool after_lf, long long n, long long g) {
-  unsigned lf = 0;
-#pragma unroll
-  for (int k = 0; k < PAIRS_CHUNK; ++k) lf |= (((v[k >> 2] >> ((k & 3) * 8)) & 0xFFu) == 0x0Au ? 1u : 0u) << k;
-  const unsigned starts = ((lf << 1) | (after_lf ? 1u : 0u)) & 0xFFFFu;
-  const long long left = n - g;
-  return left >= PAIRS_CHUNK ? starts : (left <= 0 ? 0u : starts & ((1u << (int)left) - 1u));
-}
-
-// sum of `c` over the lanes before this one (all 64 lanes active)
-__device__ __forceinline__ int pairs_lanes_before(int c, int lane) {
-  int inc = c;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(inc, o);
-    if (lane >= o) inc += t;
-  }
-  return inc - c;
-}
 
 // a name of 1 to 15 bytes between s[p] and the TAB behind it, packed: bytes 0-7 in lo, 8-14 in hi, the length in hi's top
 // byte.  Returns the length (which may exceed 15: the packed form then means nothing); p is left on the TAB.
@@ -197,25 +164,14 @@ __global__ __launch_bounds__(PAIRS_THREADS) void k_pairs_starts(const unsigned c
   __shared__ u64 names[PARSE ? 2 * PAIRS_NAMES : 1];
   __shared__ int wave_tot[PAIRS_THREADS / WAVE];
   __shared__ unsigned cls[8];
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
   const long long base = (long long)blockIdx.x * PAIRS_TILE;
-  const long long g = base + (long long)threadIdx.x * PAIRS_CHUNK;
-  u32x4 v = {0u, 0u, 0u, 0u};
-  bool after_lf = false;
-  if (g < n) {
-    v = pairs_load16(text, n, g);
-    after_lf = g == 0 || text[g - 1] == 0x0Au;
-  }
-  const unsigned starts = pairs_start_mask(v, after_lf, n, g);
-  const int mine = __popc(starts);
-  const int before = pairs_lanes_before(mine, lane);
-  if (lane == WAVE - 1) wave_tot[w] = before + mine;
+  const LinesFront f = lines_tile_front(text, n, wave_tot);
   if (PARSE) {
-    *(u32x4*)(tile + threadIdx.x * PAIRS_CHUNK) = v;
+    *(u32x4*)(tile + threadIdx.x * PAIRS_CHUNK) = f.v;
     if (threadIdx.x < PAIRS_OVER / PAIRS_CHUNK) {
       const long long go = base + PAIRS_TILE + (long long)threadIdx.x * PAIRS_CHUNK;
       u32x4 o = {0u, 0u, 0u, 0u};
-      if (go < n) o = pairs_load16(text, n, go);
+      if (go < n) o = lines_load16(text, n, go);
       *(u32x4*)(tile + PAIRS_TILE + threadIdx.x * PAIRS_CHUNK) = o;
     }
     if (threadIdx.x < 2 * R.n_chroms) names[threadIdx.x] = names_g[threadIdx.x];
@@ -223,13 +179,12 @@ __global__ __launch_bounds__(PAIRS_THREADS) void k_pairs_starts(const unsigned c
   }
   __syncthreads();
   if (!PARSE) {
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wg_count(wave_tot);
     return;
   }
-  int first = before;
-  for (int k = 0; k < w; ++k) first += wave_tot[k];
-  const int n_lines = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  for (unsigned m = starts; m; m &= m - 1u, ++first) lstart[first] = (unsigned short)(threadIdx.x * PAIRS_CHUNK + (__ffs(m) - 1));
+  int first = wg_before(f.before, wave_tot);
+  const int n_lines = wg_count(wave_tot);
+  for (unsigned m = f.starts; m; m &= m - 1u, ++first) lstart[first] = (unsigned short)(threadIdx.x * PAIRS_CHUNK + (__ffs(m) - 1));
   __syncthreads();                                       // wave_tot is reused below
   const long long line0 = (long long)ws[WS_BASE + CGCN_PAIRS_T_LINES] + tile_off[blockIdx.x];
   int kept_base = 0;                                     // kept pairs of the rounds before
@@ -242,13 +197,9 @@ __global__ __launch_bounds__(PAIRS_THREADS) void k_pairs_starts(const unsigned c
       kind = pairs_parse_line(tile + rel, n - (base + rel), R, names, key);
       atomicAdd(&cls[kind], 1u);
     }
-    const u64 kb = __ballot(kind == LINE_KEPT);
-    const int wrank = __popcll(kb & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[w] = __popcll(kb);
-    __syncthreads();
-    int rank = kept_base + wrank;
-    for (int k = 0; k < w; ++k) rank += wave_tot[k];
-    kept_base += wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    const WgFlags<> kept(kind == LINE_KEPT, wave_tot);
+    const int rank = kept.before(kept_base);
+    kept_base += kept.count();
     if (kind == LINE_KEPT) {
       if (rank < PAIRS_TILE_KEYS) tmp_keys[(size_t)blockIdx.x * PAIRS_TILE_KEYS + rank] = key;
     } else if (kind == LINE_SLOW || kind == LINE_MALFORMED) {
@@ -264,31 +215,6 @@ __global__ __launch_bounds__(PAIRS_THREADS) void k_pairs_starts(const unsigned c
   }
   if (threadIdx.x == 0) kept_counts[blockIdx.x] = kept_base < PAIRS_TILE_KEYS ? kept_base : PAIRS_TILE_KEYS;
   if (threadIdx.x >= 1 && threadIdx.x < 8 && threadIdx.x != LINE_KEPT && cls[threadIdx.x]) atomicAdd(&ws[WS_CLASS + threadIdx.x], (u64)cls[threadIdx.x]);
-}
-
-// exclusive scan of counts[0..nb) into off[0..nb); the total goes to total[0].  One workgroup of 1024 threads.
-__global__ __launch_bounds__(1024) void k_pairs_scan(int nb, const int* __restrict__ counts, long long* __restrict__ off,
-                                                     long long* __restrict__ total) {
-  __shared__ long long part[1024];
-  const int t = threadIdx.x;
-  const int per = (nb + 1023) / 1024;
-  const int i0 = min(nb, t * per), i1 = min(nb, i0 + per);
-  long long s = 0;
-  for (int i = i0; i < i1; ++i) s += counts[i];
-  part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const long long v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  long long run = t ? part[t - 1] : 0;
-  for (int i = i0; i < i1; ++i) {
-    off[i] = run;
-    run += counts[i];
-  }
-  if (t == 1023) total[0] = part[1023];
 }
 
 // the keys of tile blockIdx.x behind the keys of the tiles and the chunks before it
@@ -339,15 +265,14 @@ __global__ __launch_bounds__(RED_THREADS) void k_pairs_heads(long long n, const 
     if (i0 + j < n && (i0 + j == 0 || (k[j + 1] >> 1) != (k[j] >> 1))) heads |= 1u << j;
   }
   const int mine = __popc(heads);
-  const int before = pairs_lanes_before(mine, lane);
+  const int before = wave_excl_sum(mine, lane);
   if (lane == WAVE - 1) wave_tot[w] = before + mine;
   __syncthreads();
   if (!WRITE) {
-    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    if (threadIdx.x == 0) tile_counts[blockIdx.x] = wg_count(wave_tot);
     return;
   }
-  long long r = tile_off[blockIdx.x] + before;
-  for (int q = 0; q < w; ++q) r += wave_tot[q];
+  long long r = wg_before(tile_off[blockIdx.x] + before, wave_tot);
 #pragma unroll
   for (int j = 0; j < RED_ITEMS; ++j) {
     if (i0 + j >= n) break;
@@ -379,21 +304,18 @@ struct PairsPlan {
   size_t o_counts, o_off, o_kcounts, o_koff, o_ws, o_tmp, total;
 };
 
-static inline size_t pairs_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static bool pairs_plan(long long n_bytes, PairsPlan* p) {
   if (n_bytes < 0) return false;
-  p->tiles = (n_bytes + PAIRS_TILE - 1) / PAIRS_TILE;
-  if (p->tiles < 1) p->tiles = 1;
+  p->tiles = tiles_of(n_bytes, PAIRS_TILE);
   if (p->tiles >= 2147483647ll) return false;
-  size_t o = 0;
-  p->o_counts = o; o += pairs_al((size_t)p->tiles * 4);
-  p->o_off = o; o += pairs_al((size_t)p->tiles * 8);
-  p->o_kcounts = o; o += pairs_al((size_t)p->tiles * 4);
-  p->o_koff = o; o += pairs_al((size_t)p->tiles * 8);
-  p->o_ws = o; o += pairs_al(WS_WORDS * 8);
-  p->o_tmp = o; o += pairs_al((size_t)p->tiles * PAIRS_TILE_KEYS * 8);
-  p->total = o + 256;   // the base is rounded up to 256 bytes
+  WsBump b = {0};
+  p->o_counts = b.take((size_t)p->tiles * 4);
+  p->o_off = b.take((size_t)p->tiles * 8);
+  p->o_kcounts = b.take((size_t)p->tiles * 4);
+  p->o_koff = b.take((size_t)p->tiles * 8);
+  p->o_ws = b.take(WS_WORDS * 8);
+  p->o_tmp = b.take((size_t)p->tiles * PAIRS_TILE_KEYS * 8);
+  p->total = b.o + 256;   // the base is rounded up to 256 bytes
   return true;
 }
 
@@ -405,17 +327,17 @@ struct ReducePlan {
 static bool reduce_plan(long long n_keys, ReducePlan* p) {
   if (n_keys < 0 || n_keys >= 2147483647ll) return false;
   const long long n = n_keys < 1 ? 1 : n_keys;
-  p->tiles = (n + RED_TILE - 1) / RED_TILE;
+  p->tiles = tiles_of(n, RED_TILE);
   size_t t = 0;
   (void)rocprim::radix_sort_keys(nullptr, t, (const u64*)nullptr, (u64*)nullptr, (size_t)n, 1u, 63u);
   p->temp = t;
-  size_t o = 0;
-  p->o_sorted = o; o += pairs_al((size_t)n * 8);
-  p->o_first = o; o += pairs_al((size_t)n * 4);
-  p->o_counts = o; o += pairs_al((size_t)p->tiles * 4);
-  p->o_off = o; o += pairs_al((size_t)p->tiles * 8);
-  p->o_temp = o; o += pairs_al(t);
-  p->total = o + 256;
+  WsBump b = {0};
+  p->o_sorted = b.take((size_t)n * 8);
+  p->o_first = b.take((size_t)n * 4);
+  p->o_counts = b.take((size_t)p->tiles * 4);
+  p->o_off = b.take((size_t)p->tiles * 8);
+  p->o_temp = b.take(t);
+  p->total = b.o + 256;
   return true;
 }
 
@@ -440,7 +362,7 @@ int cgcn_pairs_parse(cgcn_stream_t stream, const void* text, long long n_bytes, 
   if (!pairs_plan(n_bytes, &p)) return CGCN_ERR_UNSUPPORTED;
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   u64* ws = (u64*)(w + p.o_ws);
   if (hipMemsetAsync(ws, 0, WS_WORDS * 8, st) != hipSuccess) return CGCN_ERR_LAUNCH;
   if (hipMemcpyAsync(ws + WS_BASE, totals, 64, hipMemcpyDeviceToDevice, st) != hipSuccess) return CGCN_ERR_LAUNCH;
@@ -455,13 +377,13 @@ int cgcn_pairs_parse(cgcn_stream_t stream, const void* text, long long n_bytes, 
     hipLaunchKernelGGL(k_pairs_starts<false>, dim3((unsigned)p.tiles), dim3(PAIRS_THREADS), 0, st, t, n_bytes, (int*)(w + p.o_counts),
                        (const long long*)nullptr, R, (const u64*)nullptr, 0ll, (u64*)nullptr, (int*)nullptr, (long long*)nullptr, 0ll,
                        (u64*)nullptr);
-    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_counts), (long long*)(w + p.o_off),
-                       (long long*)(ws + WS_LINES));
+    hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_counts), (long long*)(w + p.o_off),
+                       (long long*)(ws + WS_LINES), (int*)nullptr, 0ll);
     hipLaunchKernelGGL(k_pairs_starts<true>, dim3((unsigned)p.tiles), dim3(PAIRS_THREADS), 0, st, t, n_bytes, (int*)nullptr,
                        (const long long*)(w + p.o_off), R, (const u64*)names, byte_base, (u64*)(w + p.o_tmp), (int*)(w + p.o_kcounts),
                        flags, flag_capacity, ws);
-    hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_kcounts),
-                       (long long*)(w + p.o_koff), (long long*)(ws + WS_KEPT));
+    hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_kcounts),
+                       (long long*)(w + p.o_koff), (long long*)(ws + WS_KEPT), (int*)nullptr, 0ll);
     hipLaunchKernelGGL(k_pairs_compact, dim3((unsigned)p.tiles), dim3(PAIRS_THREADS), 0, st, (const u64*)(w + p.o_tmp),
                        (const int*)(w + p.o_kcounts), (const long long*)(w + p.o_koff), (const u64*)ws, (u64*)keys, key_capacity);
   }
@@ -489,7 +411,7 @@ int cgcn_pairs_reduce(cgcn_stream_t stream, long long n_keys, const unsigned lon
     if (hipMemsetAsync(chrom_offsets, 0, (size_t)(n_chroms + 1) * 8, st) != hipSuccess) return CGCN_ERR_LAUNCH;
     return hipMemsetAsync(n_records, 0, 8, st) == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH;
   }
-  char* w = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* w = ws_base(workspace);
   u64* sorted = (u64*)(w + p.o_sorted);
   size_t temp = p.temp;
   if (rocprim::radix_sort_keys((void*)(w + p.o_temp), temp, (const u64*)keys, sorted, (size_t)n_keys, 1u, 63u, st) != hipSuccess)
@@ -497,8 +419,8 @@ int cgcn_pairs_reduce(cgcn_stream_t stream, long long n_keys, const unsigned lon
   hipLaunchKernelGGL(k_pairs_heads<false>, dim3((unsigned)p.tiles), dim3(RED_THREADS), 0, st, n_keys, (const u64*)sorted,
                      (int*)(w + p.o_counts), (const long long*)nullptr, (const long long*)nullptr, n_chroms, (unsigned)resolution_bp,
                      (int*)nullptr, (int*)nullptr, (unsigned*)nullptr, (long long*)nullptr);
-  hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_counts), (long long*)(w + p.o_off),
-                     n_records);
+  hipLaunchKernelGGL(k_tile_scan<>, dim3(1), dim3(1024), 0, st, (int)p.tiles, (const int*)(w + p.o_counts), (long long*)(w + p.o_off),
+                     n_records, (int*)nullptr, 0ll);
   hipLaunchKernelGGL(k_pairs_heads<true>, dim3((unsigned)p.tiles), dim3(RED_THREADS), 0, st, n_keys, (const u64*)sorted, (int*)nullptr,
                      (const long long*)(w + p.o_off), (const long long*)n_records, n_chroms, (unsigned)resolution_bp, pos1_out, pos2_out,
                      (unsigned*)(w + p.o_first), chrom_offsets);

@@ -16,7 +16,7 @@
 //
 // No atomics: a row is reduced inside one wave, totals by one workgroup in a fixed order, so two launches with the same
 // inputs give the same bits.
-#include "cgcn_common.hpp"
+#include "cgcn_compact.hpp"
 
 #include <math.h>
 
@@ -328,8 +328,6 @@ __global__ __launch_bounds__(SUM_THREADS) void k_tsne_update(int n, float* __res
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static inline size_t ts_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // workspace: Z (one double in 256 bytes) | zrow fp32 [n] | klrow / row totals fp64 [n]
 struct TsnePlan {
   size_t o_z, o_zrow, o_rows, total;
@@ -342,11 +340,10 @@ static bool tsne_shape_ok(int n, int ld) {
 static void tsne_plan(int n, TsnePlan* p) {
   p->o_z = 0;
   p->o_zrow = 256;
-  p->o_rows = p->o_zrow + ts_align((size_t)n * 4);
-  p->total = p->o_rows + ts_align((size_t)n * 8) + 256;   // + 256: the base is aligned up inside the call
+  p->o_rows = p->o_zrow + ws_align((size_t)n * 4);
+  p->total = p->o_rows + ws_align((size_t)n * 8) + 256;   // + 256: the base is aligned up inside the call
 }
 
-static inline char* tsne_base(void* workspace) { return (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
 static inline int tsne_launched() { return hipGetLastError() == hipSuccess ? CGCN_OK : CGCN_ERR_LAUNCH; }
 
 extern "C" {
@@ -380,7 +377,7 @@ int cgcn_tsne_symmetrize(cgcn_stream_t stream, int n, int ld, const float* C, fl
   TsnePlan p;
   tsne_plan(n, &p);
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
-  char* w = tsne_base(workspace);
+  char* w = ws_base(workspace);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_tsne_rowsum, dim3((unsigned)n), dim3(256), 0, st, n, ld, C, (double*)(w + p.o_rows));
   hipLaunchKernelGGL(k_tsne_total<double>, dim3(1), dim3(SUM_THREADS), 0, st, n, (const double*)(w + p.o_rows), 2.0, (double*)(w + p.o_z));
@@ -396,7 +393,7 @@ int cgcn_tsne_gradient(cgcn_stream_t stream, int n, int ld, const float* P, cons
   TsnePlan p;
   tsne_plan(n, &p);
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
-  char* w = tsne_base(workspace);
+  char* w = ws_base(workspace);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((n + TG_ROWS - 1) / TG_ROWS)), block(TG_THREADS);
   double* Z = (double*)(w + p.o_z);
@@ -420,7 +417,7 @@ int cgcn_tsne_update(cgcn_stream_t stream, int n, float* Y, float* update, float
   TsnePlan p;
   tsne_plan(n, &p);
   if (workspace_bytes < p.total) return CGCN_ERR_WORKSPACE;
-  char* w = tsne_base(workspace);
+  char* w = ws_base(workspace);
   hipLaunchKernelGGL(k_tsne_update, dim3(1), dim3(SUM_THREADS), 0, (hipStream_t)stream, n, Y, update, gains, grad, momentum,
                      learning_rate, (const double*)(w + p.o_rows), (const double*)(w + p.o_z), have_kl, record);
   return tsne_launched();
