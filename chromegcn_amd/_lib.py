@@ -245,6 +245,13 @@ def _workspace(nbytes, device, what):
     return torch.empty(nbytes, device=device, dtype=torch.uint8)
 
 
+def workspace_for(fn, device, what, **sizes):
+    """(uint8 workspace, its size in bytes) for the sizes the `*_workspace_bytes` function `fn` takes; `what` names the
+    call in the unsupported-shape error"""
+    nbytes = query(fn, **sizes)
+    return _workspace(nbytes, device, what), nbytes
+
+
 def head_workspace(n, S, d, C, device):
     """the uint8 workspace of cgcn_head_fwd / cgcn_head_train / cgcn_head_bwd"""
     return _workspace(query("cgcn_head_workspace_bytes", n=n, S=S, d=d, C=C), device,

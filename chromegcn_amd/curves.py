@@ -77,8 +77,7 @@ def _curves_raw(kind: str, probs: torch.Tensor, targets: torch.Tensor, drop_inte
     if probs.dim() != 2 or tuple(targets.shape) != tuple(probs.shape):
         raise RuntimeError("probs and targets must both be [n, C]")
     n, C = probs.shape
-    ws_bytes = _lib.query("cgcn_curves_workspace_bytes", n=n, C=C)
-    ws = _lib._workspace(ws_bytes, probs.device, "curves, n=%d C=%d" % (n, C))
+    ws, ws_bytes = _lib.workspace_for("cgcn_curves_workspace_bytes", probs.device, "curves, n=%d C=%d" % (n, C), n=n, C=C)
     head = torch.zeros(C + 2, device=probs.device, dtype=torch.int64)   # offsets [C + 1], then the `bad` word
     offsets = head[:C + 1]
     _lib.call("cgcn_curves_count", n=n, C=C, probs=probs, targets=targets,

@@ -43,35 +43,22 @@ b2 = pos2 // res, d = |b1 - b2|, n_bins = the largest bin + 1 unless given (a sm
      loops).  min_distance_bp = 0 is the rule above; everything else about survival stays; survivor counts count what
      survives both rules.
 
-Contact TEXT (a Juicer `RAWobserved` dump, which the reference reads with int() and float(), :71-76) becomes records by one
-rule, restated by parse_contacts_text_host and run on the device by HicContacts.from_text (csrc/cgcn_text.hip):
-  * a file is a sequence of lines, each ended by LF or CR LF, the last one possibly by nothing (a CR belongs to the terminator
-    only in front of an LF); record r is the r-th line; the empty piece behind a final terminator is no line; a line is
-    F1 TAB F2 TAB F3;
-  * FAST: at most TEXT_LINE_MAX = 64 bytes without the terminator; F1, F2 one to ten decimal digits below 2^31; F3 is
-    [+-]? digits [. digits]? ([eE] [+-]? digits)?; its digits without leading zeros and without trailing zeros of the fraction
-    are at most 15 and form the integer w < 10^15 < 2^53; e = exponent - (fraction digits that remain in w), |e| <= 22; the
-    value is float(w) * 10^e (e >= 0) or float(w) / 10^-e, negated behind '-': one correctly rounded operation on two exact
-    operands, so it IS float(F3);
-  * SLOW: not fast, but int(float(F1)), int(float(F2)) and float(F3) accept the fields and the positions fit int32 (16 or more
-    digits, |e| > 22, nan, inf, 1e3 as a position, blanks around a field, a line beyond the bound): parsed by exactly those
-    calls, on the host in both paths; 17-digit normalised dumps are of this kind throughout: load_contacts_text reads
-    those faster;
-  * MALFORMED: everything else (an empty line, a field count other than three, a '#' comment, a field float() rejects):
-    ValueError naming the first such line, 1-based, the same text from both paths."""
+Contact TEXT becomes records by the rule of chromegcn_amd/hictext.py (HicContacts.from_text, parse_contacts_text_host); the
+`.cghic` cache of the records is chromegcn_amd/hiccache.py's.  Their public names are still found here."""
 from __future__ import annotations
 
-import csv
-import os
-import time
-from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from . import graph as G
+# the names that lived here before the text rule, the cache format and the staging buffers got modules of their own
+from ._textio import release_text_staging  # noqa: F401
+from .hiccache import (HostContacts, contact_cache_path, load_contacts_cache, load_contacts_text,  # noqa: F401
+                       save_contacts_cache, windows_from_bed)
+from .hictext import TEXT_LINE_MAX, TEXT_MALFORMED, TEXT_SLOW, parse_contacts_text, parse_contacts_text_host  # noqa: F401
 
 
 # ----------------------------------------------------------------------------------------------
@@ -141,6 +128,13 @@ def _gap(min_distance_bp) -> int:
     return g
 
 
+def _auto_expected(expected) -> bool:
+    """whether `expected` asks for the vector computed from the records; any string but "auto" is an error"""
+    if isinstance(expected, str) and expected != "auto":
+        raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+    return isinstance(expected, str)
+
+
 def _survivors_up(p1, p2, ws, wbp, up, keep=None):
     """(source record, child a, child b, i, j) of the survivors of the expanded file, in its order, from the compact records:
     per record the two up-bit masks of its children that are windows; only records with a survivor are expanded.  keep: the
@@ -201,9 +195,7 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
             v = v / (nv[p1[src] // int(resolution_bp)] * nv[p2[src] // int(resolution_bp)])
     if expected is not None:
         from . import hicdist
-        if isinstance(expected, str):
-            if expected != "auto":
-                raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+        if _auto_expected(expected):
             expected = hicdist.expected_vector_host(pos1, pos2, count, norm, resolution_bp, **(expected_args or {}))
         if int(resolution_bp) < 1:
             raise ValueError("resolution_bp must be positive")
@@ -224,16 +216,13 @@ def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, h
     ws = _windows(window_start)
     n = ws.size
     k = _budget(hic_edges)
-    if isinstance(expected, str):
+    if _auto_expected(expected):
         from . import hicdist
-        if expected != "auto":
-            raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
         expected = hicdist.expected_vector_host(pos1, pos2, count, norm, resolution_bp, norm_args=norm_args, **(expected_args or {}))
     if isinstance(norm, str):
         from . import hicnorm
         norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **(norm_args or {}))
-        if not info.get("converged", True):
-            raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+        hicnorm._require_converged(info)
         norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
     _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected)
     take = np.argsort(-v, kind="stable")[:k]
@@ -246,299 +235,15 @@ def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, h
 
 
 # ----------------------------------------------------------------------------------------------
-# contact records of one chromosome on the host: text parser and flat binary cache
-# ----------------------------------------------------------------------------------------------
-@dataclass
-class HostContacts:
-    pos1: np.ndarray                 # int32 [M]
-    pos2: np.ndarray                 # int32 [M]
-    count: np.ndarray                # float64 [M]
-    norms: Dict[str, np.ndarray] = field(default_factory=dict)   # name ('KR', 'VC', 'SQRTVC') -> float64 [n_bins]
-    resolution_bp: int = 1000
-    window_start: Optional[np.ndarray] = None   # int32 [N]: the chromosome's windows with peaks, when known
-
-    @property
-    def M(self) -> int:
-        return int(self.pos1.shape[0])
-
-
-def load_contacts_text(raw_path: str, norm_paths: Optional[Dict[str, str]] = None, resolution_bp: int = 1000,
-                       window_start=None) -> HostContacts:
-    """Parse a `RAWobserved` file (`start_pos1<TAB>start_pos2<TAB>count` per line) and its norm files (one value per line,
-    'NaN' allowed) once, with numpy.  Slow and simple on purpose: the result goes into the binary cache."""
-    raw = np.loadtxt(raw_path, dtype=np.float64, delimiter="\t", ndmin=2)
-    if raw.size == 0:
-        raw = raw.reshape(0, 3)
-    if raw.shape[1] != 3:
-        raise ValueError("%s: expected three columns, found %d" % (raw_path, raw.shape[1]))
-    norms = {name: np.loadtxt(p, dtype=np.float64, ndmin=1) for name, p in (norm_paths or {}).items()}
-    return HostContacts(raw[:, 0].astype(np.int32), raw[:, 1].astype(np.int32), np.ascontiguousarray(raw[:, 2]), norms,
-                        int(resolution_bp), None if window_start is None else _windows(window_start))
-
-
-# ----------------------------------------------------------------------------------------------
-# contact text -> records: the rule of the module docstring on the host
-# ----------------------------------------------------------------------------------------------
-TEXT_LINE_MAX = 64   # include/chromegcn.h: CGCN_TEXT_LINE_MAX
-TEXT_SLOW, TEXT_MALFORMED = 1, 2
-_P10 = np.array([float("1e%d" % k) for k in range(23)])           # the 23 powers of ten that are exact in fp64
-_P10U = np.array([10 ** k for k in range(16)], dtype=np.uint64)
-
-
-def _malformed(record: int) -> ValueError:
-    return ValueError("contact text: line %d is not `pos1<TAB>pos2<TAB>count`" % (record + 1))
-
-
-def _slow_line(raw: bytes):
-    """(pos1, pos2, count) of one line without its terminator by Python's own int(float(.)) and float(.); None = malformed"""
-    f = raw.split(b"\t")
-    if len(f) != 3:
-        return None
-    try:
-        a, b, v = int(float(f[0])), int(float(f[1])), float(f[2])
-    except (ValueError, OverflowError):
-        return None
-    if not (-2 ** 31 <= a < 2 ** 31 and -2 ** 31 <= b < 2 ** 31):
-        return None
-    return a, b, v
-
-
-def _text_bytes(data) -> np.ndarray:
-    if isinstance(data, np.ndarray):
-        if data.dtype != np.uint8 or data.ndim != 1:
-            raise TypeError("contact text as an array must be a uint8 vector")
-        return np.ascontiguousarray(data)
-    return np.frombuffer(data, dtype=np.uint8)
-
-
-def _text_lines(buf):
-    """(start, end) int64 [M] of every line: its first byte and the byte behind its last (terminator excluded)"""
-    n = buf.size
-    lf = np.flatnonzero(buf == 10)
-    start = np.concatenate([np.zeros(1, np.int64), lf + 1])
-    start = start[start < n]
-    end = np.concatenate([lf, np.full(1, n, np.int64)])[:start.size]
-    cr = (end < n) & (end > start) & (buf[np.maximum(end - 1, 0)] == 13)
-    return start, end - cr
-
-
-def _text_fast(buf, start, end):
-    """The fast form, all lines at once, one byte of every line per step (the walk of cgcn_text.hip's text_parse_line):
-    (fast bool [M], pos1 int64 [M], pos2 int64 [M], count float64 [M]); the last three mean nothing where fast is False."""
-    n, m_lines = buf.size, start.size
-    bufp = np.concatenate([buf, np.zeros(1, np.uint8)])
-
-    def at(p):
-        return bufp[np.minimum(p, n)].astype(np.int64)
-
-    ok = (end - start >= 1) & (end - start <= TEXT_LINE_MAX)
-    p = start.copy()
-    pos = []
-    for _ in range(2):   # one to ten digits below 2^31, then the TAB
-        x, nd, run = np.zeros(m_lines, np.int64), np.zeros(m_lines, np.int64), ok.copy()
-        for _ in range(11):
-            d = at(p) - 48
-            run = run & (p < end) & (d >= 0) & (d <= 9)
-            if not run.any():
-                break
-            x = np.where(run, x * 10 + d, x)
-            nd += run
-            p += run
-        ok &= (nd >= 1) & (nd <= 10) & (x < 2 ** 31) & (p < end) & (at(p) == 9)
-        p += 1
-        pos.append(x)
-    c = at(p)
-    sign = ok & (p < end) & ((c == 43) | (c == 45))
-    neg = sign & (c == 45)
-    p += sign
-    st = np.ones(m_lines, np.int8)   # 1 integer digits, 2 fraction digits, 3 behind [eE], 4 exponent digits
-    w = np.zeros(m_lines, np.uint64)
-    nsig, nint, nfr, fr, z, ex, nex = (np.zeros(m_lines, np.int64) for _ in range(7))
-    eneg = np.zeros(m_lines, bool)
-    for _ in range(TEXT_LINE_MAX):
-        act = ok & (p < end)
-        if not act.any():
-            break
-        c = at(p)
-        d = c - 48
-        isd = (d >= 0) & (d <= 9)
-        du = np.where(isd, d, 0).astype(np.uint64)
-        is_e = (c | 32) == 101
-        in1, in2, in3, in4 = act & (st == 1), act & (st == 2), act & (st == 3), act & (st == 4)
-        # integer part: leading zeros do not count
-        dig = in1 & isd
-        grow = dig & ((nsig > 0) | (d != 0))
-        nsig += grow
-        w = np.where(grow & (nsig <= 15), w * np.uint64(10) + du, w)   # never beyond 15 digits: w does not wrap
-        nint += dig
-        # fraction: zeros wait in z until a digit follows them
-        dig2 = in2 & isd
-        nfr += dig2
-        nz = dig2 & (d != 0)
-        first = nz & (nsig == 0)
-        more = nz & (nsig > 0)
-        nsig = np.where(first, 1, np.where(more, nsig + z + 1, nsig))
-        w = np.where(first, du, np.where(more & (nsig <= 15), w * _P10U[np.minimum(z + 1, 15)] + du, w))
-        fr += np.where(nz, z + 1, 0)
-        z = np.where(nz, 0, z + (dig2 & (d == 0)))
-        # exponent
-        esign = in3 & ((c == 43) | (c == 45))
-        eneg |= esign & (c == 45)
-        dig4 = (in3 | in4) & isd
-        ex = np.where(dig4 & (ex < 10000), ex * 10 + d, ex)
-        nex += dig4
-        # what ends a part
-        end1, end2 = in1 & ~isd, in2 & ~isd
-        to2 = end1 & (nint >= 1) & (c == 46)
-        to3 = (end1 & (nint >= 1) & is_e) | (end2 & (nfr >= 1) & is_e)
-        ok &= ~((end1 & ~to2 & ~to3) | (end2 & ~to3) | (in3 & ~esign & ~isd) | (in4 & ~isd))
-        st = np.where(to2, 2, np.where(to3, 3, np.where(esign | dig4, 4, st))).astype(np.int8)
-        p += act
-    ok &= np.where(st == 1, nint >= 1, np.where(st == 2, nfr >= 1, nex >= 1))
-    e = np.where(eneg, -ex, ex) - fr
-    ok &= (nsig <= 15) & (e >= -22) & (e <= 22)
-    mant = w.astype(np.float64)   # exact: w < 10^15
-    with np.errstate(all="ignore"):
-        val = np.where(e >= 0, mant * _P10[np.clip(e, 0, 22)], mant / _P10[np.clip(-e, 0, 22)])   # one rounding
-    return ok, pos[0], pos[1], np.where(neg, -val, val)
-
-
-def parse_contacts_text_host(data):
-    """The rule of the module docstring on bytes (bytes, bytearray, memoryview or a uint8 vector): (pos1 int32 [M], pos2 int32
-    [M], count float64 [M], slow_lines int64: the 0-based records that are SLOW, ascending).  Fast lines are parsed by the
-    walk the device kernel does, every other line by int(float(.)) and float(.); ValueError at the first malformed line."""
-    buf = _text_bytes(data)
-    start, end = _text_lines(buf)
-    fast, a, b, v = _text_fast(buf, start, end)
-    pos1, pos2, count = a.astype(np.int32), b.astype(np.int32), np.ascontiguousarray(v, dtype=np.float64)
-    slow = np.flatnonzero(~fast)
-    for r in slow.tolist():
-        rec = _slow_line(buf[start[r]:end[r]].tobytes())
-        if rec is None:
-            raise _malformed(r)
-        pos1[r], pos2[r], count[r] = rec
-    return pos1, pos2, count, slow.astype(np.int64)
-
-
-def windows_from_bed(path: str, chroms) -> Dict[str, np.ndarray]:
-    """{chrom: int32 window starts, ascending} of a windows bed (chrom<TAB>start<TAB>...): create_bin_dict of
-    data/7create_graph_new.py:14-47 -- the distinct start positions of every chromosome of `chroms`; a window's node index
-    is its rank.  Host only."""
-    starts = {c: set() for c in chroms}
-    with open(path, newline="") as f:
-        for row in csv.reader(f, delimiter="\t"):
-            if row and row[0] in starts:
-                starts[row[0]].add(int(row[1]))
-    return {c: np.array(sorted(s), dtype=np.int32) for c, s in starts.items()}
-
-
-_MAGIC = b"CGHIC01\0"
-
-
-def save_contacts_cache(path: str, c: HostContacts):
-    """Flat little-endian file: magic, int64 header [M, n_norms, resolution_bp, N or -1], pos1 int32[M], pos2 int32[M],
-    count fp64[M], per norm vector (name 16 bytes, int64 n_bins, fp64[n_bins]), window_start int32[N]."""
-    n = -1 if c.window_start is None else int(c.window_start.shape[0])
-    with open(path, "wb") as f:
-        f.write(_MAGIC)
-        f.write(np.array([c.M, len(c.norms), c.resolution_bp, n], dtype="<i8").tobytes())
-        f.write(np.ascontiguousarray(c.pos1, dtype="<i4").tobytes())
-        f.write(np.ascontiguousarray(c.pos2, dtype="<i4").tobytes())
-        f.write(np.ascontiguousarray(c.count, dtype="<f8").tobytes())
-        for name, v in c.norms.items():
-            b = name.encode()
-            if not 0 < len(b) <= 16:
-                raise ValueError("norm name %r does not fit 16 bytes" % name)
-            f.write(b.ljust(16, b"\0"))
-            f.write(np.array([v.shape[0]], dtype="<i8").tobytes())
-            f.write(np.ascontiguousarray(v, dtype="<f8").tobytes())
-        if n >= 0:
-            f.write(np.ascontiguousarray(c.window_start, dtype="<i4").tobytes())
-
-
-def load_contacts_cache(path: str) -> HostContacts:
-    def take(f, dtype, k):
-        raw = f.read(np.dtype(dtype).itemsize * k)
-        if len(raw) != np.dtype(dtype).itemsize * k:
-            raise ValueError("%s is truncated" % path)
-        return np.frombuffer(raw, dtype=dtype).copy()
-
-    with open(path, "rb") as f:
-        if f.read(8) != _MAGIC:
-            raise ValueError("%s is not a chromegcn contact cache" % path)
-        m, n_norms, res, n = take(f, "<i8", 4).tolist()
-        if m < 0 or n_norms < 0 or res < 1 or n < -1:
-            raise ValueError("%s is corrupt" % path)
-        pos1, pos2, count = take(f, "<i4", m), take(f, "<i4", m), take(f, "<f8", m)
-        norms = {}
-        for _ in range(n_norms):
-            name = f.read(16).rstrip(b"\0").decode()
-            norms[name] = take(f, "<f8", int(take(f, "<i8", 1)[0]))
-        ws = None if n < 0 else _windows(take(f, "<i4", n))
-    return HostContacts(pos1, pos2, count, norms, int(res), ws)
-
-
-# ----------------------------------------------------------------------------------------------
 # device build
 # ----------------------------------------------------------------------------------------------
-def _find_lf(mem, off: int) -> int:
-    """index of the first LF at or behind `off` in a byte memoryview, or its length - 1"""
-    step = 4096
-    for lo in range(off, len(mem), step):
-        k = bytes(mem[lo:lo + step]).find(b"\n")
-        if k >= 0:
-            return lo + k
-    return len(mem) - 1
-
-
-_staging = {}   # (device, chunk_bytes) -> the two pinned staging buffers of from_text (release_text_staging frees them)
-
-
-def release_text_staging():
-    """Free the two pinned staging buffers HicContacts.from_text keeps between calls (2 x chunk_bytes of page-locked host
-    memory, 64 MiB at the default; kept because pinning costs more than a chunk's copy, replaced when chunk_bytes or the
-    device changes)."""
-    _staging.clear()
-
-
-
-def _stage_text(src, is_path, n, text, chunk_bytes) -> float:
-    """Copy the n bytes of a file or a memoryview into the device buffer `text`, chunk by chunk through two pinned buffers:
-    chunk k + 1 is read while chunk k is on its way.  Returns the seconds spent reading."""
-    key = (text.device, chunk_bytes)
-    if key not in _staging:
-        _staging.clear()
-        _staging[key] = [torch.empty(chunk_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-    pinned, busy, t_read = _staging[key], [None, None], 0.0
-    f = open(src, "rb", buffering=0) if is_path else None
-    try:
-        off, k = 0, 0
-        while off < n:
-            if busy[k] is not None:
-                busy[k].synchronize()
-            want = min(chunk_bytes, n - off)
-            t0 = time.perf_counter()
-            if is_path:
-                got, view = 0, memoryview(pinned[k].numpy())
-                while got < want:
-                    r = f.readinto(view[got:want])
-                    if not r:
-                        raise ValueError("%s ended after %d of %d bytes" % (src, off + got, n))
-                    got += r
-            else:
-                pinned[k].numpy()[:want] = np.frombuffer(src[off:off + want], dtype=np.uint8)
-            t_read += time.perf_counter() - t0
-            text[off:off + want].copy_(pinned[k][:want], non_blocking=True)
-            busy[k] = torch.cuda.Event()
-            busy[k].record()
-            off, k = off + want, k ^ 1
-        for e in busy:
-            if e is not None:
-                e.synchronize()   # the buffers are shared with the next call
-    finally:
-        if f is not None:
-            f.close()
-    return t_read
+class _Route(NamedTuple):
+    """The top-K entry points of one (resolution_bp, window_bp): direct when the records are at the windows' resolution,
+    else the `_up` forms.  HicContacts._route makes it; _count and build_raw add "_dist" for a gap or an expected vector."""
+    suffix: str          # "" or "_up", behind cgcn_hic_count / cgcn_hic_build
+    workspace_fn: str    # cgcn_hic_workspace_bytes or cgcn_hic_up_workspace_bytes
+    extra: dict          # what the _up forms take besides: resolution_bp, window_bp, n_window_bins
+    what: str            # how the workspace's unsupported-shape error starts
 
 
 class HicContacts:
@@ -557,13 +262,11 @@ class HicContacts:
             raise ValueError("pos1, pos2 and count must be vectors of one length")
         self.M = int(self.pos1.numel())
         self._ws_host = self._ws_dev = None
-        self._survivors = None   # of the current window set, records at the windows' resolution
-        self._survivors_up = {}  # of the current window set, per (resolution_bp, window_bp)
+        self._survivors = {}     # of the current window set, per (resolution_bp, window_bp, min_distance_bp); direct: (None, None, gap)
         self._on_grid = set()    # the resolutions of which every position is known to be a multiple
         self._vectors = []   # (the caller's object, its device copy): a sweep passes the same vector again
         self._matrices = {}  # (resolution_bp, n_bins or None) -> hicnorm.DeviceContactMatrix
         self._norms = {}     # norm_vector's argument tuple -> (vector, info)
-        self._gap_survivors = {}   # of the current window set, per (min_distance_bp, resolution_bp, window_bp) with a gap > 0
         self._dist_sums = {}       # distance_sums' argument tuple -> (raw, act, host syncs)
         self._expected = {}        # expected_vector's argument tuple -> (vector, info)
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
@@ -580,7 +283,7 @@ class HicContacts:
     @classmethod
     def from_text(cls, path_or_bytes, device="cuda", chunk_bytes: int = 32 << 20, flag_capacity: int = 1 << 16,
                   timings: Optional[dict] = None) -> "HicContacts":
-        """The records of contact text (a path, or bytes / bytearray / memoryview) by the rule of the module docstring, parsed
+        """The records of contact text (a path, or bytes / bytearray / memoryview) by the rule of hictext's docstring, parsed
         on the device: the file is read in chunks of `chunk_bytes` through two pinned staging buffers into one device text
         buffer, cgcn_text_count sizes the arrays (one sync), cgcn_text_parse fills them and lists the lines that are not fast
         (a second call when more than `flag_capacity` are), those alone are parsed on the host and patched in, and the text
@@ -591,87 +294,7 @@ class HicContacts:
         `text_info` of the result: n_bytes, slow_lines (int64, the
         records parsed on the host), parse_calls.  timings: a dict that receives the seconds of every stage (with a device
         sync behind each)."""
-        from . import _lib
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("HicContacts.from_text needs a GPU; parse_contacts_text_host is the CPU path")
-        if int(chunk_bytes) < 1 or int(flag_capacity) < 0:
-            raise ValueError("chunk_bytes must be positive and flag_capacity non-negative")
-        is_path = isinstance(path_or_bytes, (str, os.PathLike))
-        mem = None if is_path else memoryview(path_or_bytes).cast("B")
-        n = os.path.getsize(path_or_bytes) if is_path else len(mem)
-        t = [time.perf_counter()]
-
-        def lap(name):
-            if timings is not None:
-                torch.cuda.synchronize(device)
-                t.append(time.perf_counter())
-                timings[name] = t[-1] - t[-2]
-
-        def line_at(src, off):   # the line that starts at byte `off`, without its terminator
-            if is_path:
-                src.seek(off)
-                raw = src.readline()
-            else:
-                stop = _find_lf(mem, off)
-                raw = bytes(mem[off:stop + 1])
-            return raw[:-2] if raw.endswith(b"\r\n") else raw[:-1] if raw.endswith(b"\n") else raw
-
-        with torch.cuda.device(device):
-            text = torch.empty(max(n, 1), dtype=torch.uint8, device=device)
-            t_read = _stage_text(path_or_bytes if is_path else mem, is_path, n, text, int(chunk_bytes))
-            if timings is not None:
-                torch.cuda.synchronize(device)
-                t.append(time.perf_counter())
-                timings["read"], timings["h2d"] = t_read, t[-1] - t[-2] - t_read
-            need = _lib.query("cgcn_text_workspace_bytes", n_bytes=n)
-            wsp = _lib._workspace(need, device, "contact text, %d bytes" % n)
-            out = torch.zeros(1, dtype=torch.int64, device=device)
-            _lib.call("cgcn_text_count", text=text, n_bytes=n, workspace=wsp, workspace_bytes=need, n_records=out)
-            m = int(out.item())
-            lap("count")
-            if m >= 2 ** 31:
-                raise ValueError("contact text: %d records, more than 2^31 - 1" % m)
-            pos1 = torch.empty(m, dtype=torch.int32, device=device)
-            pos2 = torch.empty(m, dtype=torch.int32, device=device)
-            count = torch.empty(m, dtype=torch.float64, device=device)
-            cap, calls = int(flag_capacity), 0
-            while True:
-                flags = torch.empty((max(cap, 1), 3), dtype=torch.int64, device=device)
-                totals = torch.zeros(2, dtype=torch.int64, device=device)
-                _lib.call("cgcn_text_parse", text=text, n_bytes=n, M=m, pos1_out=pos1, pos2_out=pos2, count_out=count,
-                          flags=flags, flag_capacity=cap, flag_totals=totals, workspace=wsp, workspace_bytes=need)
-                calls += 1
-                flagged = int(totals.sum().item())
-                if flagged <= cap:
-                    break
-                if calls == 2:
-                    raise RuntimeError("chromegcn_amd: cgcn_text_parse reported %d flagged lines for a capacity of %d" % (flagged, cap))
-                cap = flagged   # once more, with room for every one of them
-            lap("parse")
-            fl = flags[:flagged].cpu().numpy()
-            del text, flags, wsp
-            fl = fl[np.argsort(fl[:, 0], kind="stable")]
-            if flagged:
-                recs = []
-                src = open(path_or_bytes, "rb") if is_path else None
-                try:
-                    for r, off, _ in fl.tolist():   # ascending records: the first line that fails is the first malformed one
-                        rec = _slow_line(line_at(src, off))
-                        if rec is None:
-                            raise _malformed(r)
-                        recs.append(rec)
-                finally:
-                    if src is not None:
-                        src.close()
-                idx = torch.from_numpy(fl[:, 0].copy()).to(device)
-                pos1.index_copy_(0, idx, torch.tensor([x[0] for x in recs], dtype=torch.int32).to(device))
-                pos2.index_copy_(0, idx, torch.tensor([x[1] for x in recs], dtype=torch.int32).to(device))
-                count.index_copy_(0, idx, torch.tensor([x[2] for x in recs], dtype=torch.float64).to(device))
-            lap("patch")
-        c = cls(pos1, pos2, count, device)
-        c.text_info = {"n_bytes": int(n), "slow_lines": fl[:, 0].astype(np.int64), "parse_calls": calls}
-        return c
+        return parse_contacts_text(cls, path_or_bytes, device, chunk_bytes, flag_capacity, timings)
 
     def _up(self, a, dtype) -> torch.Tensor:
         t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
@@ -703,12 +326,12 @@ class HicContacts:
         v, info = self._norms[key]
         return (v, dict(info)) if return_info else v
 
-    def _named_norm(self, norm, resolution_bp, n_bins=None, norm_args=None):
-        """'KR' / 'VC' / 'SQRTVC' -> the vector computed from the records (HicNormError for a KR that did not converge)"""
+    def _named_norm(self, norm, resolution_bp, norm_args, **size):
+        """'KR' / 'VC' / 'SQRTVC' -> the vector computed from the records (HicNormError for a KR that did not converge);
+        size: n_bins, where the caller and not norm_args says it"""
         from . import hicnorm
-        v, info = self.norm_vector(norm, resolution_bp, n_bins=n_bins, return_info=True, **(norm_args or {}))
-        if not info.get("converged", True):
-            raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+        v, info = self.norm_vector(norm, resolution_bp, return_info=True, **size, **(norm_args or {}))
+        hicnorm._require_converged(info)
         return v
 
     @staticmethod
@@ -739,7 +362,7 @@ class HicContacts:
         key = None if nk is None else nk + (res, given)
         if key is not None and key in self._dist_sums:
             return self._dist_sums[key]
-        nv = self._named_norm(norm, res, given, norm_args) if isinstance(norm, str) else self._norm(norm)
+        nv = self._named_norm(norm, res, norm_args, n_bins=given) if isinstance(norm, str) else self._norm(norm)
         syncs = 0
         with torch.cuda.device(self.device):
             sizes = torch.zeros(2, dtype=torch.int64, device=self.device)
@@ -749,27 +372,23 @@ class HicContacts:
             if n is None and (res, None) in self._matrices:
                 n = self._matrices[(res, None)].n   # aggregate_contacts has checked the records and counted the bins
             if n is None:
-                need = _lib.query("cgcn_hicdist_workspace_bytes", M=self.M, n_bins=0)
-                wsp = _lib._workspace(need, self.device, "Hi-C distance sums, M=%d" % self.M)
+                wsp, need = _lib.workspace_for("cgcn_hicdist_workspace_bytes", self.device, "Hi-C distance sums, M=%d" % self.M,
+                                               M=self.M, n_bins=0)
                 _lib.call("cgcn_hicdist_sums", n_bins=0, workspace=wsp, workspace_bytes=need, raw_out=None, act_out=None,
                           sizes=sizes, **args)
                 flags, n = sizes.tolist()
                 syncs += 1
-                err = hicnorm._bad_records(flags)
-                if err is not None:
-                    raise err
+                hicnorm._bad_records(flags)
             raw = torch.zeros(n, dtype=torch.float64, device=self.device)
             act = torch.zeros(n, dtype=torch.float64, device=self.device)
             if n:
-                need = _lib.query("cgcn_hicdist_workspace_bytes", M=self.M, n_bins=n)
-                wsp = _lib._workspace(need, self.device, "Hi-C distance sums, M=%d n_bins=%d" % (self.M, n))
+                wsp, need = _lib.workspace_for("cgcn_hicdist_workspace_bytes", self.device,
+                                               "Hi-C distance sums, M=%d n_bins=%d" % (self.M, n), M=self.M, n_bins=n)
                 _lib.call("cgcn_hicdist_sums", n_bins=n, workspace=wsp, workspace_bytes=need, raw_out=raw, act_out=act, sizes=sizes,
                           **args)
                 flags, top = sizes.tolist()
                 syncs += 1
-                err = hicnorm._bad_records(flags)
-                if err is not None:
-                    raise err
+                hicnorm._bad_records(flags)
                 if flags & 4:
                     raise ValueError("n_bins=%d but the records reach bin %d" % (n, top - 1))
             elif self.M:
@@ -815,7 +434,7 @@ class HicContacts:
         ws = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
         if self._ws_host is None or not np.array_equal(ws, self._ws_host):
             self._ws_host, self._ws_dev = ws, torch.from_numpy(ws).to(self.device)
-            self._survivors, self._survivors_up, self._gap_survivors = None, {}, {}
+            self._survivors = {}
 
     def _window_bins(self, wbp) -> int:
         """the extent of the window bitmap (cgcn_hic_count_up's n_window_bins)"""
@@ -827,75 +446,47 @@ class HicContacts:
         window_bp: of the expanded file (cgcn_hic_count_up; one host sync per window set and window_bp).  min_distance_bp:
         of the records at least that far apart (the *_dist forms; one host sync per window set, window_bp and gap).  expected,
         expected_args: taken like the builders' and without effect: a value does not decide survival."""
-        from . import _lib
-        up = _upsample(resolution_bp, window_bp)
+        _upsample(resolution_bp, window_bp)
         gap = _gap(min_distance_bp)
         self._set_windows(window_start)
-        n = int(self._ws_host.size)
-        if gap:
-            return self._survivors_with_gap(n, up, resolution_bp, window_bp, gap)
-        if window_bp is None or int(window_bp) == int(resolution_bp):
-            if self._survivors is None:
-                with torch.cuda.device(self.device):
-                    need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=0, K=0)
-                    wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d" % self.M)
-                    out = torch.zeros(1, dtype=torch.int64, device=self.device)
-                    _lib.call("cgcn_hic_count", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
-                              workspace=wsp, workspace_bytes=need, n_survivors=out)
-                    self._survivors = int(out.item())
-            return self._survivors
-        res, wbp = int(resolution_bp), int(window_bp)
-        if (res, wbp) not in self._survivors_up:
-            with torch.cuda.device(self.device):
-                bins = self._window_bins(wbp)
-                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=0, K=0, resolution_bp=res, window_bp=wbp,
-                                  n_window_bins=bins)
-                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d" % (self.M, up))
-                out = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: survivors, [1]: positions off the grid
-                if res not in self._on_grid:   # read back with the count: still one sync
-                    out[1] = ((self.pos1 % res) != 0).sum() + ((self.pos2 % res) != 0).sum()
-                _lib.call("cgcn_hic_count_up", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
-                          resolution_bp=res, window_bp=wbp, n_window_bins=bins, workspace=wsp, workspace_bytes=need,
-                          n_survivors=out)
-                s, off = out.tolist()
-            if off:
-                raise ValueError("pos1 / pos2 hold %d positions that are no multiple of resolution_bp=%d" % (off, res))
-            self._on_grid.add(res)
-            self._survivors_up[(res, wbp)] = int(s)
-        return self._survivors_up[(res, wbp)]
+        return self._count(self._route(resolution_bp, window_bp), gap)
 
-    def _survivors_with_gap(self, n, up, resolution_bp, window_bp, gap) -> int:
+    def _route(self, resolution_bp, window_bp) -> _Route:
+        """which of the top-K entry points serve records of resolution_bp and windows of window_bp (of the current window set)"""
+        if window_bp is None or int(window_bp) == int(resolution_bp):
+            return _Route("", "cgcn_hic_workspace_bytes", {}, "Hi-C build, M=%d" % self.M)
+        res, wbp = int(resolution_bp), int(window_bp)
+        return _Route("_up", "cgcn_hic_up_workspace_bytes",
+                      dict(resolution_bp=res, window_bp=wbp, n_window_bins=self._window_bins(wbp)),
+                      "Hi-C build, M=%d up=%d" % (self.M, res // wbp))
+
+    def _count(self, route: _Route, gap: int) -> int:
+        """the survivors of the current window set on `route` with the minimum gap `gap`: counted and read back once, then kept"""
         from . import _lib
-        direct = window_bp is None or int(window_bp) == int(resolution_bp)
-        key = (gap, None, None) if direct else (gap, int(resolution_bp), int(window_bp))
-        if key in self._gap_survivors:
-            return self._gap_survivors[key]
-        with torch.cuda.device(self.device):
-            if direct:
-                need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=0, K=0)
-                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d" % self.M)
-                out = torch.zeros(1, dtype=torch.int64, device=self.device)
-                _lib.call("cgcn_hic_count_dist", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
-                          min_distance_bp=gap, workspace=wsp, workspace_bytes=need, n_survivors=out)
-                s = int(out.item())
-            else:
-                res, wbp = key[1], key[2]
-                bins = self._window_bins(wbp)
-                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=0, K=0, resolution_bp=res, window_bp=wbp,
-                                  n_window_bins=bins)
-                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d" % (self.M, up))
-                out = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: survivors, [1]: positions off the grid
-                if res not in self._on_grid:   # read back with the count: still one sync
+        res = route.extra.get("resolution_bp")
+        key = (res, route.extra.get("window_bp"), gap)
+        if key not in self._survivors:
+            n = int(self._ws_host.size)
+            dist = dict(min_distance_bp=gap) if gap else {}
+            with torch.cuda.device(self.device):
+                wsp, need = _lib.workspace_for(route.workspace_fn, self.device, route.what, M=self.M, N=n, capacity=0, K=0,
+                                               **route.extra)
+                # [0]: survivors; the up forms add [1]: positions off the grid
+                out = torch.zeros(2 if route.suffix else 1, dtype=torch.int64, device=self.device)
+                if route.suffix and res not in self._on_grid:   # read back with the count: still one sync
                     out[1] = ((self.pos1 % res) != 0).sum() + ((self.pos2 % res) != 0).sum()
-                _lib.call("cgcn_hic_count_up_dist", M=self.M, pos1=self.pos1, pos2=self.pos2, window_start=self._ws_dev, N=n,
-                          resolution_bp=res, window_bp=wbp, n_window_bins=bins, min_distance_bp=gap, workspace=wsp,
-                          workspace_bytes=need, n_survivors=out)
-                s, off = out.tolist()
-                if off:
-                    raise ValueError("pos1 / pos2 hold %d positions that are no multiple of resolution_bp=%d" % (off, res))
-                self._on_grid.add(res)
-        self._gap_survivors[key] = int(s)
-        return self._gap_survivors[key]
+                _lib.call("cgcn_hic_count" + route.suffix + ("_dist" if gap else ""), M=self.M, pos1=self.pos1, pos2=self.pos2,
+                          window_start=self._ws_dev, N=n, workspace=wsp, workspace_bytes=need, n_survivors=out, **route.extra,
+                          **dist)
+                if route.suffix:
+                    s, off = out.tolist()
+                    if off:
+                        raise ValueError("pos1 / pos2 hold %d positions that are no multiple of resolution_bp=%d" % (off, res))
+                    self._on_grid.add(res)
+                else:
+                    s = out.item()
+            self._survivors[key] = int(s)
+        return self._survivors[key]
 
     def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None, min_distance_bp=0,
                   expected=None, expected_args=None):
@@ -908,21 +499,17 @@ class HicContacts:
         from . import _lib
         k = _budget(hic_edges)
         gap = _gap(min_distance_bp)
-        if isinstance(expected, str):
-            if expected != "auto":
-                raise ValueError("expected=%r is none of None, a vector, 'auto'" % (expected,))
+        if _auto_expected(expected):
             expected = self.expected_vector(norm, resolution_bp, norm_args=norm_args, **(expected_args or {}))
         if isinstance(norm, str):
             from . import hicnorm
-            norm, info = self.norm_vector(norm, resolution_bp, return_info=True, **(norm_args or {}))
-            if not info.get("converged", True):
-                raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+            norm = self._named_norm(norm, resolution_bp, norm_args)
             ws_last = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
             norm = hicnorm.pad_vector(norm, int(ws_last[-1]) // int(resolution_bp) + 1 if ws_last.size else 0)
-        up = _upsample(resolution_bp, window_bp)
-        direct = window_bp is None or int(window_bp) == int(resolution_bp)
-        cap = (self.survivors(window_start, min_distance_bp=gap) if direct
-               else self.survivors(window_start, resolution_bp, window_bp, min_distance_bp=gap))
+        _upsample(resolution_bp, window_bp)
+        self._set_windows(window_start)
+        route = self._route(resolution_bp, window_bp)
+        cap = self._count(route, gap)
         ws, n = self._ws_dev, int(self._ws_host.size)
         nv = self._norm(norm)
         if nv is not None:
@@ -939,23 +526,14 @@ class HicContacts:
             rowptr = torch.empty(n + 1, dtype=torch.int32, device=self.device)
             col = torch.empty(max(2 * min(k, cap), 1), dtype=torch.int32, device=self.device)
             sizes = torch.zeros(2, dtype=torch.int64, device=self.device)   # [0]: nnz (its low int32 half), [1]: survivors
-            if direct:
-                need = _lib.query("cgcn_hic_workspace_bytes", M=self.M, N=n, capacity=cap, K=k)
-                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d capacity=%d K=%d" % (self.M, cap, k))
-                _lib.call("cgcn_hic_build_dist" if dist else "cgcn_hic_build", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
-                          n_bins=0 if nv is None else int(nv.numel()), resolution_bp=int(resolution_bp), window_start=ws, N=n,
-                          K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr, col_out=col,
-                          nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8, **dist)
-            else:
-                res, wbp = int(resolution_bp), int(window_bp)
-                bins = self._window_bins(wbp)
-                need = _lib.query("cgcn_hic_up_workspace_bytes", M=self.M, N=n, capacity=cap, K=k, resolution_bp=res,
-                                  window_bp=wbp, n_window_bins=bins)
-                wsp = _lib._workspace(need, self.device, "Hi-C build, M=%d up=%d capacity=%d K=%d" % (self.M, up, cap, k))
-                _lib.call("cgcn_hic_build_up_dist" if dist else "cgcn_hic_build_up", M=self.M, pos1=self.pos1, pos2=self.pos2, count=self.count, norm=nv,
-                          n_bins=0 if nv is None else int(nv.numel()), resolution_bp=res, window_bp=wbp, n_window_bins=bins,
-                          window_start=ws, N=n, K=k, capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr,
-                          col_out=col, nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8, **dist)
+            wsp, need = _lib.workspace_for(route.workspace_fn, self.device, "%s capacity=%d K=%d" % (route.what, cap, k),
+                                           M=self.M, N=n, capacity=cap, K=k, **route.extra)
+            # every build takes resolution_bp (the norm bins); the _up forms have it in route.extra already
+            _lib.call("cgcn_hic_build" + route.suffix + ("_dist" if dist else ""), M=self.M, pos1=self.pos1, pos2=self.pos2,
+                      count=self.count, norm=nv, n_bins=0 if nv is None else int(nv.numel()), window_start=ws, N=n, K=k,
+                      capacity=cap, workspace=wsp, workspace_bytes=need, rowptr_out=rowptr, col_out=col,
+                      nnz_out=sizes.data_ptr(), n_survivors=sizes.data_ptr() + 8,
+                      **{"resolution_bp": int(resolution_bp), **route.extra}, **dist)
         return rowptr, col, sizes
 
     def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
@@ -991,10 +569,6 @@ def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_ed
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
     """HicContacts.from_text: contact text in, device-resident records out"""
     return HicContacts.from_text(path_or_bytes, device=device, **kw)
-
-
-def contact_cache_path(root: str, chrom: str) -> str:
-    return os.path.join(root, "%s.cghic" % chrom)
 
 
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",

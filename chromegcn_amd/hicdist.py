@@ -42,8 +42,7 @@ def _resolve_norm_host(pos1, pos2, count, norm, resolution_bp, n_bins, norm_args
     if not isinstance(norm, str):
         return norm
     v, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, n_bins, **(norm_args or {}))
-    if not info.get("converged", True):
-        raise hicnorm.HicNormError("KR did not converge: %r" % (info,), info)
+    hicnorm._require_converged(info)
     return v
 
 
@@ -56,9 +55,7 @@ def distance_sums_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm
     c = np.asarray(count, dtype=np.float64).ravel()
     if not (p1.shape == p2.shape == c.shape):
         raise ValueError("pos1, pos2 and count must be vectors of one length")
-    err = hicnorm._bad_records((0 if np.all(np.isfinite(c) & (c >= 0)) else 1) | (2 if p1.size and min(p1.min(), p2.min()) < 0 else 0))
-    if err is not None:
-        raise err
+    hicnorm._bad_records((0 if np.all(np.isfinite(c) & (c >= 0)) else 1) | (2 if p1.size and min(p1.min(), p2.min()) < 0 else 0))
     i, j = p1 // res, p2 // res
     top = int(max(i.max(), j.max())) + 1 if i.size else 0
     n = top if n_bins is None else int(n_bins)

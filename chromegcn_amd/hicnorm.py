@@ -77,10 +77,14 @@ def _kind(kind) -> str:
 
 def _bad_records(flags: int):
     if flags & 1:
-        return ValueError("contact counts must be finite and non-negative")
+        raise ValueError("contact counts must be finite and non-negative")
     if flags & 2:
-        return ValueError("contact positions must be non-negative")
-    return None
+        raise ValueError("contact positions must be non-negative")
+
+
+def _require_converged(info):
+    if not info.get("converged", True):
+        raise HicNormError("KR did not converge: %r" % (info,), info)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -95,9 +99,7 @@ def contact_matrix_host(pos1, pos2, count, resolution_bp, n_bins=None) -> sp.csr
     c = np.asarray(count, dtype=np.float64).ravel()
     if not (p1.shape == p2.shape == c.shape):
         raise ValueError("pos1, pos2 and count must be vectors of one length")
-    err = _bad_records((0 if np.all(np.isfinite(c) & (c >= 0)) else 1) | (2 if p1.size and min(p1.min(), p2.min()) < 0 else 0))
-    if err is not None:
-        raise err
+    _bad_records((0 if np.all(np.isfinite(c) & (c >= 0)) else 1) | (2 if p1.size and min(p1.min(), p2.min()) < 0 else 0))
     i, j = p1 // res, p2 // res
     top = int(max(i.max(), j.max())) + 1 if i.size else 0
     n = top if n_bins is None else int(n_bins)
@@ -279,15 +281,13 @@ def aggregate_contacts(pos1, pos2, count, resolution_bp, n_bins=None) -> DeviceC
     if given < 0:
         raise ValueError("n_bins must not be negative")
     with torch.cuda.device(dev):
-        need = _lib.query("cgcn_hicnorm_workspace_bytes", M=m, n_bins=0)   # the bins are counted first: n_bins = 0
-        wsp = _lib._workspace(need, dev, "Hi-C norm aggregation, M=%d" % m)
+        # the bins are counted first: n_bins = 0
+        wsp, need = _lib.workspace_for("cgcn_hicnorm_workspace_bytes", dev, "Hi-C norm aggregation, M=%d" % m, M=m, n_bins=0)
         sizes = torch.zeros(4, dtype=torch.int64, device=dev)
         _lib.call("cgcn_hicnorm_count", M=m, pos1=pos1, pos2=pos2, count=count, resolution_bp=res, n_bins=0, workspace=wsp,
                   workspace_bytes=need, sizes=sizes)
         entries, flags, top, _ = sizes.tolist()
-        err = _bad_records(flags)
-        if err is not None:
-            raise err
+        _bad_records(flags)
         n = top if n_bins is None else given
         if n < top:
             raise ValueError("n_bins=%d but the records reach bin %d" % (n, top - 1))

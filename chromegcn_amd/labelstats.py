@@ -219,8 +219,8 @@ class _Accumulator:
             raise RuntimeError("label_stats: every label matrix must be [n, %d] on %s" % (self.C, self.dev))
         acc = int(self.calls > 0)
         with torch.cuda.device(self.dev):
-            ws_bytes = _lib.query("cgcn_labelstats_workspace_bytes", n=n, C=C)
-            ws = _lib._workspace(ws_bytes, self.dev, "label statistics, n=%d C=%d" % (n, C))
+            ws, ws_bytes = _lib.workspace_for("cgcn_labelstats_workspace_bytes", self.dev,
+                                              "label statistics, n=%d C=%d" % (n, C), n=n, C=C)
             cnt, hist, co = self.window
             _lib.call("cgcn_labelstats_windows", n=n, C=C, targets=tg, workspace=ws, workspace_bytes=ws_bytes, label_count=cnt,
                       labels_hist=hist, cooccurrence=co, accumulate=acc)

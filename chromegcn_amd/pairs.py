@@ -29,7 +29,6 @@ without its third column, which is |pos2 - pos1|.  Stage B, contact records: per
 unordered bin pair, pos1 = the lower binned position, pos2 = the higher, count = the number of kept pairs (fp64), sorted by
 (pos1, pos2).  The reference stops at stage A: it never aggregates pairs into counts, and its third column is the distance, not
 a count.  Stage B is this project's definition.  It is the one Juicer's `dump observed` would give for the same pairs."""
-import os
 import time
 from dataclasses import dataclass, field
 from typing import Dict, Optional, Sequence
@@ -38,6 +37,7 @@ import numpy as np
 import torch
 
 from . import hic
+from ._textio import TextSource, _text_bytes, _text_lines, lap_adder, staging
 
 DEFAULT_CHROMS = tuple(["chr%d" % k for k in range(1, 23)] + ["chrX"])
 LINE_MAX, NAME_MAX, MAX_CHROMS = 256, 15, 64   # include/chromegcn.h: CGCN_PAIRS_LINE_MAX, _NAME_MAX, _MAX_CHROMS
@@ -220,7 +220,7 @@ def bin_read_pairs_host(data, chroms: Sequence = DEFAULT_CHROMS, resolution_bp: 
     names = _check_rule(chroms, resolution_bp, binning)
     res, min_diff = int(resolution_bp), int(min_diff)
     index = {nm: k for k, nm in enumerate(names)}
-    buf = hic._text_bytes(data)
+    buf = _text_bytes(data)
     totals = dict.fromkeys(TOTALS, 0)
     out_c, out_1, out_2, slow_lines = [], [], [], []
     off, line0 = 0, 0
@@ -234,7 +234,7 @@ def bin_read_pairs_host(data, chroms: Sequence = DEFAULT_CHROMS, resolution_bp: 
                 more = np.flatnonzero(buf[stop:] == 10)
                 stop = stop + int(more[0]) + 1 if more.size else buf.size
         blk = buf[off:stop]
-        start, end = hic._text_lines(blk)
+        start, end = _text_lines(blk)
         fast, fate, chrom, p1, p2 = _fast_lines(blk, start, end, names, res, binning, min_diff)
         fast = fast | (end == start)
         for r in np.flatnonzero(~fast if vectorised else end > start).tolist():
@@ -277,40 +277,16 @@ def pairs_to_contacts_host(pos1, pos2, resolution_bp: int):
 # device path
 # ----------------------------------------------------------------------------------------------
 class _LineChunks:
-    """The bytes of a file or a memoryview as chunks of whole lines of at most `chunk_bytes`, staged in turn in the two pinned
-    buffers of hic._staging (a line longer than that travels alone, in a buffer of its own).  next() -> (uint8 host tensor,
+    """The bytes of a TextSource as chunks of whole lines of at most `chunk_bytes`, staged in turn in the two pinned buffers
+    of _textio.staging (a line longer than that travels alone, in a buffer of its own).  next() -> (uint8 host tensor,
     byte offset of its first byte in the source) or None."""
 
-    def __init__(self, src, is_path, n, chunk_bytes, device):
-        key = (device, chunk_bytes)
-        if key not in hic._staging:
-            hic._staging.clear()
-            hic._staging[key] = [torch.empty(chunk_bytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-        self.pinned, self.k = hic._staging[key], 0
-        self.src, self.is_path, self.n, self.chunk = src, is_path, n, chunk_bytes
-        self.f = open(src, "rb", buffering=0) if is_path else None
-        self.off = 0          # bytes taken from the source
+    def __init__(self, src: TextSource, chunk_bytes, device):
+        self.pinned, self.k = staging(device, chunk_bytes), 0
+        self.src, self.chunk = src, chunk_bytes
         self.base = 0         # source offset of the next chunk's first byte
         self.carry = b""      # the piece behind the last LF of the chunk before
         self.seconds = 0.0    # spent reading
-
-    def close(self):
-        if self.f is not None:
-            self.f.close()
-            self.f = None
-
-    def _fill(self, view, lo, want):
-        """source bytes [off, off + want) into view[lo:]"""
-        if self.is_path:
-            got = 0
-            while got < want:
-                r = self.f.readinto(view[lo + got:lo + want])
-                if not r:
-                    raise ValueError("%s ended after %d of %d bytes" % (self.src, self.off + got, self.n))
-                got += r
-        else:
-            view[lo:lo + want] = self.src[self.off:self.off + want]
-        self.off += want
 
     @staticmethod
     def _last_lf(view, total):
@@ -330,22 +306,23 @@ class _LineChunks:
         view = memoryview(buf.numpy())
         have = len(self.carry)
         view[:have] = self.carry
-        want = min(self.chunk - have, self.n - self.off)
-        self._fill(view, have, want)
+        src = self.src
+        want = min(self.chunk - have, src.n - src.off)
+        src.read_into(view[have:], want)
         total = have + want
         if total == 0:
             return None
         out = buf
-        if self.off == self.n:
+        if src.off == src.n:
             cut = total
         else:
             cut = self._last_lf(view, total) + 1
             if cut == 0:   # a line longer than a chunk: it travels alone, up to and with its LF
                 big = bytearray(view[:total])
-                while self.off < self.n:
-                    want = min(self.chunk, self.n - self.off)
+                while src.off < src.n:
+                    want = min(self.chunk, src.n - src.off)
                     piece = bytearray(want)
-                    self._fill(memoryview(piece), 0, want)
+                    src.read_into(memoryview(piece), want)
                     k = piece.find(b"\n")
                     if k >= 0:
                         big += piece[:k + 1]
@@ -382,7 +359,7 @@ class ReadPairs:
                   min_diff: int = 10, device="cuda", chunk_bytes: int = 32 << 20, flag_capacity: int = 1 << 16,
                   timings: Optional[dict] = None) -> "ReadPairs":
         """Stage A of a path, or of bytes / bytearray / memoryview, by the rule of the module docstring.  The text goes
-        through the pinned staging buffers of chromegcn_amd.hic in chunks of whole lines of at most `chunk_bytes`; one chunk of
+        through the pinned staging buffers HicContacts.from_text uses in chunks of whole lines of at most `chunk_bytes`; one chunk of
         text is resident at a time and the keys (8 bytes per kept pair) are what stays, so a 30 GB file does not need 30 GB
         of device memory.  Per chunk: copy, cgcn_pairs_parse (a second call when more than `flag_capacity` lines of the chunk
         are not fast), then the next chunk is read while the device works, and one read-back of the running totals.  The
@@ -397,15 +374,10 @@ class ReadPairs:
         if chunk_bytes < 1 or int(flag_capacity) < 0:
             raise ValueError("chunk_bytes must be positive and flag_capacity non-negative")
         index = {nm: k for k, nm in enumerate(names)}
-        is_path = isinstance(path_or_bytes, (str, os.PathLike))
-        mem = None if is_path else memoryview(path_or_bytes).cast("B")
-        n = os.path.getsize(path_or_bytes) if is_path else len(mem)
+        src = TextSource(path_or_bytes)
+        n = src.n
         tm = dict.fromkeys(("read", "h2d", "parse", "patch"), 0.0)
-
-        def lap(name, t0):
-            if timings is not None:
-                torch.cuda.synchronize(device)
-                tm[name] += time.perf_counter() - t0
+        lap = lap_adder(tm, timings is not None, device)
 
         table = np.zeros((len(names), 16), np.uint8)
         for k, nm in enumerate(names):
@@ -414,23 +386,13 @@ class ReadPairs:
         host_totals = dict.fromkeys(TOTALS, 0)     # the fates of the lines the host parsed
         slow_lines, slow_rank, slow_key = [], [], []
         calls = 0
-        chunks = _LineChunks(path_or_bytes if is_path else mem, is_path, n, chunk_bytes, device)
-        src = open(path_or_bytes, "rb") if is_path else None
-
-        def line_at(off):   # the line that starts at byte `off`, without its terminator
-            if is_path:
-                src.seek(off)
-                raw = src.readline()
-            else:
-                raw = bytes(mem[off:hic._find_lf(mem, off) + 1]) if off < n else b""
-            return raw[:-2] if raw.endswith(b"\r\n") else raw[:-1] if raw.endswith(b"\n") else raw
-
+        chunks = _LineChunks(src, chunk_bytes, device)
         try:
             with torch.cuda.device(device):
                 names_dev = torch.from_numpy(table).to(device)
                 text = torch.empty(chunk_bytes, dtype=torch.uint8, device=device)
-                need = _lib.query("cgcn_pairs_parse_workspace_bytes", n_bytes=chunk_bytes)
-                wsp = _lib._workspace(need, device, "read pairs, chunks of %d bytes" % chunk_bytes)
+                wsp, need = _lib.workspace_for("cgcn_pairs_parse_workspace_bytes", device,
+                                               "read pairs, chunks of %d bytes" % chunk_bytes, n_bytes=chunk_bytes)
                 totals = torch.zeros((2, 8), dtype=torch.int64, device=device)   # running | this chunk's
                 before = np.zeros(8, np.int64)
                 keys = torch.empty(max(1, min(n, chunk_bytes) // 9 + 1), dtype=torch.int64, device=device)
@@ -443,8 +405,8 @@ class ReadPairs:
                     tx, ws_c, need_c = text, wsp, need
                     if nb > chunk_bytes:            # a single line longer than a chunk
                         tx = torch.empty(nb, dtype=torch.uint8, device=device)
-                        need_c = _lib.query("cgcn_pairs_parse_workspace_bytes", n_bytes=nb)
-                        ws_c = _lib._workspace(need_c, device, "read pairs, a line of %d bytes" % nb)
+                        ws_c, need_c = _lib.workspace_for("cgcn_pairs_parse_workspace_bytes", device,
+                                                          "read pairs, a line of %d bytes" % nb, n_bytes=nb)
                     tx[:nb].copy_(chunk, non_blocking=True)
                     lap("h2d", t0)
                     kept0 = int(before[2])
@@ -485,7 +447,7 @@ class ReadPairs:
                         fl = flags[:flagged].cpu().numpy()
                         fl = fl[np.argsort(fl[:, 0], kind="stable")]
                         for line, off, _, rank in fl.tolist():   # ascending lines: the first that fails is the first malformed
-                            what, c, a, b = _host_line(line_at(off), index, res, binning, min_diff)
+                            what, c, a, b = _host_line(src.line_at(off), index, res, binning, min_diff)
                             if what == _BAD:
                                 raise _malformed(line)
                             host_totals[what] += 1
@@ -512,9 +474,7 @@ class ReadPairs:
                 per = torch.bincount(keys >> 57, minlength=len(names)).cpu().numpy() if keys.numel() else np.zeros(len(names), np.int64)
                 lap("patch", t0)
         finally:
-            chunks.close()
-            if src is not None:
-                src.close()
+            src.close()
         tm["read"] = chunks.seconds
         totals_all = {k: int(before[i]) + host_totals[k] for i, k in enumerate(TOTALS)}
         if timings is not None:
@@ -541,8 +501,7 @@ class ReadPairs:
             n, nc = int(self.keys.numel()), len(self.chroms)
             t0 = time.perf_counter()
             with torch.cuda.device(self.device):
-                need = _lib.query("cgcn_pairs_reduce_workspace_bytes", n_keys=n)
-                wsp = _lib._workspace(need, self.device, "read pairs, %d keys" % n)
+                wsp, need = _lib.workspace_for("cgcn_pairs_reduce_workspace_bytes", self.device, "read pairs, %d keys" % n, n_keys=n)
                 pos1 = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
                 pos2 = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
                 count = torch.empty(max(n, 1), dtype=torch.float64, device=self.device)

@@ -85,8 +85,8 @@ def threshold_counts(probs: torch.Tensor, targets: torch.Tensor, thresholds) -> 
     tpsum = torch.empty(T, K, device=dev, dtype=torch.int64)
     for t0 in range(0, T, MAX_T):
         t1 = min(T, t0 + MAX_T)
-        ws_bytes = _lib.query("cgcn_threshold_workspace_bytes", n=n, C=C, T=t1 - t0)
-        ws = _lib._workspace(ws_bytes, dev, "thresholded counts, n=%d C=%d T=%d" % (n, C, t1 - t0))
+        ws, ws_bytes = _lib.workspace_for("cgcn_threshold_workspace_bytes", dev,
+                                          "thresholded counts, n=%d C=%d T=%d" % (n, C, t1 - t0), n=n, C=C, T=t1 - t0)
         _lib.call("cgcn_threshold_counts", n=n, C=C, T=t1 - t0, probs=probs, targets=targets, thresholds=thr[t0:t1],
                   pos=pos, tp=tp[t0:t1], pp=pp[t0:t1], exact=exact[t0:t1], rows=rows[t0:t1], tpsum=tpsum[t0:t1],
                   workspace=ws, workspace_bytes=ws_bytes)

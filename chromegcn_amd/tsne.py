@@ -49,7 +49,7 @@ def _check_square(m: torch.Tensor, name: str) -> int:
 
 def workspace(n: int, device) -> torch.Tensor:
     """the uint8 workspace every cgcn_tsne_* call of one point count shares"""
-    return _lib._workspace(_lib.query("cgcn_tsne_workspace_bytes", n=n), device, "t-SNE, n=%d" % n)
+    return _lib.workspace_for("cgcn_tsne_workspace_bytes", device, "t-SNE, n=%d" % n, n=n)[0]
 
 
 def sqdist(x: torch.Tensor) -> torch.Tensor:
