@@ -684,15 +684,12 @@ __global__ __launch_bounds__(512) void k_head_bwd(int n, int S, int C, const flo
       }
     }
     __syncthreads();
-#ifndef HB_SKIP_DBO
     if (threadIdx.x < CP) {
       float sacc = 0.f;
 #pragma unroll 8
       for (int row = 0; row < TR; ++row) sacc += Pt[row * LDP + threadIdx.x];
       dbo += sacc;
     }
-#endif
-#ifndef HB_SKIP_DW
     // ---- dW_out += Pt^T Yt   (K = TR rows)
 #pragma unroll 2
     for (int kk = 0; kk < TR / 4; ++kk) {
@@ -709,14 +706,12 @@ __global__ __launch_bounds__(512) void k_head_bwd(int n, int S, int C, const flo
         }
       }
     }
-#endif
     // ---- dym tile = Pt W_out   (M = TR rows, K = labels, N = D)
     f32x4 accY[2][JBW];
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
       for (int jb = 0; jb < JBW; ++jb) accY[mb][jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#ifndef HB_SKIP_DYM
     if (PREB) {
 #pragma unroll
       for (int kk = 0; kk < CBMAX * 4; ++kk) {
@@ -746,7 +741,6 @@ __global__ __launch_bounds__(512) void k_head_bwd(int n, int S, int C, const flo
         }
       }
     }
-#endif
     __syncthreads();  // all reads of Yt / Pt done
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb)
@@ -792,7 +786,6 @@ __global__ __launch_bounds__(512) void k_head_bwd(int n, int S, int C, const flo
 
   // ---- partials
   float* P = part + (size_t)blockIdx.x * PS;
-#ifndef HB_SKIP_PART
 #pragma unroll
   for (int ib = 0; ib < CBMAX; ++ib)
 #pragma unroll
@@ -800,7 +793,6 @@ __global__ __launch_bounds__(512) void k_head_bwd(int n, int S, int C, const flo
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (c0 + ib * 16 < CPT) P[(size_t)(c0 + ib * 16 + q * 4 + e) * D + (wave * JBW + jb) * 16 + r] = accW[ib][jb][e];
-#endif
   if (threadIdx.x < CP && c0 + (int)threadIdx.x < CPT) P[CPT * D + c0 + threadIdx.x] = dbo;
   if (last) head_stats_partial<D, NW, TR * LDY>(Yt, (double*)(P + CPT * D + CPT), sdy, sdyx, wave, lane);
 }
@@ -827,11 +819,8 @@ __device__ unsigned long long hf_stamps[8 * 16];
 #define HF_STAMP(i)
 #endif
 
-#ifndef HF_LOWREG
-#define HF_LOWREG 0   // experiment: no register-resident W_out fragments / no tile prefetch, <= 128 VGPRs, two workgroups per CU
-#endif
 template <int D, int CBMAX>
-__global__ __launch_bounds__(512, HF_LOWREG ? 4 : 1) void k_head_fused(int n, int S, int C, const float* __restrict__ X,
+__global__ __launch_bounds__(512, 1) void k_head_fused(int n, int S, int C, const float* __restrict__ X,
                                                     const float* __restrict__ bn_w, const float* __restrict__ bn_b,
                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
                                                     const float* __restrict__ Wout, const float* __restrict__ bout,
@@ -845,7 +834,7 @@ __global__ __launch_bounds__(512, HF_LOWREG ? 4 : 1) void k_head_fused(int n, in
   constexpr int LDP = CP + ((CP & 16) ? 2 : 18);
   constexpr int LDY = D + 16;
   constexpr int JBW = D / 128;
-  constexpr bool PRE = (D == 128) && !HF_LOWREG;
+  constexpr bool PRE = (D == 128);
   __shared__ __attribute__((aligned(16))) float Pt[TR * LDP];
   __shared__ __attribute__((aligned(16))) float Yt[TR * LDY];
   __shared__ float lsum[NW];
@@ -921,7 +910,7 @@ __global__ __launch_bounds__(512, HF_LOWREG ? 4 : 1) void k_head_fused(int n, in
   // All global loads of a tile -- this wave's X rows, the targets / bias of this lane's logits -- are issued together.
   // Workgroups that walk several tiles (large chromosomes) issue the NEXT tile's loads right after the current tile's
   // operands are in LDS, so they are in flight during the three MFMA phases; the current tile keeps its copy.
-  constexpr bool PF = (CBMAX == 8) && !HF_LOWREG;  // the 256-label variant has no registers to spare for a second tile
+  constexpr bool PF = (CBMAX == 8);  // the 256-label variant has no registers to spare for a second tile
   float xv[RPW][2][EPL], xv_n[PF ? RPW : 1][2][EPL];
   float tgv[NCBW][2][4], tgv_n[PF ? NCBW : 1][2][4], bjv[NCBW];
 #pragma unroll
@@ -1214,17 +1203,10 @@ __global__ __launch_bounds__(512, HF_LOWREG ? 4 : 1) void k_head_fused(int n, in
 // accumulators -- lives in the SAME 40 registers).  LDS: W_out 72 KB + two Yt + two Pt tiles 73 KB.
 // Same partial records, label passes and results as k_head_fused.
 // ------------------------------------------------------------------------------------------
-#if (defined(HRSX_NOBACC) || defined(HRSX_NOSTAGE) || defined(HRSX_NOTICKET)) && !defined(CGCN_EXPERIMENT_BUILD)
-#error "HRSX_* are decomposition switches (garbage results): build a variant with -DCGCN_EXPERIMENT_BUILD (tools/mkvariant.py), never the shipped library"
-#endif
 #ifndef HEAD_RS
-#define HEAD_RS 1   // 0: the 8-wave k_head_fused at d = 128 as well (A/B builds)
-#endif
-#ifndef HEAD_NT_PROBS
-#define HEAD_NT_PROBS 0   // non-temporal probs stores in k_head_fused_rs (A/B: profiles/r05_head_experiments.txt)
-#endif
-#ifndef HEAD_RS_PRIO
-#define HEAD_RS_PRIO 0   // wave priority inside the matrix sub-phases (measured: 2 is neutral for the head, -2 % for the row-local kernel)
+#define HEAD_RS 1   // 0: the 8-wave k_head_fused at d = 128 as well (A/B builds).  Still a switch, and k_head_fused<128, 8> still
+                    // instantiated: without that instance the compiler inlines the helpers it shares with the d = 128 kernels
+                    // in another order, and 25 of them come out with other instruction streams (tools/isa_diff.py)
 #endif
 #ifdef RS_TIMING  // tuning build only (tools/khead_train.py --stamps): phase timestamps of period RS_STAMP_K of a few workgroups
 __device__ unsigned long long rs_stamps[8 * 2 * 8];
@@ -1303,9 +1285,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
   // period 1, read by both roles right behind the "Wl complete" barrier)
   float* const stash = Pt[1];
   static_assert(TR * LDP >= 6 * D, "the stash fits a P tile");
-#ifndef HRSX_NOSTAGE   // (decomposition build)
   if (sa.acc) head_stat_stage<D>(sa, n, S, stash, 1024);
-#endif
   // The two roles run SEPARATE loops (the register allocator then sees each role's state on its own path) that execute
   // the same number of workgroup barriers: one before and one after the loop, three per period.
   // In every role phase the lane-derived indices are re-derived from an opaque copy of the lane id: addresses kept live
@@ -1401,7 +1381,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
         if (k + 1 < mt) load_rows(tile + G);   // the rows were consumed in S1
         if (own < NB) {
           OPAQUE_LANE(r, q, lq);
-          __builtin_amdgcn_s_setprio(HEAD_RS_PRIO);   // matrix sub-phase: issue ahead of the other team's vector work
+          __builtin_amdgcn_s_setprio(0);   // matrix sub-phase (a raised priority here was measured neutral: DESIGN.md, retired switches)
           const float* __restrict__ Ya = Yt[k & 1] + r * LDY + 4 * q;
           const float* __restrict__ Wa = Wl + (own * 16 + r) * LDW + 4 * q;
 #pragma unroll
@@ -1439,10 +1419,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
             const float p = pred >= 0.f ? inv : en * inv;
             const float l = fmaxf(pred, 0.f) - pred * tgv[mb][e] + __logf(1.f + en);
             lacc += ok ? l : 0.f;
-            if (ok) {   // written once, read by nobody on the device before the epoch's end (HEAD_NT_PROBS: keep it out of the L2s)
-              if (HEAD_NT_PROBS) __builtin_nontemporal_store(p, &probs[(unsigned)(i * C + c0 + j)]);
-              else probs[(unsigned)(i * C + c0 + j)] = p;
-            }
+            if (ok) probs[(unsigned)(i * C + c0 + j)] = p;
             const float dp = ok ? (p - tgv[mb][e]) * inv_count : 0.f;
             dbo += dp;
             Pb[row * LDP + j] = dp;
@@ -1465,9 +1442,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
       for (int w = 0; w < 8; ++w) t += lsum[w];
       const float tl = first ? t : loss_part[blockIdx.x] + t;   // the label passes' shares add up
       loss_part[blockIdx.x] = tl;
-#ifndef HRSX_NOTICKET   // (decomposition build)
       if (sa.acc && last) head_loss_ticket(sa, S, D, tl, inv_count);   // (the Q team's integer adds: before the barrier above)
-#endif
     }
   } else {
     // =============================================================== Q: grad team, one tile behind
@@ -1517,7 +1492,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
             }
         }
         // label groups of 16 (4 k-steps: 8 A reads from Pt, 4 B reads from W_out), the next group's reads under this group's MFMAs
-        __builtin_amdgcn_s_setprio(HEAD_RS_PRIO);
+        __builtin_amdgcn_s_setprio(0);
         const float* __restrict__ Pa = Pb + r * LDP + q;
         const float* __restrict__ Wa = Wl + q * LDW + own * 16 + r;
         float pa[2][4 * NRB], wb[2][4];
@@ -1580,7 +1555,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
       if (k < mt) load_xq((int)blockIdx.x + k * G);   // tile k's values, used in S2 of the next period
       if (k >= 1) {
         OPAQUE_LANE(r, q, lq);
-        __builtin_amdgcn_s_setprio(HEAD_RS_PRIO);
+        __builtin_amdgcn_s_setprio(0);
         const float* __restrict__ Pa = Pt[(k - 1) & 1] + q * LDP + r;
         const float* __restrict__ Ya = Yt[(k - 1) & 1] + q * LDY + own * 16 + r;
         float a0[NB], a1[NB], b0, b1;
@@ -1634,9 +1609,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
             int fa, fb;
             head_bacc_points(wmax, 16, keep_scale, n, fa, fb);
             unsigned long long* bb = bacc_base(sa.acc, S, D);
-#ifndef HRSX_NOBACC   // (decomposition build: profiles/r06_stat_acc_experiment.txt item 5)
             bacc_add(bb, S, D, (int)blockIdx.x & (STAT_ACC_SLOTS - 1), s, own * 16 + r, a, b, fa, fb);
-#endif
             if (blockIdx.x == 0 && s == 0 && own == 0 && r == 0)
               bb[(size_t)STAT_ACC_SLOTS * S * D * 2 + BACC_EXP] = ((unsigned long long)(unsigned)(fb + 1024) << 32) | (unsigned long long)(unsigned)(fa + 1024);
           }
@@ -1667,10 +1640,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_rs(int n, int S, int C, con
 // Barriers per period: TWO.  k_head_fused_rs has three, so that in every sub-phase one team is on the matrix pipe and the other
 // on the vector pipe (fp32 MFMA holds the vector ALUs); with the bf16 forms that alternation buys nothing, and the data only asks
 // for: P's ym rows complete before P's pred product (B1), and the period's tiles complete before the next period reuses their
-// buffers (B2).  P: S1 | B1 | S2 S3 | B2;  Q (one tile behind): S1 S2 | B1 | S3 | B2.  (HEADSP_BARRIERS = 3: A/B builds.)
-#ifndef HEADSP_BARRIERS
-#define HEADSP_BARRIERS 2
-#endif
+// buffers (B2).  P: S1 | B1 | S2 S3 | B2;  Q (one tile behind): S1 S2 | B1 | S3 | B2.
 template <bool MULTI, int NB, bool DROP>
 __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, const float* __restrict__ X,
                                                         const float* __restrict__ bn_w, const float* __restrict__ bn_b,
@@ -1730,9 +1700,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
   // accumulate mode: batch mean / invstd decoded once per workgroup into the second P tile (first written in S3 of period 1)
   float* const stash = (float*)Ptb[1];
   static_assert(3 * LVT >= 6 * D * (int)sizeof(float), "the stash fits a P tile");
-#ifndef HRSX_NOSTAGE   // (decomposition build)
   if (sa.acc) head_stat_stage<D>(sa, n, S, stash, 1024);
-#endif
 #define OPAQUE_LANE(r_, q_, l_)          \
   int l_ = lane;                         \
   asm volatile("" : "+v"(l_));           \
@@ -1850,9 +1818,6 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
           acc = sacc.sum();
         }
       }
-#if HEADSP_BARRIERS == 3
-      __syncthreads();
-#endif
       // ---- S3: sigmoid / BCE / probs; d loss / d pred -> the levels of Pt[k & 1] (zero outside the valid region)   (vector; Q: dW_out product)
       if (k < mt) {
         unsigned char* __restrict__ Pb = Ptb[k & 1];
@@ -1869,10 +1834,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
           const float p = pred >= 0.f ? inv : en * inv;
           const float l = fmaxf(pred, 0.f) - pred * tgv[e] + __logf(1.f + en);
           lacc += ok ? l : 0.f;
-          if (ok) {
-            if (HEAD_NT_PROBS) __builtin_nontemporal_store(p, &probs[(unsigned)(i * C + c0 + j)]);
-            else probs[(unsigned)(i * C + c0 + j)] = p;
-          }
+          if (ok) probs[(unsigned)(i * C + c0 + j)] = p;
           const float dp = ok ? (p - tgv[e]) * inv_count : 0.f;
           dbo += dp;
           uint16_t dh, dm, dl;
@@ -1899,9 +1861,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
       for (int w = 0; w < 8; ++w) t += lsum[w];
       const float tl = first ? t : loss_part[blockIdx.x] + t;   // the label passes' shares add up
       loss_part[blockIdx.x] = tl;
-#ifndef HRSX_NOTICKET   // (decomposition build)
       if (sa.acc && last) head_loss_ticket(sa, S, D, tl, inv_count);   // (the Q team's integer adds: before the barrier above)
-#endif
     }
   } else {
     // =============================================================== Q: grad team, one tile behind
@@ -1969,9 +1929,6 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
           }
         }
       }
-#if HEADSP_BARRIERS == 3
-      __syncthreads();
-#endif
       // ---- S2: dym out, BatchNorm-backward column sums of tile k-1              (vector; P: pred product)
       if (k >= 1) {
         OPAQUE_LANE(r, q, lq);
@@ -2055,9 +2012,7 @@ __global__ __launch_bounds__(1024) void k_head_fused_sp(int n, int S, int C, con
             int fa, fb;
             head_bacc_points(wmax, 16, keep_scale, n, fa, fb);
             unsigned long long* bb = bacc_base(sa.acc, S, D);
-#ifndef HRSX_NOBACC
             bacc_add(bb, S, D, (int)blockIdx.x & (STAT_ACC_SLOTS - 1), s, own * 16 + r, a, b, fa, fb);
-#endif
             if (blockIdx.x == 0 && s == 0 && own == 0 && r == 0)
               bb[(size_t)STAT_ACC_SLOTS * S * D * 2 + BACC_EXP] = ((unsigned long long)(unsigned)(fb + 1024) << 32) | (unsigned long long)(unsigned)(fa + 1024);
           }

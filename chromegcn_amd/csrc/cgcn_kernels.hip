@@ -7,16 +7,24 @@
 // Kernel inventory (DESIGN.md has the roofline for each):
 //   k_spmm<S,D>             unfused aggregation  Y = diag(rs) Ahat X, whole-row gather  (tables that fit the L2s)
 //   k_aggregate_sliced<S,D> the same aggregation, feature-sliced: one 128-byte column slice per XCD (large tables)
-//   k_layer_fwd<S,D>        fused layer forward: gather -> LDS tile -> MFMA (x W) -> bias/tanh/gate/mix epilogue
-//   k_layer_dense<S,D>      the row-local half of the layer forward on an H that is in memory (after k_aggregate_sliced)
-//   k_bwd_rowlocal_ring     (d = 128) per-row gate/tanh derivative by a row team, H^T dU and dHs = diag(rs) dU W^T on MFMA by a
-//                           matrix team, the teams meeting through a flag-synchronised ring of LDS slots (no per-tile barrier)
+//   k_spmm_any              k_spmm for any width that is a multiple of 4 (the GraphConvolution drop-in)
+//   k_band_aggregate<S,D,R> the aggregation of a band graph as a sliding-window stream;  k_bwd_band: its backward gather
+//   k_layer_fwd<S,D,HAS_VAL,DEEP,PROD>  fused layer forward, one 16-row tile (16 / S nodes) per 8-wave workgroup: gather -> LDS
+//                           tile -> MFMA (x W) -> bias/tanh/gate/mix epilogue; d = 128: a row per half-wave in the row passes
+//   k_layer_dense<S,PROD>   (d = 128) the row-local half of the layer forward on an H that is in memory (after
+//                           k_aggregate_sliced), persistent over 16-row tiles;  k_layer_dense256<S>: the same at d = 256
+//   k_bwd_rowlocal_ring<HEAD,DROP,PROD>  (d = 128) per-row gate/tanh derivative by a row team, H^T dU and dHs = diag(rs) dU W^T on
+//                           MFMA by a matrix team, the teams meeting through a flag-synchronised ring of LDS slots (no per-tile barrier)
 //   The dense fp32 products of the d = 128 kernels come in two forms (template parameter PROD; cgcn_common.hpp):
 //   split products (default) -- six v_mfma_f32_*_bf16 partial products of an exact 3-way split of both fp32 operands, fp32
 //   accumulators -- or the fp32 MFMA chain v_mfma_f32_16x16x4_f32 (rounds 1-5; CGCN_PRODUCTS=fp32); d = 256 runs the chain.
 //   k_bwd_rowlocal256s      the same work at d = 256: column-slab workgroups, both products per 32-row tile
 //   k_reduce_partials       deterministic second stage of the column / dW sums
 //   k_bwd_sliced<S,D>       dX = mask ((1-g) dXn + Ahat^T dHs): feature-sliced gather + element-wise epilogue (+ a companion aggregation)
+//   k_sddmm, k_saliency_rows, k_sgd, k_adam   saliency product on the pattern and its row normalisation; optimizer steps
+// Build switches: numbers (#ifndef X / #define X n: tools/mkvariant.py sweeps them), the timing builds (KT_TIMING) and the
+// ring kernel's experiment builds (RING_TEST_SLOW_*, RING_SKIP_MFMA / RING_SKIP_ROWTEAM / RING_NO_WAIT, behind
+// CGCN_EXPERIMENT_BUILD).  The A/B switches that lost are gone: DESIGN.md 4, "Retired build switches".
 //
 // Reference semantics: models/SubLayers.py:42-52, models/ChromeModels.py:34-46 (forward);
 // SURVEY.md Appendix A (backward).
@@ -46,7 +54,7 @@ struct Geo {
 // unit with v_readlane.  Neighbour rows are fetched GU wave-loads at a time, all issued before the first
 // add.  The code is branch-free inside a 64-neighbour chunk: a ragged tail re-reads the row's last valid
 // neighbour (an L1 hit) and adds a selected zero, so it never degenerates into a serial
-// load-wait-add chain.  GATHER_DB = 1 additionally double-buffers the batches.
+// load-wait-add chain.
 // Batch depth (GU wave-loads in flight per wave) is a property of the payload and of where the rows come from,
 // measured on MI355X (whole chr21-like step, ms): the sweet spot is about 2 KiB in flight per wave with as many
 // resident waves as the registers then allow (66 instead of 86 VGPRs: three instead of two workgroups per CU, so
@@ -54,32 +62,11 @@ struct Geo {
 // (d = 256, L = 4): GU 1 / 2 / 3 / 8 = .887 / 1.04 / 1.08 / 1.13.  When the feature table is much larger than the
 // L2s (chr1-like, 30 MB) the longer miss latency wants one more load in flight: GU 2 / 3 / 8 = .670 / .647 / .668.
 // S*D = 128 (one strand, two neighbours per wave-load): layer forward 26.5 / 25.4 / 27.1 us at GU 3 / 4 / 6.
-#ifndef GU_OVERRIDE
-#define GU_OVERRIDE 0  // tuning: force one depth everywhere
-#endif
-// Z and H are written for the backward only.  Non-temporal stores for them (NT_SAVED=1) were measured neutral
-// for the kernel (34.3 vs 34.5 us) and slightly negative for the whole step, so plain stores are the default.
-#ifndef NT_SAVED
-#define NT_SAVED 0
-#endif
-#if NT_SAVED
-#define NT_STORE4(p, v) __builtin_nontemporal_store((v), (f32x4*)(p))
-#define NT_STORE1(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define NT_STORE4(p, v) (*(f32x4*)(p) = (v))
-#define NT_STORE1(p, v) (*(p) = (v))
-#endif
-#ifndef CBW128
-#define CBW128 1   // column blocks per wave at D = 128: 1 -> 8-wave workgroups, 2 -> 4-wave
-#endif
-#ifndef GATHER_DB
-#define GATHER_DB 0
-#endif
 template <int S, int D, bool HAS_VAL, bool DEEP>
 struct Gather {
   using G = Geo<S, D>;
   static constexpr int NV = G::NV;
-  static constexpr int GU = GU_OVERRIDE ? GU_OVERRIDE : (G::HALF ? 4 : (NV == 2 ? 1 : (DEEP ? 3 : 2)));
+  static constexpr int GU = G::HALF ? 4 : (NV == 2 ? 1 : (DEEP ? 3 : 2));
   static constexpr int NPL = G::HALF ? 2 : 1;   // neighbours per wave-load
   static constexpr unsigned ROWB = D * 4;       // bytes per (strand,node) row
 
@@ -139,24 +126,12 @@ __device__ __forceinline__ void gather_range(const int* __restrict__ col, const 
       if (HAS_VAL) myv = val[kb + lane];
     }
     const int nbat = (cnt + GU * GA::NPL - 1) / (GU * GA::NPL);
-#if GATHER_DB
-    f32x4 ta[GU][NV], tb[GU][NV];
-    float wa[GU], wb[GU];
-    GA::issue(ta, wa, 0, cnt, myc, myv, Xb, lane_off, lane);
-    for (int b = 0; b < nbat; b += 2) {
-      GA::issue(tb, wb, b + 1, cnt, myc, myv, Xb, lane_off, lane);   // past the end: clamped re-reads, adds zero
-      GA::consume(ta, wa, b, cnt, acc, lane);
-      GA::issue(ta, wa, b + 2, cnt, myc, myv, Xb, lane_off, lane);
-      GA::consume(tb, wb, b + 1, cnt, acc, lane);
-    }
-#else
     for (int b = 0; b < nbat; ++b) {
       f32x4 t[GU][NV];
       float w[GU];
       GA::issue(t, w, b, cnt, myc, myv, Xb, lane_off, lane);
       GA::consume(t, w, b, cnt, acc, lane);
     }
-#endif
   }
 }
 
@@ -221,7 +196,7 @@ __device__ __forceinline__ void gather_tile(int n, int node0, const int* __restr
       for (int v = 0; v < NV; ++v) {
         const int s = G::strand(v, lane), c = G::column(v, lane);
         *(f32x4*)&T[(s * R + rr) * LD + c] = acc[v];
-        if (Hout && i < n) NT_STORE4(&Hout[((size_t)s * n + i) * D + c], acc[v]);
+        if (Hout && i < n) *(f32x4*)&Hout[((size_t)s * n + i) * D + c] = acc[v];
       }
     }
   }
@@ -251,7 +226,7 @@ __device__ __forceinline__ void gather_tile(int n, int node0, const int* __restr
         for (int w = 0; w < NW; ++w) t += *(const f32x4*)&scratch[w * PAY + s * D + c];
         t *= sc;
         *(f32x4*)&T[(s * R + rr) * LD + c] = t;
-        if (Hout) NT_STORE4(&Hout[((size_t)s * n + i) * D + c], t);
+        if (Hout) *(f32x4*)&Hout[((size_t)s * n + i) * D + c] = t;
       }
     }
     __syncthreads();
@@ -340,16 +315,16 @@ __global__ __launch_bounds__(256) void k_spmm_any(int n_rows, int n_cols, int S,
 // ------------------------------------------------------------------------------------------
 // Shared pieces of the fused kernels (k_layer_fwd; round 1: also the fused backward gather).
 //
-// Tile: TN = 16*MB/S nodes x S strands = 16*MB MFMA rows, staged in LDS as T[row][D+4].
+// Tile: 16 / S nodes x S strands = 16 MFMA rows, staged in LDS as T[row][D+4].
 // MFMA: v_mfma_f32_16x16x4_f32.  A lane l: A[row l&15][k-slot l>>4]; B lane l: B[k-slot l>>4][col l&15];
 // C: col l&15, row 4*(l>>4)+reg.  The K index is permuted so that operand reads are 16 bytes wide and the
 // four k-slots of one step read 64 contiguous bytes of a row: step (t,u) of k-slot q (= l>>4) uses
 // k = 16t + 4q + u, for A and B alike.
-// Wave w owns output columns [32w, 32w+32) as two 16-wide blocks.
+// Wave w of 8 owns CBW 16-wide blocks of output columns: one at D = 128, two at D = 256.
 //   TRANS_W == false: B(k,j) = W[k][j]   (forward,  U = H W)
 //   TRANS_W == true : B(k,j) = W[j][k]   (backward, dS W^T)
-// For D = 128 a wave's whole B operand (2 x 32 floats per lane) is fetched into registers BEFORE the
-// gather phase, so its L2 latency hides behind the gather; for D = 256 it is read in the K loop.
+// For D = 128 a wave's whole B operand (32 floats per lane) is fetched into registers once (PRELOADED); for D = 256 it
+// is read in the K loop.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ int xcd_contiguous(int b, int nblk) {
   // Workgroups are dealt round-robin over the 8 XCDs; give each XCD (each private L2) a contiguous
@@ -379,36 +354,27 @@ __device__ __forceinline__ void load_wfrag(const float* __restrict__ W, int wave
   }
 }
 
-template <int MB, int D, int CBW, int LD, bool TRANS_W, bool PRELOADED>
+template <int D, int CBW, int LD, bool TRANS_W, bool PRELOADED>
 __device__ __forceinline__ void tile_mfma(const float* __restrict__ T, const float* __restrict__ W,
-                                          const float (&bw)[CBW][D / 4], int wave, int lane, f32x4 (&acc)[MB][CBW]) {
+                                          const float (&bw)[CBW][D / 4], int wave, int lane, f32x4 (&acc)[CBW]) {
   constexpr int KQ = D / 4;
   const int r = lane & 15, q = lane >> 4;
 #pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int cb = 0; cb < CBW; ++cb) acc[mb][cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int cb = 0; cb < CBW; ++cb) acc[cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (PRELOADED) {
 #pragma unroll
     for (int t = 0; t < KQ / 4; ++t) {
-      f32x4 a[MB];
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) a[mb] = *(const f32x4*)&T[(mb * 16 + r) * LD + 16 * t + 4 * q];
+      const f32x4 a = *(const f32x4*)&T[r * LD + 16 * t + 4 * q];
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-          for (int cb = 0; cb < CBW; ++cb)
-            acc[mb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][u], bw[cb][4 * t + u], acc[mb][cb], 0, 0, 0);
+        for (int cb = 0; cb < CBW; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], bw[cb][4 * t + u], acc[cb], 0, 0, 0);
     }
   } else {
     const int j0 = wave * (16 * CBW) + r;
 #pragma unroll 2
     for (int t = 0; t < KQ / 4; ++t) {
-      f32x4 a[MB];
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) a[mb] = *(const f32x4*)&T[(mb * 16 + r) * LD + 16 * t + 4 * q];
+      const f32x4 a = *(const f32x4*)&T[r * LD + 16 * t + 4 * q];
       f32x4 b[CBW];
 #pragma unroll
       for (int cb = 0; cb < CBW; ++cb) {
@@ -422,10 +388,7 @@ __device__ __forceinline__ void tile_mfma(const float* __restrict__ T, const flo
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-          for (int cb = 0; cb < CBW; ++cb)
-            acc[mb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][u], b[cb][u], acc[mb][cb], 0, 0, 0);
+        for (int cb = 0; cb < CBW; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[cb][u], acc[cb], 0, 0, 0);
     }
   }
 }
@@ -440,17 +403,8 @@ __device__ __forceinline__ void tile_mfma(const float* __restrict__ T, const flo
 // 8 waves per SIMD (<= 64 VGPRs; the two-strand 16-row variants need 62-66 as it is): four workgroups per CU
 // resident.  Measured with it: chr10-like layer forward 73.4 -> 68.9 us, chr1-like 92.5 -> 87.3 us, chr21-like
 // unchanged.  Not for the single-strand geometry (deeper batches, more registers: 25.4 us free vs 29.2 us forced).
-#ifndef DENSE_HALF_WAVE_ROWS
-#define DENSE_HALF_WAVE_ROWS 1   // d = 128: the row-wise passes of k_layer_fwd / k_layer_dense take a row per half-wave, 16 B per lane
-#endif
-#ifndef FWD_HALF_WAVE_ROWS
-#define FWD_HALF_WAVE_ROWS 1
-#endif
 #ifndef FWD_WAVES_PER_SIMD
 #define FWD_WAVES_PER_SIMD(S_, D_) (((S_) * (D_) == 128) ? 1 : 8)
-#endif
-#ifndef FWD_OCC
-#define FWD_OCC
 #endif
 #ifdef KT_TIMING  // tuning build only (tools/khead.py --stamps-rowlocal): phase timestamps of a few workgroups
 __device__ unsigned long long kt_stamps[8 * 16];
@@ -488,8 +442,8 @@ extern "C" int cgcn_debug_kt_stamps(unsigned long long* out) {
 #define KT_STAMP_NW(i, tid, cond)
 #endif
 
-template <int S, int D, int MB, bool HAS_VAL, bool DEEP, int PROD>
-__global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : FWD_WAVES_PER_SIMD(S, D)) FWD_OCC void k_layer_fwd(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+template <int S, int D, bool HAS_VAL, bool DEEP, int PROD>
+__global__ __launch_bounds__(512, PROD ? 4 : FWD_WAVES_PER_SIMD(S, D)) void k_layer_fwd(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
                                                      const float* __restrict__ val, const float* __restrict__ rs,
                                                      const float* __restrict__ X, const float* __restrict__ W,
                                                      const float* __restrict__ bias, const float* __restrict__ wg,
@@ -503,9 +457,9 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
   // (statistics totals of a LATER launch of the step -- cgcn_layer_fwd's colstats_rows = -2 -- zeroed here like k_aggregate_sliced does)
   if (zero_words && (int)blockIdx.x < min((int)gridDim.x, 8))
     for (int i = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x; i < zero_count; i += min((int)gridDim.x, 8) * (int)blockDim.x) zero_words[i] = 0ull;
-  constexpr int ROWS = 16 * MB;      // MFMA rows in the tile
+  constexpr int ROWS = 16;           // MFMA rows in the tile
   constexpr int R = ROWS / S;        // nodes in the tile
-  constexpr int CBW = (D == 128) ? CBW128 : 2;  // 16-wide output column blocks per wave
+  constexpr int CBW = (D == 128) ? 1 : 2;  // 16-wide output column blocks per wave
   constexpr int NW = D / (16 * CBW); // 8 waves per workgroup
   constexpr int LD = D + 4;          // LDS row stride (floats); keeps 16-byte alignment
   constexpr int EPL = D / 64;        // floats per lane in the row-wise epilogue
@@ -518,7 +472,7 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
   // registers instead of 32: 4 waves per SIMD (this kernel only serves tables below the split threshold).
   constexpr int LVT = ROWS * 256;   // bytes of one level tile (swizzled image of cgcn_common.hpp, sp_sigma)
   __shared__ __attribute__((aligned(16))) unsigned char Tb[PROD ? 3 * LVT : 16];
-  static_assert(PROD == 0 || (D == 128 && MB == 1 && CBW == 1 && FWD_HALF_WAVE_ROWS), "split products: d = 128, the half-wave-row form");
+  static_assert(PROD == 0 || D == 128, "split products: d = 128, the half-wave-row form");
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -554,7 +508,7 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
   // prefetch the residual rows this wave will mix in phase 3 (latency hides behind the MFMA phase)
   // D = 128: the row-wise epilogue takes a row per HALF-wave, 16 bytes per lane (see k_layer_dense): the wave's two rows
   // of the 16-row tile are 2 wave + {0, 1}
-  constexpr bool HW = (D == 128 && MB == 1 && NW == 8 && FWD_HALF_WAVE_ROWS);
+  constexpr bool HW = (D == 128);
   const bool upper = lane >= 32;
   const int l4 = (lane & 31) * 4;
   const int hm = 2 * wave + (upper ? 1 : 0);
@@ -584,7 +538,7 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
 
   KT_STAMP(11);
   // ---- phase 2
-  f32x4 acc[MB][CBW];
+  f32x4 acc[CBW];
   if constexpr (PROD != 0) {
     {   // this half-wave's row of the gathered tile -> the three levels
       u32x2 h2, m2, l2;
@@ -608,9 +562,9 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
       const bf16x8 al = __builtin_bit_cast(bf16x8, *(const u32x4*)(Ta + 2 * LVT + o));
       sa.step(ah, am, al, wh[s], wm[s], wl[s]);
     }
-    acc[0][0] = sa.sum();
+    acc[0] = sa.sum();
   } else {
-    tile_mfma<MB, D, CBW, LD, false, PRE>(T, W, bw, wave, lane, acc);
+    tile_mfma<D, CBW, LD, false, PRE>(T, W, bw, wave, lane, acc);
     __syncthreads();  // every wave is done reading T as the A operand
   }
 
@@ -626,9 +580,7 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
       const int j = wave * (16 * CBW) + cb * 16 + r;
       const float bj = bjv[cb];
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) T[(mb * 16 + q * 4 + e) * LD + j] = layer_tanh(acc[mb][cb][e] + bj);
+      for (int e = 0; e < 4; ++e) T[(q * 4 + e) * LD + j] = layer_tanh(acc[cb][e] + bj);
     }
   }
   __syncthreads();
@@ -730,14 +682,14 @@ __global__ __launch_bounds__((D == 128 && CBW128 == 2) ? 256 : 512, PROD ? 4 : F
 // k_layer_dense: the row-local half of the layer forward for an aggregation H that is already in memory (the split
 // path: k_aggregate_sliced wrote it; or the engine's cached A X of the first layer): U = H W + b on MFMA, tanh, gate,
 // mix, optional dropout and BatchNorm column statistics -- phases 2 and 3 of k_layer_fwd.  Persistent: a workgroup
-// walks node tiles (R nodes x S strands = 16 MB rows) with its W fragments resident in registers (D = 128), so W is
+// walks node tiles (R nodes x S strands = 16 rows) with its W fragments resident in registers (D = 128 only), so W is
 // read once per workgroup instead of once per tile, and several workgroups per CU overlap each other's load, MFMA
 // and store phases.  Streams H and X in, Xn, Z and the gate out.
 // ------------------------------------------------------------------------------------------
 #ifndef DENSE_WAVES_PER_SIMD
 #define DENSE_WAVES_PER_SIMD 4
 #endif
-template <int S, int D, int MB, int PROD>
+template <int S, int PROD>
 __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n, int ntiles, const float* __restrict__ Hin,
                                                     const float* __restrict__ X, const float* __restrict__ W,
                                                     const float* __restrict__ bias, const float* __restrict__ wg,
@@ -749,16 +701,11 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
                                                     int stat_acc, unsigned long long* __restrict__ zero_words, int zero_count) {
   if (zero_words && (int)blockIdx.x < min((int)gridDim.x, 8))   // (totals of a LATER launch of the step: colstats_rows = -2)
     for (int i = (int)blockIdx.x * 512 + (int)threadIdx.x; i < zero_count; i += min((int)gridDim.x, 8) * 512) zero_words[i] = 0ull;
-  constexpr int ROWS = 16 * MB;      // MFMA rows in the tile
+  constexpr int D = 128;             // d = 256 has its own kernel (k_layer_dense256)
+  constexpr int ROWS = 16;           // MFMA rows in the tile: two per wave
   constexpr int R = ROWS / S;        // nodes in the tile
-  static_assert(D == 128, "d = 256 has its own kernel (k_layer_dense256)");
   constexpr int CBW = 1;             // 16-wide output column blocks per wave
-  constexpr int NW = 8;
   constexpr int LD = D + 4;          // LDS row stride (floats); keeps 16-byte alignment
-  constexpr int EPL = D / 64;        // floats per lane in the row-wise passes
-  constexpr int RPW = ROWS / NW;     // rows per wave
-  constexpr bool PRE = true;         // W fragments resident in registers
-  static_assert(D / (16 * CBW) == NW && ROWS % NW == 0, "geometry");
   __shared__ __attribute__((aligned(16))) float T[ROWS * LD];
   // PROD == 1 (split products, cgcn_common.hpp): the A operand lives in its own tile as three bf16 levels (the swizzled level-tile
   // image sp_sigma: padded 272-byte rows cost 2 800 bank-conflict cycles per CU and launch on the ds_read_b128 operand reads,
@@ -766,12 +713,11 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
   // tile go (nobody reads T as an operand, nobody rewrites it early)
   constexpr int LVT = ROWS * 256;
   __shared__ __attribute__((aligned(16))) unsigned char Tb[PROD ? 3 * LVT : 16];
-  static_assert(PROD == 0 || (D == 128 && MB == 1 && DENSE_HALF_WAVE_ROWS), "split products: the half-wave-row form");
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   KT_STAMP(8);
-  float bw[PROD ? 1 : CBW][PROD ? 1 : D / 4];
+  float bw[CBW][PROD ? 1 : D / 4];   // W fragments resident in registers
   bf16x8 wh[PROD ? D / 32 : 1], wm[PROD ? D / 32 : 1], wl[PROD ? D / 32 : 1];
   if constexpr (PROD != 0) {   // B operand of K-step s: W[32 s + 8 q + u][16 wave + r], u < 8, as three levels
     const int r = lane & 15, q = lane >> 4;
@@ -783,43 +729,29 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
       sp_split8(v, wh[s], wm[s], wl[s]);
     }
   } else {
-    if (PRE) load_wfrag<D, CBW, false>(W, wave, lane, bw);
+    load_wfrag<D, CBW, false>(W, wave, lane, bw);
   }
-  float bjv[CBW], wgl[EPL];
+  float bjv[CBW];
 #pragma unroll
   for (int cb = 0; cb < CBW; ++cb) bjv[cb] = bias[wave * (16 * CBW) + cb * 16 + (lane & 15)];
-  ld_row<EPL>(wgl, &wg[lane * EPL]);
   const float c0 = cg[0];
   const uint32_t key = thresh ? dropout_key(rng_state, stream_id) : 0u;
-  // D = 128 (round 4): the row-wise passes take a row per HALF-wave, 16 bytes per lane -- one wave instruction moves two
+  // The row-wise passes take a row per HALF-wave, 16 bytes per lane -- one wave instruction moves two
   // rows (k_bwd_rowlocal_ring's row team streams the same rows at 6.5 TB/s that way against 5.3 with 8 bytes per lane
   // and a row per wave): half the loads / stores / LDS accesses, one DPP reduction for two rows.  The wave's two rows of
   // a 16-row tile are 2 wave + {0, 1}.
-  constexpr bool HW = (D == 128 && MB == 1 && DENSE_HALF_WAVE_ROWS);
   const bool upper = lane >= 32;
   const int l4 = (lane & 31) * 4;
   const int hm = 2 * wave + (upper ? 1 : 0);            // this half-wave's row of the tile
   const int hs = hm / R, hr = hm % R;                   // its strand and its node inside the tile
-  const f32x4 wgl4 = HW ? *(const f32x4*)&wg[l4] : (f32x4){0.f, 0.f, 0.f, 0.f};
+  const f32x4 wgl4 = *(const f32x4*)&wg[l4];
+  // Both input streams run one whole tile ahead: the loads of tile t+1 are issued at the top of tile t, so every
+  // resident workgroup keeps a full tile of reads in flight through its MFMA, tanh and store phases.
   f32x4 hrow4 = {0.f, 0.f, 0.f, 0.f}, xres4 = hrow4, xnext4 = hrow4;
   auto load_rows4 = [&](f32x4& dst, const float* __restrict__ src, int tile) {
     const int i = tile * R + hr;
     dst = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (i < n) dst = *(const f32x4*)&src[((size_t)hs * n + i) * D + l4];
-  };
-
-  // rows of the tile this wave streams in / finishes: m = wave + t * NW  ->  (strand m / R, node node0 + m % R).
-  // Both input streams run one whole tile ahead: the loads of tile t+1 are issued at the top of tile t, so every
-  // resident workgroup keeps a full tile of reads in flight through its MFMA, tanh and store phases.
-  float hrow[RPW][EPL], xres[RPW][EPL], xnext[RPW][EPL];
-  auto load_rows = [&](float (&dst)[RPW][EPL], const float* __restrict__ src, int tile) {
-#pragma unroll
-    for (int t = 0; t < RPW; ++t) {
-      const int m = wave + t * NW;
-      const int i = tile * R + (m % R);
-      if (i < n) ld_row<EPL>(dst[t], &src[((size_t)(m / R) * n + i) * D + lane * EPL]);
-      else zero_row<EPL>(dst[t]);
-    }
   };
   // Tile walk.  Without column statistics: tiles b, b + G, b + 2G, ... (G = grid).  With them: the CONTIGUOUS tiles
   // [b * stat_chunk, (b + 1) * stat_chunk), whose statistics are merged on chip (Chan) into ONE record per workgroup --
@@ -830,50 +762,32 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
   const int tend = colstats ? min(ntiles, tfirst + stat_chunk) : ntiles;
   float st_cnt = 0.f, st_mean = 0.f, st_m2 = 0.f;   // running statistics of this thread's (strand, column)
   if (tfirst < tend) {
-    if (HW) {
-      load_rows4(hrow4, Hin, tfirst);
-      load_rows4(xnext4, X, tfirst);
-    } else {
-      load_rows(hrow, Hin, tfirst);
-      load_rows(xnext, X, tfirst);
-    }
+    load_rows4(hrow4, Hin, tfirst);
+    load_rows4(xnext4, X, tfirst);
   }
   KT_STAMP(9);
   for (int tile = tfirst; tile < tend; tile += tstep) {
     const int node0 = tile * R;
     KT_STAMP(10);
-    if (HW) {
-      if (PROD) {
-        u32x2 h2, m2, l2;
-        sp_split4(hrow4, h2, m2, l2);
-        unsigned char* w = Tb + hm * 256 + ((((lane & 31) >> 1) ^ sp_sigma(hm)) << 4) + ((lane & 1) << 3);
-        *(u32x2*)w = h2;
-        *(u32x2*)(w + LVT) = m2;
-        *(u32x2*)(w + 2 * LVT) = l2;
-      } else {
-        *(f32x4*)&T[hm * LD + l4] = hrow4;
-      }
-      xres4 = xnext4;
-      if (tile + tstep < tend) {
-        load_rows4(hrow4, Hin, tile + tstep);
-        load_rows4(xnext4, X, tile + tstep);
-      }
+    if (PROD) {
+      u32x2 h2, m2, l2;
+      sp_split4(hrow4, h2, m2, l2);
+      unsigned char* w = Tb + hm * 256 + ((((lane & 31) >> 1) ^ sp_sigma(hm)) << 4) + ((lane & 1) << 3);
+      *(u32x2*)w = h2;
+      *(u32x2*)(w + LVT) = m2;
+      *(u32x2*)(w + 2 * LVT) = l2;
     } else {
-#pragma unroll
-      for (int t = 0; t < RPW; ++t) {
-        st_row<EPL>(&T[(wave + t * NW) * LD + lane * EPL], hrow[t]);
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) xres[t][e] = xnext[t][e];
-      }
-      if (tile + tstep < tend) {
-        load_rows(hrow, Hin, tile + tstep);
-        load_rows(xnext, X, tile + tstep);
-      }
+      *(f32x4*)&T[hm * LD + l4] = hrow4;
+    }
+    xres4 = xnext4;
+    if (tile + tstep < tend) {
+      load_rows4(hrow4, Hin, tile + tstep);
+      load_rows4(xnext4, X, tile + tstep);
     }
     __syncthreads();
     KT_STAMP(11);
     // ---- U = H W
-    f32x4 acc[MB][CBW];
+    f32x4 acc[CBW];
     if constexpr (PROD != 0) {
       const int r = lane & 15, q = lane >> 4;
       const unsigned char* __restrict__ Ta = Tb + r * 256 + ((q ^ (sp_sigma(r) & 3)) << 4);
@@ -888,28 +802,23 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
         const bf16x8 al = __builtin_bit_cast(bf16x8, *(const u32x4*)(Ta + 2 * LVT + o));
         sa.step(ah, am, al, wh[s], wm[s], wl[s]);
       }
-      acc[0][0] = sa.sum();
+      acc[0] = sa.sum();
     } else {
-      tile_mfma<MB, D, CBW, LD, false, PRE>(T, W, bw, wave, lane, acc);
+      tile_mfma<D, CBW, LD, false, true>(T, W, bw, wave, lane, acc);
       __syncthreads();  // every wave is done reading T as the A operand
     }
     KT_STAMP(12);
     // ---- Z = tanh(U + b) back into the tile
     {
       const int r = lane & 15, q = lane >> 4;
+      const int j = wave * 16 + r;
 #pragma unroll
-      for (int cb = 0; cb < CBW; ++cb) {
-        const int j = wave * (16 * CBW) + cb * 16 + r;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) T[(mb * 16 + q * 4 + e) * LD + j] = layer_tanh(acc[mb][cb][e] + bjv[cb]);
-      }
+      for (int e = 0; e < 4; ++e) T[(q * 4 + e) * LD + j] = layer_tanh(acc[0][e] + bjv[0]);
     }
     __syncthreads();
     KT_STAMP(13);
     // ---- row-wise gate + residual mix, coalesced stores
-    if (HW) {
+    {
       const int i = node0 + hr;
       const f32x4 z4 = *(const f32x4*)&T[hm * LD + l4];
       float dot = z4[0] * wgl4[0] + z4[1] * wgl4[1] + z4[2] * wgl4[2] + z4[3] * wgl4[3];
@@ -928,40 +837,13 @@ __global__ __launch_bounds__(512, DENSE_WAVES_PER_SIMD) void k_layer_dense(int n
         if (Zout) *(f32x4*)&Zout[g_off] = z4;
         if ((lane & 31) == 0) gate[(size_t)hs * n + i] = g;
       }
-    } else
-#pragma unroll
-    for (int t = 0; t < RPW; ++t) {
-      const int m = wave + t * NW;
-      const int s = m / R, rr = m % R;
-      const int i = node0 + rr;
-      if (i >= n) continue;  // wave-uniform
-      float z[EPL];
-      float dot = 0.f;
-      const size_t g_off = ((size_t)s * n + i) * D + lane * EPL;
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) {
-        z[e] = T[m * LD + lane * EPL + e];
-        dot += z[e] * wgl[e];
-      }
-      dot = wave_sum(dot);
-      const float g = sigmoidf_(dot + c0);
-      float xo[EPL];
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) {
-        xo[e] = (1.f - g) * xres[t][e] + g * z[e];
-        if (thresh) xo[e] = dropout_keep(key, (uint32_t)(g_off + e), thresh) ? xo[e] * keep_scale : 0.f;
-        if (colstats) T[m * LD + lane * EPL + e] = fmaxf(xo[e], 0.f);  // own row, already consumed above
-      }
-      st_row<EPL>(&Xn[g_off], xo);
-      if (Zout) st_row<EPL>(&Zout[g_off], z);
-      if (lane == 0) gate[(size_t)s * n + i] = g;
     }
     KT_STAMP(14);
     // ---- optional: first stage of the classifier head's BatchNorm statistics while the tile is on chip: per
     // (strand, column) the exact two-pass (mean, M2) of relu(Xn) over this tile's nodes
     if (colstats) {
       __syncthreads();
-      static_assert(MB * S * D <= 512, "one (strand, column) per thread");
+      static_assert(S * D <= 512, "one (strand, column) per thread");
       const int idx = threadIdx.x;
       if (idx < S * D) {
         const int s = idx / D, c = idx % D;
@@ -1211,7 +1093,7 @@ __global__ __launch_bounds__(1024) void k_layer_dense256(int n, int ntiles, cons
 #define RING_SLOTS 8
 #endif
 #ifndef RING_ROW_WAVES
-#define RING_ROW_WAVES 8 // 8: 16-wave workgroups, 2 row + 2 matrix waves per SIMD, <= 128 registers (needs RING_OPBUF 2, RING_PRIME 0);
+#define RING_ROW_WAVES 8 // 8: 16-wave workgroups, 2 row + 2 matrix waves per SIMD, <= 128 registers;
 #endif                   // 4: 12 waves, 1 row + 2 matrix per SIMD, <= 168.  Measured (profiles/r04_rowlocal_ring_experiment.txt): 8 wins
 #define RING_THREADS ((RING_ROW_WAVES + 8) * 64)
 #ifndef RING_PF
@@ -1220,25 +1102,16 @@ __global__ __launch_bounds__(1024) void k_layer_dense256(int n, int ntiles, cons
 #ifndef RING_PF_HEAD
 #define RING_PF_HEAD 2   // ... in head mode (the head prologue needs ~25 more registers per row pair)
 #endif
-#ifndef RING_PRIO
-#define RING_PRIO 1      // s_setprio of the matrix team (measured: 0 -> 1: 51.3 -> 45.6 us at n = 29 910)
-#endif
-#ifndef RING_OPBUF
-#define RING_OPBUF 2     // matrix team: operand sets in flight (3: two steps ahead, 2: one step ahead, 8 registers fewer)
-#endif
-#ifndef RING_EARLY_FLAG
-#define RING_EARLY_FLAG 1 // matrix team: read the next slot's FULL flag under the current slot's MFMAs; poll only if it was not up yet
-#endif
 #ifndef RING_PRIME
-#define RING_PRIME 0     // matrix team: request the next slot's first operands under the current slot's last MFMAs (measured: no gain)
-#endif
+#define RING_PRIME 0     // fp32-chain matrix team: request the next slot's first operands under the current slot's last MFMAs
+#endif                   // (measured: no gain; RING_ROW_WAVES 8 has no registers for it).  Still a switch: without `primed` the
+                         // compiler allocates the registers of the fp32-chain instances differently (tools/isa_diff.py)
 // Every switch below changes WHAT the kernel computes or how its teams meet (decomposition builds of tools/ring_decomp.sh:
 // garbage results by design; the slowed teams of tests/test_gpu_ring_stress.py: same results, other timing).  None of
 // them can be reached by a stray -D: they need -DCGCN_EXPERIMENT_BUILD, which chromegcn_amd/_build.py refuses for the
 // in-tree library.
-#if (defined(RING_NO_WAIT) || defined(RING_SKIP_MFMA) || defined(RING_SKIP_ROWTEAM) || defined(RING_SKIP_LOADS) || \
-     defined(RING_TEST_SLOW_ROW) || defined(RING_TEST_SLOW_MATRIX) || defined(RL256_SKIP_MFMA) || defined(RL256_SKIP_LOADS) || \
-     defined(BSX_NORIDERS) || defined(BSX_NODXN) || defined(BSX_NOSTORE)) && \
+#if (defined(RING_NO_WAIT) || defined(RING_SKIP_MFMA) || defined(RING_SKIP_ROWTEAM) || defined(RING_TEST_SLOW_ROW) || \
+     defined(RING_TEST_SLOW_MATRIX)) && \
     !defined(CGCN_EXPERIMENT_BUILD)
 #error "RING_NO_WAIT / RING_SKIP_* / RING_TEST_SLOW_* are experiment switches: build a variant with -DCGCN_EXPERIMENT_BUILD (tools/mkvariant.py), never the shipped library"
 #endif
@@ -1369,10 +1242,6 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
         if (s == 0) Hc[8 * D + c] = hp.bn_w[c];
       }
     }
-#ifndef RING_NT_LOADS
-#define RING_NT_LOADS 0   // bit mask of row streams loaded non-temporally (every one is a last use): 1 Z, 2 X, 4 H, 8 dXn, 16 dym
-#endif
-#define RING_LD(bit, p) ((RING_NT_LOADS & (bit)) ? __builtin_nontemporal_load((const f32x4*)(p)) : *(const f32x4*)(p))
     struct Rows { f32x4 z[RT], x[RT], h[RT], g[RT]; float gt[RT], sc[RT]; };
     Rows R_[PF];
     // this lane's element of a slot's rows, as 32-bit offsets from UNIFORM per-slot bases (scalar base + vector offset
@@ -1380,11 +1249,7 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
     const unsigned lane_el = (unsigned)(row0 * D + 4 * l);
     auto load_slot = [&](int it, Rows& w) {
       const int m0 = (s_begin + it) * SR;   // first row of the slot (uniform)
-#ifdef RING_SKIP_LOADS
-      if (false) {
-#else
       if (m0 + SR <= M && (m0 >= n || m0 + SR <= n)) {
-#endif
         // the whole slot lies inside the table and inside one strand (all but two slots of a launch): no predicates
         const int mi0 = m0 >= n ? m0 - n : m0;   // S <= 2
         const float* __restrict__ Zb = Z + (size_t)m0 * D;
@@ -1398,10 +1263,10 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
           unsigned ob = 4u * lane_el + (unsigned)(2 * NRW * t * D * 4);
           unsigned rb4 = 4u * (unsigned)(row0 + 2 * NRW * t);
           asm volatile("" : "+v"(ob), "+v"(rb4));   // keep the zero-extension next to the loads (a hoisted 64-bit offset defeats the mode)
-          w.z[t] = RING_LD(1, (const char*)Zb + ob);
-          w.x[t] = RING_LD(2, (const char*)Xb + ob);
-          w.h[t] = RING_LD(4, (const char*)Hb + ob);
-          w.g[t] = RING_LD(HEAD ? 16 : 8, (const char*)Gb + ob);
+          w.z[t] = *(const f32x4*)((const char*)Zb + ob);
+          w.x[t] = *(const f32x4*)((const char*)Xb + ob);
+          w.h[t] = *(const f32x4*)((const char*)Hb + ob);
+          w.g[t] = *(const f32x4*)((const char*)Gb + ob);
           w.gt[t] = *(const float*)((const char*)gb + rb4);
           w.sc[t] = rb ? *(const float*)((const char*)rb + rb4) : 1.f;
         }
@@ -1410,16 +1275,11 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #pragma unroll
       for (int t = 0; t < RT; ++t) {
         const int m = m0 + row0 + 2 * NRW * t;
-#ifdef RING_SKIP_LOADS
-        const bool ok = false;
-#else
-        const bool ok = m < M;
-#endif
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         w.z[t] = w.x[t] = w.h[t] = w.g[t] = zero;
         w.gt[t] = 0.f;
         w.sc[t] = 0.f;
-        if (ok) {
+        if (m < M) {
           const unsigned off = (unsigned)(m * D + 4 * l);
           const int mi = m >= n ? m - n : m;   // S <= 2
           w.z[t] = *(const f32x4*)&Z[off];
@@ -1580,7 +1440,7 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #pragma unroll
       for (int e = 0; e < 16; ++e) accW[bb][e] = 0.f;
     __syncthreads();   // flags zeroed (and the row team's staging of the head constants)
-    if (RING_PRIO) __builtin_amdgcn_s_setprio(RING_PRIO);
+    __builtin_amdgcn_s_setprio(1);
     // transposed reads (32x32x16 operands): lane = 32 h + 16 c16 + i; its 16-lane group fetches rows 8 h + 4 rd + (i >> 2),
     // the 8-byte piece (i & 3) of columns [16 c16, +16) of the wave's block, and receives column 16 c16 + i of those rows
     const int hh = lq >> 5, c16 = (lq >> 4) & 1, qp = (lq & 15) >> 2, pp = lq & 3;
@@ -1606,7 +1466,7 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #ifndef RING_SKIP_MFMA
         const unsigned char* Hb = (const unsigned char*)Hs[slot];
         const unsigned char* Ub = (const unsigned char*)Us[slot];
-        if (!(RING_EARLY_FLAG && next_full)) ring_wait(&FULL[slot], (unsigned)NRW * (unsigned)(it / NSL + 1));
+        if (!next_full) ring_wait(&FULL[slot], (unsigned)NRW * (unsigned)(it / NSL + 1));
         bf16x8 hf[3], uf[3];
 #pragma unroll
         for (int v = 0; v < 3; ++v) hf[v] = tr_pair(Hb + v * LVB + trH[0], Hb + v * LVB + trH[1]);
@@ -1636,7 +1496,7 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
         }
         f32x4 sc_cur = {0.f, 0.f, 0.f, 0.f};
         if (DH) sc_cur = *(const f32x4*)&Sc[slot][4 * q4];
-        if (RING_EARLY_FLAG) {   // the next slot's flag, looked at once: usually up already -> no poll at the top of the next trip
+        {   // the next slot's flag, looked at once: usually up already -> no poll at the top of the next trip
           const unsigned nflag = __hip_atomic_load(&FULL[(it + 1) % NSL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           next_full = it + 1 < ns && (int)(__builtin_amdgcn_readfirstlane(nflag) - (unsigned)NRW * (unsigned)((it + 1) / NSL + 1)) >= 0;
           asm volatile("" ::: "memory");
@@ -1682,7 +1542,7 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #pragma unroll
     for (int t = 0; t < 8; ++t) WT[t] = dHs ? *(const f32x4*)&W[(size_t)(16 * own + r) * D + 16 * t + 4 * q] : (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();   // flags zeroed (and the row team's staging of the head constants)
-    if (RING_PRIO) __builtin_amdgcn_s_setprio(RING_PRIO);
+    __builtin_amdgcn_s_setprio(1);
     // operand offsets inside a slot (floats), see the header for the swizzles
     //   dW A: H[4 kk + q][16 own + r]            -> + kk * 4 D
     const int ha_off = q * D + (((4 * own + (r >> 2)) ^ ((q & 1) << 2)) << 2) + (r & 3);
@@ -1692,10 +1552,10 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
     const int ua_lo = r * D + ((q ^ (r & 3)) << 2);
     const int rq = r >> 2;
     const unsigned dh_lane = (unsigned)(4 * q * D + own * 16 + r);   // this lane's element of a slot's dHs rows
-    // Software pipeline across slots: under the last MFMA step of a slot the next slot's FULL flag is looked at (not
-    // waited for) and, if it is up, its first operand set is requested, so a slot whose rows are ready starts without
-    // an LDS round trip; otherwise the wave polls at the top of the next trip.
-    constexpr int OB = RING_OPBUF;   // operand sets in flight: step s + OB - 1 is requested before the MFMAs of step s
+    // Software pipeline across slots: under the last MFMA steps of a slot the next slot's FULL flag is looked at (not
+    // waited for); if it is up the next trip starts without a poll (and, RING_PRIME, with its first operand set already
+    // requested), otherwise the wave polls at its top.
+    constexpr int OB = 2;   // operand sets in flight: step s + OB - 1 is requested before the MFMAs of step s
     float av[4];
     f32x4 bv[OB], uv[OB];
     bool primed = false, next_full = false;
@@ -1718,10 +1578,9 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
         const float* __restrict__ Hb = Hs[slot];
         const float* __restrict__ Ub = Us[slot];
         if (!primed) {
-          if (!(RING_EARLY_FLAG && next_full)) ring_wait(&FULL[slot], (unsigned)NRW * (unsigned)(it / NSL + 1));
+          if (!next_full) ring_wait(&FULL[slot], (unsigned)NRW * (unsigned)(it / NSL + 1));
           rd(Hb, Ub, 0);
         }
-        if (OB == 3) rd(Hb, Ub, 1);
         f32x4 sc_cur;
         primed = false;
         const int nslot = (it + 1) % NSL;
@@ -1732,9 +1591,9 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
           if (s + OB - 1 < 8) rd(Hb, Ub, s + OB - 1);
-          if (s == 5 && (RING_PRIME || RING_EARLY_FLAG)) nflag = __hip_atomic_load(&FULL[nslot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          if (s == 5) nflag = __hip_atomic_load(&FULL[nslot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           if (DH && s == 7) sc_cur = *(const f32x4*)&Sc[slot][4 * q];   // (requested here, not at the top: four registers less through the loop)
-          if (s == 7 && RING_EARLY_FLAG) {   // the next slot's flag was looked at two steps ago: usually up already -> no poll,
+          if (s == 7) {   // the next slot's flag was looked at two steps ago: usually up already -> no poll,
             next_full = it + 1 < ns &&       // no exposed LDS round trip at the top of the next trip
                         (int)(__builtin_amdgcn_readfirstlane(nflag) - (unsigned)NRW * (unsigned)((it + 1) / NSL + 1)) >= 0;
             asm volatile("" ::: "memory");
@@ -1814,12 +1673,6 @@ __global__ __launch_bounds__(RING_THREADS) void k_bwd_rowlocal_ring(int M, int n
 #define RL256_ROW_WAVES 8   // 8: 16 waves, 128 registers; 4: 12 waves, 168 (measured: the row team of 4 is latency-bound, 6.8 us per tile against 4.2 of MFMA)
 #endif
 #define RL256_THREADS ((RL256_ROW_WAVES + 8) * 64)
-#ifndef RL256_PRIO
-#define RL256_PRIO 1       // s_setprio of the matrix team
-#endif
-#ifndef RL256_ROW_PRIO
-#define RL256_ROW_PRIO 0   // ... of the row team
-#endif
 template <int TR>
 __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n, const float* __restrict__ dXn,
                                                           const float* __restrict__ Z, const float* __restrict__ X,
@@ -1890,11 +1743,7 @@ __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n
     auto load_row = [&](int it, int tt) {   // row (wave + NRW tt) of the workgroup's it-th tile, into register set tt % RIF
       const int t = tt % RIF;
       const int m = (t_begin + it) * TR + wave + tt * NRW;
-#ifdef RL256_SKIP_LOADS   // decomposition build (garbage results): no row streams
-      const bool ok = false;
-#else
       const bool ok = it < nt && m < M;
-#endif
       const size_t off = (size_t)m * D + lane * EPL;
       if (ok) {
         ld_row<EPL>(z[t], &Z[off]);
@@ -1913,7 +1762,6 @@ __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n
 #pragma unroll
     for (int t = 0; t < RIF; ++t) load_row(0, t);
     __syncthreads();   // flags zeroed: THE barrier of this kernel (matched by the matrix team)
-    if (RL256_ROW_PRIO) __builtin_amdgcn_s_setprio(RL256_ROW_PRIO);
     KT_STAMP_NW(0, 0, true);
     for (int it = 0; it < nt; ++it) {
       const int slot = it & 1;
@@ -2016,7 +1864,7 @@ __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n
     for (int t = 0; t < 16; ++t)
       WT[t] = dHs ? *(const f32x4*)&W[(size_t)(SW * cs + 16 * cb + r) * D + 16 * t + 4 * q] : (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();   // flags zeroed
-    if (RL256_PRIO) __builtin_amdgcn_s_setprio(RL256_PRIO);
+    __builtin_amdgcn_s_setprio(1);   // the matrix team only
     // DH: with the dHs product (a gather over Ahat^T follows) or without (dHs == NULL: nobody differentiates the layer's
     // input): a compile-time switch, so that the interleaved MFMA stream is straight-line code
     auto tile_loop = [&](auto DH_) {
@@ -2031,7 +1879,6 @@ __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n
         // the two products of the tile, one MFMA of each in turn: dW step kk (4 rows of K) holds 8 MFMAs, dHs k-step blocks
         // t = 2 kk, 2 kk + 1 hold 4 each
         f32x4 hacc = {0.f, 0.f, 0.f, 0.f};
-#ifndef RL256_SKIP_MFMA   // (decomposition build, garbage results: no products)
 #pragma unroll
         for (int kk = 0; kk < TR / 4; ++kk) {
           const int k = 4 * kk + q;
@@ -2056,7 +1903,6 @@ __global__ __launch_bounds__(RL256_THREADS) void k_bwd_rowlocal256s(int M, int n
               }
             }
         }
-#endif
         ring_arrive(&FREE[slot], lane);   // every operand of the slot is in registers (s_waitcnt lgkmcnt(0) inside)
         KT_STAMP_NW(10 + 2 * it, NRW * 64, it < 3);
         if (DH) {   // rows 16 rb + 4 q + e, column 64 cs + 16 cb + r: 64-byte row segments straight from the accumulators
@@ -2243,16 +2089,10 @@ __global__ __launch_bounds__(256) void k_reduce_partials(int P, int D, const flo
 //   one wave = 8 rows x 8 lanes; a lane holds 16 B of its row's slice; an 8-lane group walks its own row's
 //   neighbour list 8 at a time: one coalesced 32-byte load of column indices (+ values), broadcast inside the
 //   group with ds_swizzle, 8 line loads in flight per group (64 per wave), summed in list order.
-//   Waves that own a row longer than SLICED_HUB neighbours (Hi-C hubs) switch to a cooperative walk: the 8 groups
-//   share each of the wave's rows (64 neighbours per step) and are summed in a fixed butterfly order, so one hub
-//   costs len/8 instead of len serial steps and the result stays bit-reproducible.
+//   Waves for which it is cheaper (Hi-C hubs; the cost model in sliced_row_sum) switch to a cooperative walk: the 8
+//   groups share each of the wave's rows (64 neighbours per step) and are summed in a fixed butterfly order, so one
+//   hub costs len/8 instead of len serial steps and the result stays bit-reproducible.
 // ------------------------------------------------------------------------------------------
-#ifndef SLICED_HUB
-#define SLICED_HUB 192
-#endif
-#ifndef SLICED_COST_MODEL
-#define SLICED_COST_MODEL 1
-#endif
 #ifndef SLICED_COOP_OVERHEAD
 #define SLICED_COOP_OVERHEAD 3
 #endif
@@ -2313,7 +2153,6 @@ template <bool HAS_VAL, typename IT>
 __device__ __forceinline__ f32x4 sliced_row_sum(const IT* __restrict__ col, const float* __restrict__ val, int k0, int k1,
                                                 const char* __restrict__ base, unsigned lane_off, unsigned rowsh, int lane) {
   const int g = lane >> 3, j = lane & 7;
-#if SLICED_COST_MODEL
   // per-row walk: every group steps until the wave's longest row is done (8 neighbours per row and step); cooperative
   // walk: the rows one after the other, 64 neighbours per step, plus eight butterflies.  Take the cheaper one: a wave
   // whose rows are 5, 5, ..., 5, 200 neighbours long walks 11 steps together instead of 25 apart.
@@ -2324,9 +2163,6 @@ __device__ __forceinline__ f32x4 sliced_row_sum(const IT* __restrict__ col, cons
     sm += __shfl_xor(sm, o, WAVE);
   }
   if (sm + SLICED_COOP_OVERHEAD >= ((mx + 7) >> 3)) return sliced_walk<HAS_VAL, IT>(col, val, k0, k1, 8, base, lane_off, rowsh, j);
-#else
-  if (!__any(k1 - k0 > SLICED_HUB)) return sliced_walk<HAS_VAL, IT>(col, val, k0, k1, 8, base, lane_off, rowsh, j);
-#endif
   f32x4 mine = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int rr = 0; rr < 8; ++rr) {   // wave-uniform: every group helps with row rr of the wave
@@ -2425,16 +2261,10 @@ __device__ __forceinline__ f32x4 sliced_super_sum(const IT* __restrict__ col, co
 // workgroup b -> (column slice, 64-row tile).  Up to 8 slices: slice = b mod NSL, so XCD x (workgroups b = x mod 8) owns
 // slice x.  16 slices (S*D = 512 floats): two passes over the tiles, XCD x works on slice x in the first half of the
 // grid and on slice x + 8 in the second, so that one slice (not two) is hot in its L2 at a time.
-// Tuning: non-temporal accesses on the sliced kernels' once-touched streams, so that they compete less
-// with the L2-resident slice of the gathered table.  Bit 0: H store of k_aggregate_sliced; bit 1: the (1-g) dXn operand
-// of k_bwd_sliced; bit 2: its dX store.
-#ifndef SLICED_NT
-#define SLICED_NT 7   // measured (profiles/r04_sliced_nt_experiment.txt): genome epoch 4.67 -> 4.63 ms, traffic beyond L2 -6 %
-#endif
-__device__ __forceinline__ f32x4 ld_stream4(const float* p) {
-  if (SLICED_NT & 2) return __builtin_nontemporal_load((const f32x4*)p);
-  return *(const f32x4*)p;
-}
+// The sliced kernels' once-touched streams -- the H store of k_aggregate_sliced, the (1-g) dXn operand of k_bwd_sliced and
+// its dX store -- are non-temporal, so that they compete less with the L2-resident slice of the gathered table
+// (profiles/r04_sliced_nt_experiment.txt).
+__device__ __forceinline__ f32x4 ld_stream4(const float* p) { return __builtin_nontemporal_load((const f32x4*)p); }
 template <int NSL>
 __device__ __forceinline__ void sliced_block(int b, int tiles, int& slice, int& tile) {
   if (NSL <= 8) {
@@ -2506,8 +2336,7 @@ __device__ __forceinline__ void aggregate_sliced_tile(int b, int n, const int* _
                        : sliced_super_sum<HAS_VAL, IT>(col, val, t, (const char*)X, lane_off, rowsh, lane, wave);
   if (i < n) {
     if (BP) acc += bandplus_sum(bt, i, t.g0, lane);
-    if (SLICED_NT & 1) __builtin_nontemporal_store(acc * sc, (f32x4*)&H[lane_el + (size_t)i * D]);
-    else *(f32x4*)&H[lane_el + (size_t)i * D] = acc * sc;
+    __builtin_nontemporal_store(acc * sc, (f32x4*)&H[lane_el + (size_t)i * D]);
   }
 }
 
@@ -2567,9 +2396,6 @@ __device__ __forceinline__ void bwd_riders(int extra, int n, int P, const float*
 // gather; `start` is a multiple of 8, so workgroup start + e runs on XCD e mod 8 like workgroup e of k_aggregate_sliced's
 // own grid (slice <-> XCD).  Nothing in the launch waits for these workgroups and they wait for nothing.
 // riders: the workgroups [riders, riders_end) are the riders (bwd_riders).  blocks == 0: no companion.
-#ifndef CO_AGG_LAST
-#define CO_AGG_LAST 0   // 1: A/B build, the companion range behind the riders instead of in front of them (layer_bwd_impl)
-#endif
 struct CoAgg {
   int n, start, blocks, riders, riders_end;
   const int* rowptr;
@@ -2606,10 +2432,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
       aggregate_sliced_tile<S, D, HAS_VAL, IT, BP>(b - co.start, co.n, co.rowptr, (const IT*)co.col, co.val, co.rs, co.X, co.H, co.order, bt);
       return;
     }
-#ifndef BSX_NORIDERS   // (decomposition build, profiles/r06_bwd_sliced_gap.txt: the riders return at once -- gradients are garbage)
     if (b >= co.riders && b < co.riders_end)   // (what is left are the workgroups that pad the companion range to a multiple of 8)
       bwd_riders<S, D, BP>(b - co.riders, n, P, part, dW, db, dwg, dcg, accumulate, sg, reduce_slabs, hp, head_slabs, bt);
-#endif
     return;
   }
   static_assert(!(BP && HAS_VAL), "the band-plus CSR holds unit entries");
@@ -2630,9 +2454,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
   f32x4 res = (f32x4){0.f, 0.f, 0.f, 0.f}, acc;
   if (!t.super) {
     // the (1-g) dXn term first: its loads are in flight during the walk
-#ifndef BSX_NODXN      // (decomposition build: no (1-g) dXn operand)
     if (i < n) res = ld_stream4(&dXn[lane_el + (size_t)i * D]) * (1.f - gate[(size_t)s * n + i]);
-#endif
     acc = sliced_row_sum<HAS_VAL, IT>(col, val, t.k0, t.k1, (const char*)dHs, lane_off, rowsh, lane);
   } else {
     acc = sliced_super_sum<HAS_VAL, IT>(col, val, t, (const char*)dHs, lane_off, rowsh, lane, wave);
@@ -2647,11 +2469,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = dropout_keep(key, (uint32_t)(g_off + e), thresh) ? o[e] * keep_scale : 0.f;
   }
-#ifdef BSX_NOSTORE     // (decomposition build: the result leaves only if it is a number no input produces)
-  if (o[0] != 1.2345e33f) return;
-#endif
-  if (SLICED_NT & 4) __builtin_nontemporal_store(o, (f32x4*)&dX[g_off]);
-  else *(f32x4*)&dX[g_off] = o;
+  __builtin_nontemporal_store(o, (f32x4*)&dX[g_off]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2748,8 +2566,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
     if (i < n) {
       const f32x4 o = acc[p] * (rs ? rs[i] : 1.f);
       float* dst = &H[((size_t)s * n + i) * D + 4 * c];
-      if (SLICED_NT & 1) __builtin_nontemporal_store(o, (f32x4*)dst);
-      else *(f32x4*)dst = o;
+      __builtin_nontemporal_store(o, (f32x4*)dst);
     }
   }
 }
@@ -2795,8 +2612,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8))) void k
 #pragma unroll
       for (int e = 0; e < 4; ++e) o[e] = dropout_keep(key, (uint32_t)(g_off + e), thresh) ? o[e] * keep_scale : 0.f;
     }
-    if (SLICED_NT & 4) __builtin_nontemporal_store(o, (f32x4*)&dX[g_off]);
-    else *(f32x4*)&dX[g_off] = o;
+    __builtin_nontemporal_store(o, (f32x4*)&dX[g_off]);
   }
 }
 
@@ -3001,6 +2817,13 @@ static int check_shape(int n, int S, int d) {
     else if ((S_) == 1 && (d_) == 256) { if (hasval_) { CALL(1, 256, true); } else { CALL(1, 256, false); } } \
     else { if (hasval_) { CALL(2, 256, true); } else { CALL(2, 256, false); } }  \
   } while (0)
+#define SD4(S_, d_, CALLX)                      \
+  do {                                          \
+    if ((S_) == 1 && (d_) == 128) CALLX(1, 128); \
+    else if ((S_) == 2 && (d_) == 128) CALLX(2, 128); \
+    else if ((S_) == 1 && (d_) == 256) CALLX(1, 256); \
+    else CALLX(2, 256);                         \
+  } while (0)
 
 // Deeper gather batches when the gathered table is much larger than the L2s (see Gather::GU).
 #ifndef DEEP_TABLE_BYTES
@@ -3008,11 +2831,9 @@ static int check_shape(int n, int S, int d) {
 #endif
 static inline bool pick_deep(int n, int S, int d) { return (double)n * S * d * 4.0 > (double)DEEP_TABLE_BYTES; }
 
-// Tile height of the gather kernels: 16 MFMA rows (MB = 1: 8 nodes x 2 strands, or 16 nodes of one strand) at every
-// size.  A 32-row variant (the MB template parameter) existed for large chromosomes; with the shallow gather batches
-// it is slower even at 30 k nodes (layer forward 102.7 vs 92.5 us: more, smaller workgroups pack the CUs better),
-// so it is no longer instantiated.
-static inline int pick_mb(int, int) { return 1; }
+// Nodes per tile of the forward kernels (k_layer_fwd, k_layer_dense, k_layer_dense256): 16 MFMA rows at every size -- 8 nodes
+// x 2 strands, or 16 nodes of one strand.
+static inline int tile_nodes(int S) { return 16 / S; }
 
 // Events for fork/join edges between the main and the auxiliary stream.  A small pool reused round-robin;
 // never destroyed (an event may still be referenced by a captured graph).  This is the only state the
@@ -3047,25 +2868,18 @@ static void launch_aggregate_sliced(hipStream_t st, int gblocks, int n, int S, i
                                     const uint16_t* col16, const float* val, const float* rs, const float* X, float* H,
                                     const int32_t* order, bool bp = false, unsigned long long* zero_words = nullptr,
                                     int zero_count = 0) {
-#define SD4(CALLX)                         \
-  do {                                     \
-    if (S == 1 && d == 128) CALLX(1, 128); \
-    else if (S == 2 && d == 128) CALLX(2, 128); \
-    else if (S == 1 && d == 256) CALLX(1, 256); \
-    else CALLX(2, 256);                    \
-  } while (0)
   if (bp) {   // band-plus: (rowptr, col / col16) is the unit-entry CSR, the band + I half comes from the LDS window
 #define CALLBP16(S_, D_) hipLaunchKernelGGL((k_aggregate_sliced<S_, D_, false, uint16_t, true>), dim3(gblocks), dim3(512), 0, st, n, rowptr, col16, nullptr, rs, X, H, order, zero_words, zero_count)
 #define CALLBP32(S_, D_) hipLaunchKernelGGL((k_aggregate_sliced<S_, D_, false, int, true>), dim3(gblocks), dim3(512), 0, st, n, rowptr, col, nullptr, rs, X, H, order, zero_words, zero_count)
-    if (col16) SD4(CALLBP16);
-    else SD4(CALLBP32);
+    if (col16) SD4(S, d, CALLBP16);
+    else SD4(S, d, CALLBP32);
 #undef CALLBP16
 #undef CALLBP32
     return;
   }
   if (col16) {
 #define CALL16(S_, D_) hipLaunchKernelGGL((k_aggregate_sliced<S_, D_, false, uint16_t>), dim3(gblocks), dim3(512), 0, st, n, rowptr, col16, val, rs, X, H, order, zero_words, zero_count)
-    SD4(CALL16);
+    SD4(S, d, CALL16);
 #undef CALL16
     return;
   }
@@ -3099,7 +2913,7 @@ const char* cgcn_strerror(int code) {
   }
 }
 
-// the split forward (see cgcn_layer_fwd): tables from this size on; workgroups and tile height of k_layer_dense.
+// the split forward (see cgcn_layer_fwd): tables from this size on; workgroups of k_layer_dense.
 // 6 MiB since the split products (rounds 2-6: 8): the fused kernel's W operands grew from 32 to 48 registers (6 instead of 8
 // waves per SIMD under its gather) while the row-local kernel got 17 % faster, and inside a genome epoch -- inputs cold, not
 // the L2-warm loop of a single-chromosome benchmark -- the two launches win from the smallest training chromosome (6.0 MiB)
@@ -3111,9 +2925,6 @@ const char* cgcn_strerror(int code) {
 #define DENSE_MAX_BLOCKS (256 * (DENSE_WAVES_PER_SIMD / 2))   // exactly the workgroups resident at once: one round
 #endif
 static inline int dense_max_blocks(int d) { return d == 256 ? 256 : DENSE_MAX_BLOCKS; }   // d = 256 (k_layer_dense256): one workgroup per CU
-#ifndef DENSE_MB
-#define DENSE_MB 1
-#endif
 static long long fwd_split_default() {   // tuning: CGCN_FWD_SPLIT_BYTES in the environment overrides the built-in threshold
   const char* e = getenv("CGCN_FWD_SPLIT_BYTES");
   return (e && *e) ? atoll(e) : (long long)FWD_SPLIT_TABLE_BYTES;
@@ -3156,10 +2967,9 @@ static inline bool bandplus_graph(const cgcn_graph_aux* aux, const float* val) {
 static void launch_band_aggregate(hipStream_t st, int n, int S, int d, const float* rs, const float* X, float* H,
                                   unsigned long long* zw = nullptr, int zc = 0) {
   const int blocks = S * ((n + BAND_R - 1) / BAND_R);
-  if (S == 1 && d == 128) hipLaunchKernelGGL((k_band_aggregate<1, 128, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc);
-  else if (S == 2 && d == 128) hipLaunchKernelGGL((k_band_aggregate<2, 128, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc);
-  else if (S == 1 && d == 256) hipLaunchKernelGGL((k_band_aggregate<1, 256, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc);
-  else hipLaunchKernelGGL((k_band_aggregate<2, 256, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc);
+#define CALL(S_, D_) hipLaunchKernelGGL((k_band_aggregate<S_, D_, BAND_R>), dim3(blocks), dim3(512), 0, st, n, rs, X, H, zw, zc)
+  SD4(S, d, CALL);
+#undef CALL
 }
 
 // cgcn_spmm's argument checks (n_rows == 0: nothing to check, nothing to do)
@@ -3231,7 +3041,7 @@ static bool fwd_split_shape(int n, int S, int d) {
 }
 static int dense_stat_chunk(int n, int S, int d) {
   if (!fwd_split_shape(n, S, d)) return 1;
-  const int tn = 16 * DENSE_MB / S;
+  const int tn = tile_nodes(S);
   const int ntiles = (n + tn - 1) / tn;
   return (ntiles + dense_max_blocks(d) - 1) / dense_max_blocks(d);
 }
@@ -3241,7 +3051,7 @@ static int dense_stat_chunk(int n, int S, int d) {
 // launch zeroes them).  The mode is the CALLER's, per call (ABI v24): the plan below says what to allocate for it,
 // cgcn_layer_fwd is told what the plan said (colstats_rows) and never consults process state about it.
 static int acc_chunk(int n, int S, int d) {   // contiguous tiles per k_layer_dense workgroup: one round of workgroups
-  const int tn = 16 * DENSE_MB / S;
+  const int tn = tile_nodes(S);
   const int ntiles = (n + tn - 1) / tn;
   return (ntiles + dense_max_blocks(d) - 1) / dense_max_blocks(d);
 }
@@ -3254,7 +3064,7 @@ int cgcn_layer_fwd_colstats_plan(int n, int S, int d, int mode, int* rows_per_ti
     const size_t tile_bytes = (size_t)S * d * 2 * sizeof(float);
     return (int)((stat_acc_words(S, d) * 8 + tile_bytes - 1) / tile_bytes);
   }
-  const int tn = (16 * pick_mb(n, S) / S) * dense_stat_chunk(n, S, d);
+  const int tn = tile_nodes(S) * dense_stat_chunk(n, S, d);
   if (rows_per_tile) *rows_per_tile = tn;
   return (n + tn - 1) / tn;
 }
@@ -3263,7 +3073,7 @@ int cgcn_debug_layer_fwd_route(int n, int S, int d, const cgcn_graph_aux* aux, i
   const int rc = check_shape(n, S, d);
   if (rc) return rc;
   if (band_graph(aux, nullptr)) return 2;
-  const bool need_dense = colstats_rows == CGCN_COLSTATS_ROWS_ACCUMULATE || colstats_rows > 16 * DENSE_MB / S;   // see cgcn_layer_fwd
+  const bool need_dense = colstats_rows == CGCN_COLSTATS_ROWS_ACCUMULATE || colstats_rows > tile_nodes(S);   // see cgcn_layer_fwd
   return (fwd_split_shape(n, S, d) || hub_graph(aux) || (aux && aux->bp_rowptr && aux->bp_col) || need_dense) ? 1 : 0;
 }
 
@@ -3292,7 +3102,7 @@ int cgcn_layer_fwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* row
   //   -1 accumulate, THIS call zeroes the totals (its aggregation launch does: two-launch route);
   //   -2 no statistics from this call: its first launch zeroes the totals in `colstats` for a LATER call of the step;
   //   -3 accumulate into totals an earlier call zeroed (-2): any route, the fused kernel included.
-  const int tn0 = 16 * DENSE_MB / S;
+  const int tn = tile_nodes(S);
   const bool zero_only = colstats && colstats_rows == CGCN_COLSTATS_ROWS_ZERO_ONLY;
   const bool acc_pre = colstats && colstats_rows == CGCN_COLSTATS_ROWS_ACCUMULATE_ZEROED;
   const bool acc = colstats && (colstats_rows == CGCN_COLSTATS_ROWS_ACCUMULATE || acc_pre);
@@ -3302,8 +3112,8 @@ int cgcn_layer_fwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* row
       if (n < 2 || ((uintptr_t)colstats & 7)) return CGCN_ERR_BAD_ARG;
       chunk = acc_chunk(n, S, d);
     } else {
-      if (colstats_rows < tn0 || colstats_rows % tn0) return CGCN_ERR_BAD_ARG;
-      chunk = colstats_rows / tn0;
+      if (colstats_rows < tn || colstats_rows % tn) return CGCN_ERR_BAD_ARG;
+      chunk = colstats_rows / tn;
     }
   }
   unsigned long long* zw = zero_only ? (unsigned long long*)colstats : nullptr;   // zeroed by this call's FIRST launch
@@ -3333,8 +3143,6 @@ int cgcn_layer_fwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* row
   if (H_in) {
     // (accumulate mode without a sliced aggregation launch in this call -- a caller's H_in, a band graph: a memset node)
     if (acc && !acc_zeroed && hipMemsetAsync(colstats, 0, stat_acc_words(S, d) * 8, st) != hipSuccess) return CGCN_ERR_LAUNCH;
-    constexpr int MB = DENSE_MB;
-    const int tn = 16 * MB / S;
     const int ntiles = (n + tn - 1) / tn;
     const int grid = colstats ? (ntiles + chunk - 1) / chunk : (ntiles < dense_max_blocks(d) ? ntiles : dense_max_blocks(d));
     if (d == 256) {   // one 16-wave workgroup per CU (k_layer_dense256)
@@ -3346,26 +3154,23 @@ int cgcn_layer_fwd(cgcn_stream_t stream, int n, int S, int d, const int32_t* row
     }
     const bool sp = g_products.load() != CGCN_PRODUCTS_FP32_CHAIN;
 #define CALL(S_, P_) \
-    hipLaunchKernelGGL((k_layer_dense<S_, 128, MB, P_>), dim3(grid), dim3(512), 0, st, n, ntiles, H_in, X, W, b, wg, cg, Xn, Z, gate, \
+    hipLaunchKernelGGL((k_layer_dense<S_, P_>), dim3(grid), dim3(512), 0, st, n, ntiles, H_in, X, W, b, wg, cg, Xn, Z, gate, \
                        ks, th, rng_state, stream_id, colstats, chunk, acc ? 1 : 0, zw, zc)
     if (S == 1) { if (sp) CALL(1, 1); else CALL(1, 0); }
     else { if (sp) CALL(2, 1); else CALL(2, 0); }
 #undef CALL
     return launch_status();
   }
-  const int mb = pick_mb(n, S);
-  const int tn = 16 * mb / S;
   const int blocks = (n + tn - 1) / tn;
   const bool deep = pick_deep(n, S, d);
   const bool spf = g_products.load() != CGCN_PRODUCTS_FP32_CHAIN;   // (d = 128 only: d = 256 keeps the chain on every route)
-#define FWD(S_, D_, MB_, V_, DP_, P_)                                                                                 \
-  hipLaunchKernelGGL((k_layer_fwd<S_, D_, MB_, V_, DP_, (D_ == 128) ? P_ : 0>), dim3(blocks), blk, 0, st, n, rowptr, col, val, row_scale, \
+#define FWD(S_, D_, V_, DP_, P_)                                                                                      \
+  hipLaunchKernelGGL((k_layer_fwd<S_, D_, V_, DP_, (D_ == 128) ? P_ : 0>), dim3(blocks), dim3(512), 0, st, n, rowptr, col, val, row_scale, \
                      X, W, b, wg, cg, Xn, Z, H, gate, ks, th, rng_state, stream_id, colstats, acc ? 1 : 0, zw, zc)
 #define CALL(S_, D_, V_)                                                                                              \
   do {                                                                                                                \
-    const dim3 blk((D_ == 128 && CBW128 == 2) ? 256 : 512);                                                           \
-    if (deep) { if (spf) FWD(S_, D_, 1, V_, true, 1); else FWD(S_, D_, 1, V_, true, 0); }                             \
-    else { if (spf) FWD(S_, D_, 1, V_, false, 1); else FWD(S_, D_, 1, V_, false, 0); }                                \
+    if (deep) { if (spf) FWD(S_, D_, V_, true, 1); else FWD(S_, D_, V_, true, 0); }                                   \
+    else { if (spf) FWD(S_, D_, V_, false, 1); else FWD(S_, D_, V_, false, 0); }                                      \
   } while (0)
   DISPATCH_SDV(S, d, val != nullptr, CALL);
 #undef CALL
@@ -3475,10 +3280,7 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
   }
   // the head's second-stage workgroups ride in the gather launch when there is one on this stream and it does not carry
   // the optimizer step (whose workgroups would step the head's gradients while these finish them); else in the row-local one
-#ifndef HEAD_SLABS_IN_GATHER
-#define HEAD_SLABS_IN_GATHER 1   // 0: A/B, round 3's placement (profiles/r04_head_slabs_in_gather.txt)
-#endif
-  const bool head_in_gather = HEAD_SLABS_IN_GATHER && head_slabs > 0 && n > 0 && dX != nullptr && !sg.param && !(aux_stream && aux_stream != stream);
+  const bool head_in_gather = head_slabs > 0 && n > 0 && dX != nullptr && !sg.param && !(aux_stream && aux_stream != stream);
   const int head_slabs_rl = head_in_gather ? 0 : head_slabs, head_slabs_g = head_in_gather ? head_slabs : 0;
   if (!workspace || workspace_bytes < cgcn_layer_bwd_workspace_bytes(n, S, d)) return CGCN_ERR_WORKSPACE;
   if (misaligned16(workspace)) return CGCN_ERR_BAD_ARG;
@@ -3547,10 +3349,7 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
   hipLaunchKernelGGL((k_bwd_band<S_, D_, BAND_R>), dim3(bblocks + (fuse_reduce ? rslabs : 0) + head_slabs_g + sgd_blocks), dim3(512), 0, st, \
                      n, dHs, dXn, gate, dX, ks, th, rng_state, in_stream_id, bblocks, P, part, dW, db, dwg, dcg, accumulate, sg, \
                      fuse_reduce ? rslabs : 0, hp, head_slabs_g)
-    if (S == 1 && d == 128) CALLB(1, 128);
-    else if (S == 2 && d == 128) CALLB(2, 128);
-    else if (S == 1 && d == 256) CALLB(1, 256);
-    else CALLB(2, 256);
+    SD4(S, d, CALLB);
 #undef CALLB
   } else {
     // the arrays k_bwd_sliced walks: 'both' graphs the unit-entry CSR (+ the band window from LDS, BP), 16-bit indices
@@ -3563,15 +3362,10 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
       const SlicedCsr cc = sliced_csr(co->aux, co->rowptr, co->col, co->val, co->n);
       const int cblocks = (S * d / 32) * ((co->n + 63) / 64);
       // the companion range starts at a multiple of 8 workgroups (slice <-> XCD); the workgroups in between return at once.
-      // Grid order (profiles/co_aggregation_ab.txt): [backward gather | companion | riders]; the A/B build puts the
-      // companion behind the riders (+0.26 % on the genome epoch, inside the spread)
-#if CO_AGG_LAST
-      ca.start = (blocks + nriders + 7) & ~7;
-#else
+      // Grid order (profiles/co_aggregation_ab.txt): [backward gather | companion | riders]
       ca.start = (blocks + 7) & ~7;
       ca.riders = ca.start + cblocks;
       ca.riders_end = ca.riders + nriders;
-#endif
       ca.n = co->n;
       ca.blocks = cblocks;
       ca.rowptr = cc.rowptr;
@@ -3592,8 +3386,8 @@ static int layer_bwd_impl(cgcn_stream_t stream, int n, int S, int d, const int32
 #define CALLBP32(S_, D_) BSL(S_, D_, false, int, true, c.col)
 #define CALL16(S_, D_) BSL(S_, D_, false, uint16_t, false, c.col16)
 #define CALL(S_, D_, V_) BSL(S_, D_, V_, int, false, c.col)
-    if (c.bp) { if (c.col16) SD4(CALLBP16); else SD4(CALLBP32); }
-    else if (c.col16) SD4(CALL16);
+    if (c.bp) { if (c.col16) SD4(S, d, CALLBP16); else SD4(S, d, CALLBP32); }
+    else if (c.col16) SD4(S, d, CALL16);
     else DISPATCH_SDV(S, d, c.val != nullptr, CALL);
 #undef CALL
 #undef CALL16
@@ -3661,10 +3455,9 @@ int cgcn_sddmm(cgcn_stream_t stream, int n, int S, int d, const int32_t* rowptr,
   if (!rowptr || !col || !A || !B || !out || misaligned16(A) || misaligned16(B)) return CGCN_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (n + 3) / 4 < 4096 ? (n + 3) / 4 : 4096;
-  if (S == 1 && d == 128) hipLaunchKernelGGL((k_sddmm<1, 128>), dim3(blocks), dim3(256), 0, st, n, rowptr, col, A, B, out, accumulate);
-  else if (S == 2 && d == 128) hipLaunchKernelGGL((k_sddmm<2, 128>), dim3(blocks), dim3(256), 0, st, n, rowptr, col, A, B, out, accumulate);
-  else if (S == 1 && d == 256) hipLaunchKernelGGL((k_sddmm<1, 256>), dim3(blocks), dim3(256), 0, st, n, rowptr, col, A, B, out, accumulate);
-  else hipLaunchKernelGGL((k_sddmm<2, 256>), dim3(blocks), dim3(256), 0, st, n, rowptr, col, A, B, out, accumulate);
+#define CALL(S_, D_) hipLaunchKernelGGL((k_sddmm<S_, D_>), dim3(blocks), dim3(256), 0, st, n, rowptr, col, A, B, out, accumulate)
+  SD4(S, d, CALL);
+#undef CALL
   return launch_status();
 }
 

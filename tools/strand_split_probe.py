@@ -3,8 +3,8 @@
 Routes timed with HIP events, same inputs, results compared bitwise:
   fused S=2          k_layer_fwd<2,256>                       (the product route at d = 256)
   fused 2 x S=1      k_layer_fwd<1,256> on X[0], then on X[1]  (table per launch = n KiB instead of 2n KiB)
-  split S=2          k_aggregate_sliced<2,256> (16 slices, strand = pass) + k_layer_dense<2,256>
-  split 2 x S=1      k_aggregate_sliced<1,256> + k_layer_dense<1,256> per strand
+  split S=2          k_aggregate_sliced<2,256> (16 slices, strand = pass) + k_layer_dense256<2>
+  split 2 x S=1      k_aggregate_sliced<1,256> + k_layer_dense256<1> per strand
 python tools/strand_split_probe.py [n ...]"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
