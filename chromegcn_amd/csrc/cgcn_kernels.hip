@@ -2124,20 +2124,70 @@ struct SlicedBcast<0, HAS_VAL> {
 // IT: column index type -- int32, or uint16 when the graph has at most 65 536 columns (every chromosome of the genome):
 // the index list is re-read once per column slice (8 x 2 MB per launch at int32), and the 16-bit list halves that:
 // 0 ... -7 % per launch (profiles/r03_u16_index_experiment.txt), sums bit-identical.
+#ifdef SLICED_TIMING  // tuning build only (tools/sliced_stamps.py): timestamps of every workgroup of one selected gather launch
+// slot i of workgroup b (100 MHz wall clock): 0 workgroup start, 1 order / rowptr returned, 2 first chunk of column indices
+// returned, 3 its table lines returned (2, 3: thread 0's first chunk; 0 when its row is empty), 4 walk done, 5 store done,
+// 7 the launch's grid size.  Every stamp waits for all memory operations in flight, so the first chunk runs serialised.
+// The launch is selected by (n, kind: 0 aggregation body / 1 backward gather, grid size or 0 = any): in a replayed epoch the
+// last launch that matches is the one left in the table.
+constexpr int SL_WGS = 8192;
+__device__ unsigned long long sl_stamps[SL_WGS * 8];
+__device__ int sl_sel[3];
+__shared__ int sl_on;   // written and read by thread 0 only
+extern "C" int cgcn_debug_sliced_stamps(unsigned long long* out, int n, int kind, int grid) {
+  const int sel[3] = {n, kind, grid};
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(sl_stamps), sizeof(unsigned long long) * SL_WGS * 8) != hipSuccess) return -1;
+  void* p = nullptr;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(sl_stamps)) != hipSuccess || hipMemset(p, 0, sizeof(unsigned long long) * SL_WGS * 8) != hipSuccess) return -1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(sl_sel), sel, sizeof(sel)) == hipSuccess ? 0 : -1;
+}
+#define SL_BEGIN(kind_, n_)                                                                                              \
+  do {                                                                                                                   \
+    if (threadIdx.x == 0) {                                                                                              \
+      sl_on = blockIdx.x < SL_WGS && sl_sel[0] == (n_) && sl_sel[1] == (kind_) && (sl_sel[2] == 0 || sl_sel[2] == (int)gridDim.x); \
+      if (sl_on) {                                                                                                       \
+        unsigned long long* s_ = &sl_stamps[blockIdx.x * 8];                                                             \
+        s_[2] = s_[3] = 0ull;                                                                                            \
+        s_[7] = gridDim.x;                                                                                               \
+        s_[0] = wall_clock64();                                                                                          \
+      }                                                                                                                  \
+    }                                                                                                                    \
+  } while (0)
+#define SL_STAMP(i)                                                                                                      \
+  do {                                                                                                                   \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                          \
+    if (threadIdx.x == 0 && sl_on) sl_stamps[blockIdx.x * 8 + (i)] = wall_clock64();                                     \
+  } while (0)
+#define SL_STAMP_FIRST(i, cond, v)                                                                                       \
+  do {                                                                                                                   \
+    if (cond) {                                                                                                          \
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(v)::"memory");                                                 \
+      if (threadIdx.x == 0 && sl_on && sl_stamps[blockIdx.x * 8 + (i)] == 0ull) sl_stamps[blockIdx.x * 8 + (i)] = wall_clock64(); \
+    }                                                                                                                    \
+  } while (0)
+#else
+#define SL_BEGIN(kind_, n_)
+#define SL_STAMP(i)
+#define SL_STAMP_FIRST(i, cond, v)
+#endif
+
 template <bool HAS_VAL, typename IT>
 __device__ __forceinline__ f32x4 sliced_walk(const IT* __restrict__ col, const float* __restrict__ val, int k0, int k1,
                                              int step, const char* __restrict__ base, unsigned lane_off, unsigned rowsh, int j) {
   f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (int k = k0; k < k1; k += step) {
     const int kk = min(k + j, k1 - 1);   // ragged tail: re-read the last neighbour (an L1 hit), add a selected zero
-    const int myc = (int)col[kk];
+    int myc = (int)col[kk];
     const float myv = HAS_VAL ? val[kk] : 0.f;
+    SL_STAMP_FIRST(2, k == k0, myc);
     unsigned off[8];
     float w[8];
     SlicedBcast<8, HAS_VAL>::run(off, w, myc, myv, rowsh, lane_off);
     f32x4 t[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) t[u] = *(const f32x4*)(base + (size_t)off[u]);
+    SL_STAMP_FIRST(3, k == k0, t[7][0]);
     const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -2277,6 +2327,29 @@ __device__ __forceinline__ void sliced_block(int b, int tiles, int& slice, int& 
   }
 }
 
+// First-touch warming.  Inside a train step the producer of the gathered table ran on other XCDs, so every line of an XCD's
+// slice misses its L2 the first time the walk asks for it, and the workgroups that start with the launch reach their first
+// table line only behind three dependent loads (order -> rowptr -> col) during which the fabric carries nothing.  The first
+// SLICED_WARM_WGS workgroups of a slice (tile < SLICED_WARM_WGS: they start with the launch) therefore touch, before their own
+// chain, one word of every 128-byte line of the slice -- thread t of warming workgroup w: nodes 512 w + t, + 512 * (number of
+// warming workgroups), ... < n.  The values go nowhere: the walk's demand misses become hits, or hits in flight.  Plain
+// loads (they must allocate in L2), issued as relaxed wavefront-scope atomic loads only so that the compiler keeps a load
+// whose value nobody reads; no cache bit and no wait comes with that scope.  Loads return in order, so a warming workgroup's
+// own chain waits for its share: ceil(n / 4096) lines per thread.  The 16-slice instances run two passes and warm each
+// pass's slice at its start.  Measured (profiles/sliced_cold_start_ab.txt): 8 workgroups per slice -1.7 % of the genome epoch,
+// 4 / 16 / 32 less, 1 / 2 slower than none; touching rowptr / order or the index list as well, or issuing the touches behind
+// the workgroup's own descriptors, loses part of it.  0: off (A/B).
+#ifndef SLICED_WARM_WGS
+#define SLICED_WARM_WGS 8
+#endif
+// T + slice_el: row 0 of the slice (D floats per row, n rows); tile / tiles: this workgroup's tile and the slice's tile count
+__device__ __forceinline__ void sliced_warm(const float* __restrict__ T, size_t slice_el, int D, int n, int tile, int tiles) {
+  if (SLICED_WARM_WGS <= 0 || tile >= SLICED_WARM_WGS) return;
+  const int stride = 512 * min(tiles, SLICED_WARM_WGS);
+  for (int l = tile * 512 + (int)threadIdx.x; l < n; l += stride)   // node l < n of this slice: inside the table
+    (void)__hip_atomic_load((const int*)(T + slice_el + (size_t)l * D), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
 constexpr int BAND_W = 7;   // the reference's constant_range (utils/util_methods.py:147)
 // ------------------------------------------------------------------------------------------
 // BP ("band plus", adj_type 'both': utils/util_methods.py:168-171 -- Hi-C + the +-7 band + I, values 1 or 2, not
@@ -2324,7 +2397,10 @@ __device__ __forceinline__ void aggregate_sliced_tile(int b, int n, const int* _
   sliced_block<NSL>(b, (n + 63) / 64, slice, tile);
   const size_t slice_el = (size_t)(slice / QPR) * n * D + (slice % QPR) * 32;
   const size_t lane_el = slice_el + (lane & 7) * 4;
+  SL_BEGIN(0, n);
+  sliced_warm(X, slice_el, D, n, tile, (n + 63) / 64);
   const SlicedTile t = sliced_tile(rowptr, order, n, tile, wave, lane);
+  SL_STAMP(1);
   if (BP) {
     bandplus_stage(bt, X, slice_el, n, t.g0, D);
     __syncthreads();
@@ -2334,10 +2410,12 @@ __device__ __forceinline__ void aggregate_sliced_tile(int b, int n, const int* _
   const unsigned lane_off = (unsigned)(lane_el * 4), rowsh = D == 128 ? 9u : 10u;
   f32x4 acc = !t.super ? sliced_row_sum<HAS_VAL, IT>(col, val, t.k0, t.k1, (const char*)X, lane_off, rowsh, lane)
                        : sliced_super_sum<HAS_VAL, IT>(col, val, t, (const char*)X, lane_off, rowsh, lane, wave);
+  SL_STAMP(4);
   if (i < n) {
     if (BP) acc += bandplus_sum(bt, i, t.g0, lane);
     __builtin_nontemporal_store(acc * sc, (f32x4*)&H[lane_el + (size_t)i * D]);
   }
+  SL_STAMP(5);
 }
 
 // (grid: NSL * ceil(n / 64) workgroups of 512)
@@ -2444,7 +2522,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
   const int s = slice / QPR;
   const size_t slice_el = (size_t)s * n * D + (slice % QPR) * 32;
   const size_t lane_el = slice_el + (lane & 7) * 4;
+  SL_BEGIN(1, n);
+  sliced_warm(dHs, slice_el, D, n, tile, (n + 63) / 64);
   const SlicedTile t = sliced_tile(rowptr, order, n, tile, wave, lane);
+  SL_STAMP(1);
   if (BP) {   // the band + I half of Ahat^T dHs (Ahat is symmetric) from a window of the table staged once per workgroup
     bandplus_stage(bt, dHs, slice_el, n, t.g0, D);
     __syncthreads();
@@ -2460,8 +2541,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
     acc = sliced_super_sum<HAS_VAL, IT>(col, val, t, (const char*)dHs, lane_off, rowsh, lane, wave);
     if (i < n) res = ld_stream4(&dXn[lane_el + (size_t)i * D]) * (1.f - gate[(size_t)s * n + i]);
   }
+  SL_STAMP(4);
   if (BP && i < n) acc += bandplus_sum(bt, i, t.g0, lane);
+#ifdef SLICED_TIMING
+  if (i >= n) {
+    SL_STAMP(5);
+    return;
+  }
+#else
   if (i >= n) return;
+#endif
   const size_t g_off = lane_el + (size_t)i * D;
   f32x4 o = res + acc;
   if (thresh) {
@@ -2470,6 +2559,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(HAS_VAL ? 6
     for (int e = 0; e < 4; ++e) o[e] = dropout_keep(key, (uint32_t)(g_off + e), thresh) ? o[e] * keep_scale : 0.f;
   }
   __builtin_nontemporal_store(o, (f32x4*)&dX[g_off]);
+  SL_STAMP(5);
 }
 
 // ------------------------------------------------------------------------------------------
