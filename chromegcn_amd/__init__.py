@@ -4,6 +4,8 @@ Public surface mirrors the reference modules it replaces (see layers.py / graph.
 from .ablation import label_pair_ablation  # noqa: F401
 from .curves import (Curves, optimal_cutoff_host, optimal_cutoffs, pr_curve_host, pr_curves, roc_curve_host,  # noqa: F401
                      roc_curves)
+from .effects import (WindowEffects, effect_rows_host, knockout_map, knockout_map_host, window_effects,  # noqa: F401
+                      window_effects_host)
 from .embed import class_embeddings  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
 from .compare import compare_labels  # noqa: F401
@@ -33,4 +35,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "threshold_metrics_host", "HicNormError", "contact_matrix_host", "kr_balance_host",
            "hic_norm_vector_host", "hic_norm_vector", "distance_sums_host", "expected_from_sums",
            "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host",
-           "LabelStats", "label_stats", "label_stats_split", "label_stats_host", "compare_labels"]
+           "LabelStats", "label_stats", "label_stats_split", "label_stats_host", "compare_labels",
+           "WindowEffects", "window_effects", "window_effects_host", "effect_rows_host", "knockout_map", "knockout_map_host"]

@@ -143,6 +143,12 @@ _HEADER = {
                                         "cooccurrence accumulate:i"),
     "cgcn_labelstats_graph": (_c_int, "stream n:i C:i nnz:ll rowptr col val label_bits label_bits_bytes:z degree_sum "
                                       "contact_pairs n_entries accumulate:i"),
+    "cgcn_effects_workspace_bytes": (_c_sz, "n_inst:i S:i d:i layers:i"),
+    "cgcn_effects_plan": (_c_int, "stream n:i rowptr_t col_t n_var:i windows counts diag_pos"),
+    "cgcn_effects_rows1": (_c_int, "stream n:i S:i d:i rowptr_t col_t val_t row_scale X0 H1 windows alt offsets diag_pos "
+                                   "n_var:i own:i n_inst:i H_inst X_inst rows"),
+    "cgcn_effects_rows2": (_c_int, "stream n:i S:i d:i rowptr col val row_scale rowptr_t col_t X1 H2 windows offsets diag_pos "
+                                   "n_var:i own:i n_inst:i X1_inst H_out X_res"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -618,3 +618,49 @@ def ablation_reduce(logits, pos_lists, pos_counts, label, col_label, removed, ba
     S, n, C = logits.shape
     _lib.call("cgcn_ablation_reduce", n=n, S=S, C=C, logits=logits, pos_lists=pos_lists, pos_counts=pos_counts,
               label=int(label), col_label=int(col_label), removed=removed, base=base, M=M)
+
+
+# -- window effects (chromegcn_amd/effects.py; cgcn_effects_* in include/chromegcn.h) -----------------------------------
+def effects_workspace_bytes(n_inst, S, d, layers):
+    """bytes of the restricted route's workspace for a batch of n_inst instances (0: unsupported shape)"""
+    return _lib.query("cgcn_effects_workspace_bytes", n_inst=int(n_inst), S=int(S), d=int(d), layers=int(layers))
+
+
+def effects_plan(graph: ChromGraph, windows):
+    """windows int32 [M] on the graph's device -> (counts int32 [M]: instances per variant, diag_pos int32 [M]: position of
+    the stored diagonal in the transposed row, -1 without one)"""
+    M = int(windows.numel())
+    counts = torch.empty(max(M, 1), device=windows.device, dtype=torch.int32)[:M]
+    diag = torch.empty(max(M, 1), device=windows.device, dtype=torch.int32)[:M]
+    _lib.call("cgcn_effects_plan", n=graph.n, rowptr_t=graph.rowptr_t, col_t=graph.col_t, n_var=M, windows=windows,
+              counts=counts, diag_pos=diag)
+    return counts, diag
+
+
+def effects_rows1(graph: ChromGraph, x0, h1, windows, alt, offsets, diag_pos, n_var, own, n_inst, h_inst, x_inst, rows):
+    """cgcn_effects_rows1: the layer-1 instance rows of n_var variants (windows, alt, offsets, diag_pos: views that start at
+    the batch's first variant) into h_inst / x_inst [S][n_inst][d]; rows (or None) gets the window of every instance"""
+    S, n, d = x0.shape
+    _lib.call("cgcn_effects_rows1", n=n, S=S, d=d, rowptr_t=graph.rowptr_t, col_t=graph.col_t, val_t=graph.val_t,
+              row_scale=graph.row_scale, X0=x0, H1=h1, windows=windows, alt=alt, offsets=offsets, diag_pos=diag_pos,
+              n_var=int(n_var), own=1 if own else 0, n_inst=int(n_inst), H_inst=h_inst, X_inst=x_inst, rows=rows)
+
+
+def effects_rows2(graph: ChromGraph, x1, h2, windows, offsets, diag_pos, n_var, own, n_inst, x1_inst, h_out, x_res):
+    """cgcn_effects_rows2: the layer-2 rows of the read-out instances (own: instance 0 of every variant) from the instances'
+    layer-1 output x1_inst [S][n_inst][d]; x_res (needed when own) gets their residual input"""
+    S, n, d = x1.shape
+    _lib.call("cgcn_effects_rows2", n=n, S=S, d=d, rowptr=graph.rowptr, col=graph.col, val=graph.val, row_scale=graph.row_scale,
+              rowptr_t=graph.rowptr_t, col_t=graph.col_t, X1=x1, H2=h2, windows=windows, offsets=offsets, diag_pos=diag_pos,
+              n_var=int(n_var), own=1 if own else 0, n_inst=int(n_inst), X1_inst=x1_inst, H_out=h_out, X_res=x_res)
+
+
+def layer_dense_rows(h_in, x, params, graph: ChromGraph, xn, gate):
+    """The row-local part of one eval gated layer on a table of rows [S, rows, d] whose aggregation is already there:
+    cgcn_layer_fwd with H_in (it then launches the row-local kernel alone and never reads the graph arrays, which it only
+    requires to be non-NULL) into the caller's xn [S, rows, d] and gate [S, rows]."""
+    S, rows, d = x.shape
+    weight, bias, wg, cg = params
+    _lib.call("cgcn_layer_fwd", n=rows, S=S, d=d, rowptr=graph.rowptr, col=graph.col, val=None, row_scale=None, X=x, W=weight,
+              b=bias, wg=wg, cg=cg, Xn=xn, Z=None, H=None, gate=gate, dropout_p=0.0, rng_state=None, stream_id=0, H_in=h_in,
+              colstats=None, colstats_rows=0, aux=None)

@@ -1116,6 +1116,62 @@ int cgcn_labelstats_graph(cgcn_stream_t stream, int n, int C, long long nnz, con
                           const float *val, const void *label_bits, size_t label_bits_bytes, long long *degree_sum,
                           long long *contact_pairs, long long *n_entries, int accumulate);
 
+/*
+ * Window effects through the Hi-C graph (chromegcn_amd/effects.py).  Additions to ABI 26 like the
+ * functions above: CGCN_ABI_VERSION stays 26, nothing above changes.
+ *
+ * Variant m replaces the input row of window u = windows[m] by alt[m] ([n_var][S][d]) in both strands of an eval forward.
+ * Its INSTANCES are the rows whose layer-1 value changes: instance 0 is u itself; after it comes every v != u with a stored
+ * A[v, u], in the stored order of row u of the transpose (rowptr_t, col_t, val_t; rows sorted and duplicate-free).  A self
+ * loop does not repeat u, and a graph without a stored diagonal still has instance 0.
+ *
+ * cgcn_effects_plan: counts [n_var] (instances of every variant, >= 1) and diag_pos [n_var] (position of the stored (u, u)
+ * inside the transposed row, -1 without one).  The caller forms offsets int64 [n_var + 1] = exclusive prefix sums.
+ *
+ * The instance tables are [S][rows][d] fp32, i.e. feature tables with n = rows.  A call covers the n_var variants whose
+ * windows, alt, offsets and diag_pos entries the pointers start at (a batch: offsets[0] need not be 0).
+ *   own = 0: table row i is the instance offsets[0] + i of the batch; n_inst = offsets[n_var] - offsets[0].
+ *   own = 1: table row i is instance 0 of variant i; n_inst = n_var.
+ *
+ * cgcn_effects_rows1, layer 1, from the unperturbed layer input X0 [S, n, d] and its saved aggregation H1 [S, n, d]
+ * (cgcn_layer_fwd's H): for the instance with window v
+ *   H_inst = H1[s, v] + (row_scale[v] * val_t[v, u]) * (alt[m, s] - X0[s, u])   one fused multiply-add per element
+ *            (val_t NULL: 1; row_scale NULL: 1; instance 0 without a stored diagonal: H1[s, u] unchanged),
+ *   X_inst = alt[m, s] for instance 0, X0[s, v] otherwise (the layer's residual input),
+ *   rows[i] = v (rows may be NULL).
+ * cgcn_layer_fwd with H_in = H_inst, X = X_inst and n = n_inst then gives the instances' layer-1 output.
+ *
+ * cgcn_effects_rows2, layer 2, from the unperturbed X1, H2 [S, n, d] and the instances' layer-1 output X1_inst
+ * [S][n_inst][d] (always the own = 0 table of the same batch): for every read-out row (own as above; n_out = n_var or
+ * n_inst rows)
+ *   H_out = H2[s, v] + row_scale[v] * sum_w val[v, w] * (X1_inst[s, instance of w] - X1[s, w])
+ * over the stored entries w of row v of (rowptr, col, val) that are instances of the same variant (w = u is instance 0; else
+ * w is looked up in the transposed row of u), added in ascending w; X_res = X1_inst[s, the row's own instance] (required
+ * when own = 1, may be NULL when own = 0: X1_inst is then the residual table itself).
+ *
+ * cgcn_effects_workspace_bytes: what chromegcn_amd/effects.py carves for a batch of n_inst instances, or 0 when unsupported:
+ *   [H_inst][X_inst][X1_inst][X2_inst: layers == 2] of n_inst * S * d fp32 each, [gate: n_inst * S fp32],
+ * each part starting at a 256-byte boundary.
+ *
+ * Enqueue only: no allocation, no synchronisation, caller-owned buffers, legal under graph capture.  No atomics: results are
+ * bit-identical from call to call.  S must be 2 and d 128 or 256, else CGCN_ERR_UNSUPPORTED (layers outside {1, 2}: 0 bytes);
+ * NULL required buffers, negative sizes, a table that is not 16-byte aligned: CGCN_ERR_BAD_ARG, before any launch.
+ */
+size_t cgcn_effects_workspace_bytes(int n_inst, int S, int d, int layers);
+
+int cgcn_effects_plan(cgcn_stream_t stream, int n, const int32_t *rowptr_t, const int32_t *col_t, int n_var,
+                      const int32_t *windows, int32_t *counts, int32_t *diag_pos);
+
+int cgcn_effects_rows1(cgcn_stream_t stream, int n, int S, int d, const int32_t *rowptr_t, const int32_t *col_t,
+                       const float *val_t, const float *row_scale, const float *X0, const float *H1, const int32_t *windows,
+                       const float *alt, const long long *offsets, const int32_t *diag_pos, int n_var, int own, int n_inst,
+                       float *H_inst, float *X_inst, int32_t *rows);
+
+int cgcn_effects_rows2(cgcn_stream_t stream, int n, int S, int d, const int32_t *rowptr, const int32_t *col, const float *val,
+                       const float *row_scale, const int32_t *rowptr_t, const int32_t *col_t, const float *X1, const float *H2,
+                       const int32_t *windows, const long long *offsets, const int32_t *diag_pos, int n_var, int own, int n_inst,
+                       const float *X1_inst, float *H_out, float *X_res);
+
 #ifdef __cplusplus
 }
 #endif
