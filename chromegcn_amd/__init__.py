@@ -17,6 +17,8 @@ from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_no
 from .hicdist import (distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
                       hic_expected_vector)
 from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
+from .nullgraph import (NullGraphTest, null_chrom_graph, null_graph, null_graph_host, null_graph_test,  # noqa: F401
+                        null_statistics)
 from .pairs import ReadPairs, bin_read_pairs_host, pairs_to_contacts_host  # noqa: F401
 from .layers import ChromeGCN, GraphConvolution  # noqa: F401
 from .thresholds import (ThresholdCounts, best_thresholds, metrics_from_counts, threshold_counts,  # noqa: F401
@@ -36,4 +38,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "hic_norm_vector_host", "hic_norm_vector", "distance_sums_host", "expected_from_sums",
            "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host",
            "LabelStats", "label_stats", "label_stats_split", "label_stats_host", "compare_labels",
-           "WindowEffects", "window_effects", "window_effects_host", "effect_rows_host", "knockout_map", "knockout_map_host"]
+           "WindowEffects", "window_effects", "window_effects_host", "effect_rows_host", "knockout_map", "knockout_map_host",
+           "NullGraphTest", "null_graph", "null_graph_host", "null_chrom_graph", "null_graph_test", "null_statistics"]

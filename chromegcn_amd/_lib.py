@@ -149,6 +149,9 @@ _HEADER = {
                                    "n_var:i own:i n_inst:i H_inst X_inst rows"),
     "cgcn_effects_rows2": (_c_int, "stream n:i S:i d:i rowptr col val row_scale rowptr_t col_t X1 H2 windows offsets diag_pos "
                                    "n_var:i own:i n_inst:i X1_inst H_out X_res"),
+    "cgcn_null_graph_workspace_bytes": (_c_sz, "n:i nnz:ll capacity:ll model:i"),
+    "cgcn_null_graph": (_c_int, "stream n:i nnz:ll rowptr col model:i seed:ll rounds:i capacity:ll rowptr_out col_out sizes "
+                                "workspace workspace_bytes:z"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -537,14 +537,18 @@ class HicContacts:
         return rowptr, col, sizes
 
     def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
-              norm_args=None, min_distance_bp=0, expected=None, expected_args=None):
+              norm_args=None, min_distance_bp=0, expected=None, expected_args=None, null=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
         host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back.  norm: a vector,
         None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords).  min_distance_bp,
-        expected, expected_args: build_raw's."""
+        expected, expected_args: build_raw's.  null = (model, seed): the matrix is replaced by its null graph
+        (chromegcn_amd.nullgraph) before the normalisation; return_raw then returns the null matrix."""
         rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
                                             norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected,
                                             expected_args=expected_args)
+        if null is not None:
+            from . import nullgraph
+            rowptr, col, sizes = nullgraph.null_graph((rowptr, col), model=null[0], seed=null[1], device=self.device)
         n = int(rowptr.numel()) - 1
         g = G.normalize_device_csr(adj_type, n, rowptr, col, None, self.device)
         if not return_raw:
@@ -555,15 +559,17 @@ class HicContacts:
 
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
-                    return_raw=False, window_bp=None, norm_args=None, min_distance_bp=0, expected=None, expected_args=None):
+                    return_raw=False, window_bp=None, norm_args=None, min_distance_bp=0, expected=None, expected_args=None,
+                    null=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
     `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
     coarser than the windows and stand for their expanded file (the module's docstring).  min_distance_bp, expected (None, a
-    vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring)."""
+    vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring).  null:
+    HicContacts.build's."""
     _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
     return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp,
-                   norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args)
+                   norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args, null=null)
 
 
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
@@ -574,7 +580,7 @@ def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",
                                sizes: Optional[Dict[str, int]] = None, window_bp=None,
                                compute_norm: bool = False, min_distance_bp=0, expected=None,
-                               expected_args=None) -> Dict[str, G.ChromGraph]:
+                               expected_args=None, null=None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
@@ -582,10 +588,14 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
     (`-hic_compute_norm`): a `hicnorm` of 'KR' / 'VC' / 'SQRTVC' that the cache lacks is computed from its records.
     min_distance_bp (`-hic_min_distance`), expected (`-hic_expected`: "auto", the vector computed from each cache's records
     with the vector the call scores with; any other name: the vector the cache stores under it, tools/hic_ingest.py
-    --compute-expected writes eRAW / eKR / eVC / eSQRTVC), expected_args: build_hic_graph's."""
+    --compute-expected writes eRAW / eKR / eVC / eSQRTVC), expected_args: build_hic_graph's.  null = (model, seed)
+    (`-hic_null`, `-hic_null_seed`): every matrix is replaced by its null graph before the normalisation, chromosome index c
+    of the list with nullgraph.replicate_seed(seed, 0, c, len(chroms))."""
     from . import hicnorm as HN
+    from . import nullgraph
     out = {}
-    for chrom in chroms:
+    chroms = list(chroms)
+    for ci, chrom in enumerate(chroms):
         c = load_contacts_cache(contact_cache_path(root, chrom))
         if c.window_start is None:
             raise ValueError("%s holds no window list" % contact_cache_path(root, chrom))
@@ -606,5 +616,7 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
             ex = c.norms[expected]
         out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device,
-                                     min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args, **up)
+                                     min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args,
+                                     null=None if null is None else (null[0], nullgraph.replicate_seed(null[1], 0, ci, len(chroms))),
+                                     **up)
     return out

@@ -85,10 +85,14 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
     p = torch.as_tensor(all_predictions).to(device=device, dtype=torch.float32)
     t = torch.as_tensor(all_targets).to(device=device, dtype=torch.float32)
     C = p.shape[1]
-    host = _metrics_raw(p, t, 0.5, nonneg=True).cpu()          # ONE device-to-host copy: results + the `bad` word
-    if int(host[4 * C:].view(torch.int32).item()) != 0:        # scores that are not probabilities: the general path
-        host = _metrics_raw(p, t, 0.5, nonneg=False).cpu()
-    m = {k: v.double().numpy() for k, v in _split(host, C).items()}
+    empty = p.shape[0] == 0   # a split without a chromosome (-synthetic_chroms chr21,chr22 has no validation one): all NaN
+    if empty:
+        m = {k: np.full(C, np.nan) for k in ("auroc", "aupr", "recall_at_fdr", "average_precision")}
+    else:
+        host = _metrics_raw(p, t, 0.5, nonneg=True).cpu()          # ONE device-to-host copy: results + the `bad` word
+        if int(host[4 * C:].view(torch.int32).item()) != 0:        # scores that are not probabilities: the general path
+            host = _metrics_raw(p, t, 0.5, nonneg=False).cpu()
+        m = {k: v.double().numpy() for k, v in _split(host, C).items()}
     auc = m["auroc"][~np.isnan(m["auroc"])]
     aupr = m["aupr"][~np.isnan(m["aupr"])]
     fdr = m["recall_at_fdr"][~np.isnan(m["recall_at_fdr"])]
@@ -108,7 +112,7 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
         out.update(group_means(m, label_groups))
     if br_threshold is None:
         br_threshold = getattr(args, "br_threshold", None)
-    if br_threshold is not None:
+    if br_threshold is not None and not empty:
         from . import thresholds
         tm = thresholds.threshold_metrics(p, t, float(br_threshold))
         out.update({k: float(tm[k][0]) for k in thresholds.METRIC_KEYS})

@@ -9,7 +9,9 @@ optimizer (utils/util_methods.py:14-19) and run the epoch loop (runner.py:25-62)
 Inputs are the reference's own files: `<feat_dir>/chrom_feature_dict_{train,valid,test}.pt`
 (utils/util_methods.py:183-199) and `<graph_root>/{split}_graphs_{hicsize}_{hicnorm}norm.pkl`
 (data/7create_graph_new.py:197-202), or with `-hic_contacts DIR` the contact caches `DIR/<chrom>.cghic` from which the graphs
-are built on the GPU for any `-hicsize` / `-hicnorm` (chromegcn_amd/hic.py).  `-synthetic` replaces them by the seeded GM12878-shaped stand-in."""
+are built on the GPU for any `-hicsize` / `-hicnorm` (chromegcn_amd/hic.py).  `-synthetic` replaces them by the seeded GM12878-shaped stand-in.
+`-hic_null distance|degree|uniform` replaces every Hi-C matrix, whatever its source, by its null graph (chromegcn_amd/nullgraph.py):
+the control run that tells what the real contacts add."""
 from __future__ import annotations
 
 import argparse
@@ -43,6 +45,11 @@ def parse(argv=None):
     ap.add_argument("-hic_expected", action="store_true",
                     help="-hic_contacts: score a contact by observed / expected, the expected vector computed from the cache's "
                          "records on the GPU with the run's -hicnorm")
+    ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
+                    help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
+                         "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
+    ap.add_argument("-hic_null_seed", type=int, default=0,
+                    help="-hic_null: chromosome index c of a split's K chromosomes draws with seed + c")
     ap.add_argument("-window_size", type=int, default=1000)          # config_args.py:9
     ap.add_argument("-adj_type", type=str, default="hic", choices=["constant", "hic", "both", "none"])
     ap.add_argument("-gcn_layers", type=int, default=2)              # config_args.py:40
@@ -83,7 +90,24 @@ def summarize_data(data, dev, out=None):
     return stats
 
 
+def null_graphs(graphs, opt, dev):
+    """-hic_null: {chrom: matrix} of one split -> {chrom: ChromGraph of the null graph, normalised by opt.adj_type}; the
+    chromosome at index c of the K in the split draws with nullgraph.replicate_seed(opt.hic_null_seed, 0, c, K)"""
+    from . import nullgraph
+    seed, K = getattr(opt, "hic_null_seed", 0), len(graphs)
+    return {c: nullgraph.null_chrom_graph(a, opt.adj_type, opt.hic_null, nullgraph.replicate_seed(seed, 0, i, K), device=dev)
+            for i, (c, a) in enumerate(graphs.items())}
+
+
 def load_inputs(opt):
+    data, graphs = _load_inputs(opt)
+    if getattr(opt, "hic_null", None) and opt.adj_type in ("hic", "both") and not opt.hic_contacts:
+        dev = torch.device("cuda", opt.gpu_id)   # (contact caches: graphs_from_contact_caches has done it, before the band)
+        graphs = {sp: null_graphs(g, opt, dev) if g else g for sp, g in graphs.items()}
+    return data, graphs
+
+
+def _load_inputs(opt):
     data, graphs = {}, {}
     if opt.synthetic:
         for sp in ("train", "valid", "test"):
@@ -106,7 +130,9 @@ def load_inputs(opt):
                                                         window_bp=opt.window_size if opt.hic_upsample else None,
                                                         compute_norm=opt.hic_compute_norm,
                                                         min_distance_bp=opt.hic_min_distance,
-                                                        expected="auto" if opt.hic_expected else None)
+                                                        expected="auto" if opt.hic_expected else None,
+                                                        null=((opt.hic_null, getattr(opt, "hic_null_seed", 0))
+                                                              if getattr(opt, "hic_null", None) else None))
         elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:

@@ -1172,6 +1172,45 @@ int cgcn_effects_rows2(cgcn_stream_t stream, int n, int S, int d, const int32_t 
                        const int32_t *windows, const long long *offsets, const int32_t *diag_pos, int n_var, int own, int n_inst,
                        const float *X1_inst, float *H_out, float *X_res);
 
+/*
+ * Random contact graphs that keep the distance histogram or the degrees of a Hi-C graph (chromegcn_amd/nullgraph.py, whose
+ * docstring is the rule).  Additions to ABI 26 like the functions above: CGCN_ABI_VERSION stays 26,
+ * nothing above changes.
+ *
+ * Input: the CSR (rowptr [n + 1], col) of a graph on n windows, nnz = the number of entries col holds for it (rowptr is
+ * clamped to it); only the entries (i, j) with j > i count, in storage order.  model: CGCN_NULL_DISTANCE (placement with
+ * `rounds` rounds of retries, per-distance classes, complemented where more than half full), CGCN_NULL_DEGREE (erased
+ * configuration model; rounds is ignored but must be >= 1), CGCN_NULL_UNIFORM (placement of m pairs).  seed: 64 bits, both
+ * halves matter.
+ *
+ * Output: rowptr_out int32 [n + 1] and col_out int32 [capacity] -- the canonical symmetric CSR without a diagonal, columns
+ * ascending; col_out behind the last entry is zero.  capacity >= 1 is the room of col_out: 2 nnz is enough for DEGREE and
+ * UNIFORM, 4 nnz for DISTANCE (an unplaced hole of a complemented class adds an edge).  Nothing is written behind it: entries
+ * that do not fit are dropped and CGCN_NULL_FLAG_OVERRUN is set.
+ * sizes int64 [10], on the device: [0] entries written (= rowptr_out[n]), [1] edges in (m), [2] edges out, [3] tokens
+ * (DISTANCE: holes or edges per class; UNIFORM: m; DEGREE: the 2 m stubs), [4] unplaced tokens, [5] complemented classes,
+ * [6] loops, [7] repeats, [8] the number of rounds that had losers, [9] CGCN_NULL_FLAG_* bits: OVERRUN; UNSUPPORTED (UNIFORM
+ * with m > 0 and n < 2 or 4 m > n (n - 1): the graph is empty); BAD_INDEX (a column outside [0, n) was skipped).
+ *
+ * Enqueue only: no allocation, no synchronisation, nothing kept between calls; the result is a pure function of the input
+ * and the seed (integer atomics and sorts only).  CGCN_ERR_BAD_ARG: a negative size, capacity or rounds < 1, an unknown
+ * model, a NULL buffer that would be read or written; CGCN_ERR_UNSUPPORTED: nnz >= 2^30, capacity >= 2^31, or a key of
+ * (window, window, token) that does not fit 63 bits (cgcn_null_graph_workspace_bytes is then 0); CGCN_ERR_WORKSPACE:
+ * workspace_bytes below cgcn_null_graph_workspace_bytes(n, nnz, capacity, model).
+ */
+#define CGCN_NULL_DISTANCE 0
+#define CGCN_NULL_DEGREE 1
+#define CGCN_NULL_UNIFORM 2
+#define CGCN_NULL_FLAG_OVERRUN 1
+#define CGCN_NULL_FLAG_UNSUPPORTED 2
+#define CGCN_NULL_FLAG_BAD_INDEX 4
+
+size_t cgcn_null_graph_workspace_bytes(int n, long long nnz, long long capacity, int model);
+
+int cgcn_null_graph(cgcn_stream_t stream, int n, long long nnz, const int32_t *rowptr, const int32_t *col, int model,
+                    long long seed, int rounds, long long capacity, int32_t *rowptr_out, int32_t *col_out, long long *sizes,
+                    void *workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
