@@ -8,6 +8,9 @@ from .effects import (WindowEffects, effect_rows_host, knockout_map, knockout_ma
                       window_effects_host)
 from .embed import class_embeddings  # noqa: F401
 from .graph import ChromGraph, HostCSR, normalize_graph, process_graph, upload, as_graph  # noqa: F401
+from .bootstrap import (BootstrapComparison, BootstrapResult, bootstrap_compare, bootstrap_metrics,  # noqa: F401
+                        bootstrap_summary, bootstrap_weights, bootstrap_weights_host, metrics_from_sums, weighted_metrics,
+                        weighted_sums, weighted_sums_host)
 from .compare import compare_labels  # noqa: F401
 from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
@@ -39,4 +42,7 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "expected_vector_host", "hic_expected_vector", "ReadPairs", "bin_read_pairs_host", "pairs_to_contacts_host",
            "LabelStats", "label_stats", "label_stats_split", "label_stats_host", "compare_labels",
            "WindowEffects", "window_effects", "window_effects_host", "effect_rows_host", "knockout_map", "knockout_map_host",
-           "NullGraphTest", "null_graph", "null_graph_host", "null_chrom_graph", "null_graph_test", "null_statistics"]
+           "NullGraphTest", "null_graph", "null_graph_host", "null_chrom_graph", "null_graph_test", "null_statistics",
+           "BootstrapResult", "BootstrapComparison", "bootstrap_weights_host", "bootstrap_weights", "weighted_sums_host",
+           "weighted_sums", "metrics_from_sums", "weighted_metrics", "bootstrap_metrics", "bootstrap_compare",
+           "bootstrap_summary"]

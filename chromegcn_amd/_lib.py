@@ -152,6 +152,12 @@ _HEADER = {
     "cgcn_null_graph_workspace_bytes": (_c_sz, "n:i nnz:ll capacity:ll model:i"),
     "cgcn_null_graph": (_c_int, "stream n:i nnz:ll rowptr col model:i seed:ll rounds:i capacity:ll rowptr_out col_out sizes "
                                 "workspace workspace_bytes:z"),
+    "cgcn_bootstrap_workspace_bytes": (_c_sz, "n:ll C:i R:i"),
+    "cgcn_bootstrap_sort": (_c_int, "stream n:ll C:i probs targets order bad workspace workspace_bytes:z"),
+    "cgcn_bootstrap_weights": (_c_int, "stream n:ll rep0:ll R:i n_strata:i offsets block:i draws:ll seed:ll tile flags workspace "
+                                       "workspace_bytes:z"),
+    "cgcn_bootstrap_weights_in": (_c_int, "stream n:ll R:i weights tile flags"),
+    "cgcn_bootstrap_sums": (_c_int, "stream n:ll C:i R:i order tile fdr_cutoff out"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -72,7 +72,7 @@ def group_means(per_label: Dict[str, np.ndarray], label_groups) -> Dict[str, flo
 
 
 def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, data_dict=None, cell_type=None,
-                    device="cuda", verbose=False, label_groups=None, br_threshold=None):
+                    device="cuda", verbose=False, label_groups=None, br_threshold=None, bootstrap=None):
     """Same positional arguments and result keys as the reference's compute_metrics (utils/evals.py:26,107-120).
     Labels whose metric is undefined (a single class present) are skipped in the means, as the reference's try/except
     does.  Unlike the reference this does NOT threshold all_predictions in place (utils/evals.py:99-100).
@@ -81,7 +81,10 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
     results of the same single metrics call.  The curves its plot branch draws are chromegcn_amd.curves.
     `br_threshold` (default: `args.br_threshold` where `args` has one, else off; config_args.py:28): with a value the result
     also holds the scalars ACC, HA, ebF1, miF1, maF1 of the decisions p >= br_threshold (chromegcn_amd.thresholds, one more
-    stream over the device tensors); all_predictions is still not modified."""
+    stream over the device tensors); all_predictions is still not modified.
+    `bootstrap` (default: off, nothing changes): a dict of bootstrap_metrics' arguments (n_boot, block, seed, lengths, level);
+    the result then also holds mAP_ci, meanAUC_ci, meanAUPR_ci and meanFDR_ci, each the (low, high) percentile interval of
+    the scalar under the block bootstrap of chromegcn_amd.bootstrap (NaN for an empty split)."""
     p = torch.as_tensor(all_predictions).to(device=device, dtype=torch.float32)
     t = torch.as_tensor(all_targets).to(device=device, dtype=torch.float32)
     C = p.shape[1]
@@ -116,6 +119,14 @@ def compute_metrics(all_predictions, all_targets, loss, args=None, elapsed=0.0, 
         from . import thresholds
         tm = thresholds.threshold_metrics(p, t, float(br_threshold))
         out.update({k: float(tm[k][0]) for k in thresholds.METRIC_KEYS})
+    if bootstrap is not None:
+        keys = ("mAP", "meanAUC", "meanAUPR", "meanFDR")
+        if empty:
+            out.update({k + "_ci": (float("nan"), float("nan")) for k in keys})
+        else:
+            from . import bootstrap as B
+            res = B.bootstrap_metrics(p, t, **dict(bootstrap))
+            out.update({k + "_ci": (res.scalars[k]["ci_low"], res.scalars[k]["ci_high"]) for k in keys})
     if verbose:  # utils/evals.py:102-105
         print("mAP:      " + str(round(out["mAP"], 3)))
         print("meanAUC:  " + str(round(out["meanAUC"], 3)))
@@ -130,7 +141,8 @@ def per_chromosome_metrics(probs, targets, lengths, names=None, loss=0.0, device
     tensors, so the existing kernels run on them without a copy.  The reference's per-chromosome loop
     (scripts/analyze_results.py:288-307) selects every chromosome's rows and then hands the UNSLICED arrays to compute_metrics
     (:304), a slip that gives every chromosome the whole split's metrics; this slices.  `loss` and kwargs go to
-    compute_metrics."""
+    compute_metrics: with bootstrap=dict(n_boot=..., block=...) every chromosome's rows are resampled on their own (one
+    stratum) and its result holds the <key>_ci pairs."""
     lengths = [int(k) for k in lengths]
     names = [str(i) for i in range(len(lengths))] if names is None else [str(c) for c in names]
     if len(names) != len(lengths) or len(set(names)) != len(names):

@@ -98,7 +98,11 @@ def run_model(WindowModel, ChromeModel, train_data, valid_data, test_data, crit,
             vloss, vsum = 0.0, 0.0
         p, t, tloss, el = run_epoch(WindowModel, ChromeModel, test_data, crit, optimizer, epoch, data_dict, opt, "test",
                                     g.get("test"))                                             # runner.py:50
-        rec["test"] = M.compute_metrics(p, t, tloss, opt, el)
+        boot = None
+        if getattr(opt, "bootstrap", 0) and epoch == opt.epochs:   # -bootstrap B: intervals of the last epoch's test scalars,
+            boot = dict(n_boot=int(opt.bootstrap), block=int(getattr(opt, "bootstrap_block", 1)),   # the chromosomes as strata
+                        lengths=[int(test_data[c]["target"].shape[0]) for c in test_data])
+        rec["test"] = M.compute_metrics(p, t, tloss, opt, el, bootstrap=boot)
         saved = False
         if "valid" in rec:
             saved = log.maybe_checkpoint(epoch, opt, ChromeModel, vloss, vsum)                 # runner.py:57
@@ -111,5 +115,9 @@ def run_model(WindowModel, ChromeModel, train_data, valid_data, test_data, crit,
                 rec["valid"]["meanAUC"] if "valid" in rec else float("nan"),
                 rec["valid"]["meanAUPR"] if "valid" in rec else float("nan"), rec["test"]["meanAUC"],
                 "  [checkpoint]" if saved else ""))
+        if verbose and boot is not None:
+            print("test, %d bootstrap replicates in blocks of %d windows per chromosome, 95 %% intervals:  %s" % (
+                boot["n_boot"], boot["block"], "  ".join("%s %.4f [%.4f, %.4f]" % ((k, rec["test"][k]) + tuple(rec["test"][k + "_ci"]))
+                                                          for k in ("mAP", "meanAUC", "meanAUPR", "meanFDR"))))
         history.append(rec)
     return history

@@ -70,6 +70,10 @@ def parse(argv=None):
     ap.add_argument("-gpu_id", type=int, default=0)
     ap.add_argument("-br_threshold", type=float, default=None,       # config_args.py:28 (there 0.5; here off unless given)
                     help="also report ACC, HA, ebF1, miF1, maF1 of the decisions p >= this (chromegcn_amd.thresholds)")
+    ap.add_argument("-bootstrap", type=int, default=0, metavar="B",
+                    help="after the last epoch, print 95 %% block-bootstrap intervals of the test split's mAP, meanAUC, meanAUPR and "
+                         "meanFDR from B replicates, the test chromosomes as strata (chromegcn_amd.bootstrap)")
+    ap.add_argument("-bootstrap_block", type=int, default=50, metavar="L", help="-bootstrap: block length in windows")
     ap.add_argument("-summarize_data", action="store_true",     # config_args.py:35
                     help="print labels per window and windows per label (mean, median, max) of train + valid before the "
                          "first epoch (utils/util_methods.py:64-74; chromegcn_amd.labelstats)")

@@ -1211,6 +1211,53 @@ int cgcn_null_graph(cgcn_stream_t stream, int n, long long nnz, const int32_t *r
                     long long seed, int rounds, long long capacity, int32_t *rowptr_out, int32_t *col_out, long long *sizes,
                     void *workspace, size_t workspace_bytes);
 
+/*
+ * Weighted ranking sums of every label for many integer weight vectors from one sort: block-bootstrap confidence intervals
+ * (chromegcn_amd/bootstrap.py, whose docstring is the rule).  Additions to ABI 26 like the functions
+ * above: CGCN_ABI_VERSION stays 26, nothing above changes.
+ *
+ * Shapes: 1 <= n < 2^23 windows (so that a replicate's total weight, at most 255 n, stays below 2^31), C >= 1 labels with
+ * n C <= 2^31 and a key [label | score | target | window] of at most 64 bits (C <= 1024 with n <= 2^21 fits); anything else
+ * is CGCN_ERR_UNSUPPORTED and cgcn_bootstrap_workspace_bytes is 0.  R replicates form ceil(R / 64) groups of 64.
+ *
+ * cgcn_bootstrap_workspace_bytes(n, C, R): what cgcn_bootstrap_sort (n, C) and cgcn_bootstrap_weights (n, R) need, the larger
+ * of the two; R = 0 asks for the sort alone.
+ * cgcn_bootstrap_sort: probs, targets float [n, C] (a target is positive iff > 0.5; -0 is folded onto +0) -> order uint32
+ * [C n], label c's windows by descending score in [c n, (c + 1) n): window index | target << 30 | run end << 31, where a run
+ * end is the last element of a group of equal scores.  A NaN score ORs 1 into bad[0] (int32, zeroed by the caller).
+ * cgcn_bootstrap_weights: the circular block bootstrap of replicates rep0 .. rep0 + R - 1 (R <= 65535) over the strata
+ * [offsets[s], offsets[s + 1]) (int32 [n_strata + 1] on the device, ascending, within [0, n]; empty strata are skipped) with
+ * block length `block`; draws = the number of draws of one replicate, sum over the strata of ceil(n_s / min(block, n_s)).
+ * tile: bytes [ceil(R / 64)][n][64], the weight of window i in replicate r at ((r / 64) n + i) 64 + r % 64; lanes behind R
+ * hold 0.  cgcn_bootstrap_weights_in: the same tile from explicit weights int32 [R, n].
+ * flags[0] (int32, zeroed by the caller) collects CGCN_BOOT_FLAG_* bits: WEIGHT (a weight above 255: the byte stored is its
+ * low byte and the sums are to be discarded), NEGATIVE (stored as 0), STRATA (offsets outside the rule above).
+ * cgcn_bootstrap_sums: out, 6 R C words of 8 bytes: int64 A, P, TOT, F and float64 S_ap, S_pr, each [R, C].
+ * fdr_cutoff: a HOST pointer to one float64 in (0, 1), read during the call (CGCN_ERR_BAD_ARG outside the interval).
+ *
+ * Enqueue only: no allocation, no synchronisation, nothing kept between calls; integer atomics, one sort and sums in a fixed
+ * order, so every output is the same bits from run to run.  CGCN_ERR_BAD_ARG: a negative size, R < 1 (sums, weights),
+ * block < 1, a NULL buffer; CGCN_ERR_WORKSPACE: workspace_bytes below cgcn_bootstrap_workspace_bytes.
+ */
+#define CGCN_BOOT_FLAG_WEIGHT 1
+#define CGCN_BOOT_FLAG_NEGATIVE 2
+#define CGCN_BOOT_FLAG_STRATA 4
+
+size_t cgcn_bootstrap_workspace_bytes(long long n, int C, int R);
+
+int cgcn_bootstrap_sort(cgcn_stream_t stream, long long n, int C, const float *probs, const float *targets, uint32_t *order,
+                        int32_t *bad, void *workspace, size_t workspace_bytes);
+
+int cgcn_bootstrap_weights(cgcn_stream_t stream, long long n, long long rep0, int R, int n_strata, const int32_t *offsets,
+                           int block, long long draws, long long seed, unsigned char *tile, int32_t *flags, void *workspace,
+                           size_t workspace_bytes);
+
+int cgcn_bootstrap_weights_in(cgcn_stream_t stream, long long n, int R, const int32_t *weights, unsigned char *tile,
+                              int32_t *flags);
+
+int cgcn_bootstrap_sums(cgcn_stream_t stream, long long n, int C, int R, const uint32_t *order, const unsigned char *tile,
+                        const double *fdr_cutoff, long long *out);
+
 #ifdef __cplusplus
 }
 #endif

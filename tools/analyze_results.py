@@ -12,7 +12,10 @@ degree, and over the labels the paired t-test and the regression of the differen
 Written: --out, one .npz -- per metric m of auroc, aupr, recall_at_fdr: m_a, m_b [C], m_diff, m_kept, m_dropped, m_order and
 the scalars m_t, m_p, m_slope, m_intercept, m_r, m_p_regress, m_stderr; average_degree [C]; every integer array of the pooled
 LabelStats; contact_enrichment and pearson [C, C] -- and --csv, one line per label: label, windows, average_degree, then a, b
-and diff of every metric."""
+and diff of every metric.
+--bootstrap B (with --bootstrap-block L): B block-bootstrap replicates over the windows, the chromosomes as strata and both
+models under the same weights (chromegcn_amd.bootstrap.bootstrap_compare): m_diff_ci_low, m_diff_ci_high and m_diff_p [C] join
+the .npz, and diff_lo, diff_hi (the 95 % interval of b - a) and p (two-sided) the metric's csv columns."""
 import argparse
 import csv
 import json
@@ -71,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--lengths", required=True)
     ap.add_argument("--graphs", required=True)
     ap.add_argument("--groups", default=None)
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="B")
+    ap.add_argument("--bootstrap-block", type=int, default=50, metavar="L")
     ap.add_argument("--gpu-id", type=int, default=0)
     ap.add_argument("--out", required=True)
     ap.add_argument("--csv", required=True)
@@ -113,17 +118,28 @@ def main(argv=None):
         summary[m] = {k: r[k] for k in ("t", "p", "slope", "r")}
         if groups is not None:
             summary[m]["groups"] = r["groups"]
+    boot = None
+    if opt.bootstrap > 0:
+        from chromegcn_amd.bootstrap import bootstrap_compare
+        boot = bootstrap_compare(pb.to(dev), pa.to(dev), t, n_boot=opt.bootstrap, block=opt.bootstrap_block, lengths=lengths,
+                                 label_groups=groups)   # differences are b - a
+        for m in METRICS:
+            out[m + "_diff_ci_low"], out[m + "_diff_ci_high"], out[m + "_diff_p"] = boot.ci_low[m], boot.ci_high[m], boot.p[m]
+        summary["bootstrap"] = {k: {f: v[f] for f in ("diff", "ci_low", "ci_high", "p")} for k, v in boot.scalars.items()}
+    cols = ("a", "b", "diff") + (("diff_lo", "diff_hi", "p") if boot is not None else ())
     for path in (opt.out, opt.csv):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez(opt.out, **out)
     with open(opt.csv, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["label", "windows", "average_degree"] + ["%s_%s" % (m, k) for m in METRICS for k in ("a", "b", "diff")])
+        w.writerow(["label", "windows", "average_degree"] + ["%s_%s" % (m, k) for m in METRICS for k in cols])
         for c in range(tg.shape[1]):
             row = [c, int(host.label_count[c]), repr(float(degree[c]))]
             for m in METRICS:
                 a, b = float(per["a"][m][c]), float(per["b"][m][c])
                 row += [repr(a), repr(b), repr(b - a)]
+                if boot is not None:
+                    row += [repr(float(boot.ci_low[m][c])), repr(float(boot.ci_high[m][c])), repr(float(boot.p[m][c]))]
             w.writerow(row)
     print(json.dumps({"n": int(tg.shape[0]), "C": int(tg.shape[1]), "chromosomes": len(names), "out": opt.out, "csv": opt.csv,
                       "summary": summary}))
