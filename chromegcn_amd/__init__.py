@@ -19,6 +19,8 @@ from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_no
                       kr_balance_host)
 from .hicdist import (distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
                       hic_expected_vector)
+from .insulation import (Insulation, diamond_sums, diamond_sums_host, domain_edge_share, domain_of_windows,  # noqa: F401
+                         insulation_from_sums, insulation_host)
 from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
 from .nullgraph import (NullGraphTest, null_chrom_graph, null_graph, null_graph_host, null_graph_test,  # noqa: F401
                         null_statistics)
@@ -45,4 +47,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "NullGraphTest", "null_graph", "null_graph_host", "null_chrom_graph", "null_graph_test", "null_statistics",
            "BootstrapResult", "BootstrapComparison", "bootstrap_weights_host", "bootstrap_weights", "weighted_sums_host",
            "weighted_sums", "metrics_from_sums", "weighted_metrics", "bootstrap_metrics", "bootstrap_compare",
-           "bootstrap_summary"]
+           "bootstrap_summary", "Insulation", "diamond_sums", "diamond_sums_host", "insulation_from_sums", "insulation_host",
+           "domain_edge_share", "domain_of_windows"]

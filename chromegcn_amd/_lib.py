@@ -158,6 +158,7 @@ _HEADER = {
                                        "workspace_bytes:z"),
     "cgcn_bootstrap_weights_in": (_c_int, "stream n:ll R:i weights tile flags"),
     "cgcn_bootstrap_sums": (_c_int, "stream n:ll C:i R:i order tile fdr_cutoff out"),
+    "cgcn_hicinsul_sums": (_c_int, "stream n:i rowptr col val norm n_norm:ll n_windows:i windows out"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

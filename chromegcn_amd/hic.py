@@ -44,7 +44,14 @@ b2 = pos2 // res, d = |b1 - b2|, n_bins = the largest bin + 1 unless given (a sm
      survives both rules.
 
 Contact TEXT becomes records by the rule of chromegcn_amd/hictext.py (HicContacts.from_text, parse_contacts_text_host); the
-`.cghic` cache of the records is chromegcn_amd/hiccache.py's.  Their public names are still found here."""
+`.cghic` cache of the records is chromegcn_amd/hiccache.py's.  Their public names are still found here.
+
+Domains (domains; DESIGN.md section 4.17, chromegcn_amd/insulation.py holds the rule).  domains = (domain_of_bin, domain_bp):
+a record takes part only if dom[pos1 // domain_bp] == dom[pos2 // domain_bp], a position beyond the vector never matching;
+the test is on the SOURCE record, where the minimum gap is tested.  domain_bp must be a multiple of resolution_bp.  A dict
+stands for the vector computed from the records (HicContacts.domains / insulation.domains_host with these keywords).  Named
+norms and expected = "auto" are still computed from ALL records; the kept records stay in file order.  domains = None is the
+rule above, bit for bit."""
 from __future__ import annotations
 
 from typing import Dict, NamedTuple, Optional
@@ -162,13 +169,24 @@ def _survivors_up(p1, p2, ws, wbp, up, keep=None):
     return src, a, b, np.searchsorted(ws, p1[src] + a * wbp), np.searchsorted(ws, p2[src] + b * wbp)
 
 
+def _host_domains(domains, pos1, pos2, count, resolution_bp):
+    """the builders' `domains` on the host: None, or (domain_of_bin int32, domain_bp) -- a dict is computed from the records"""
+    if domains is None:
+        return None
+    from . import insulation
+    if isinstance(domains, dict):
+        domains = insulation.domains_host(pos1, pos2, count, **domains)
+    return insulation.check_domains(domains, resolution_bp)
+
+
 def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp=None, min_distance_bp=0, expected=None,
-                    expected_args=None):
+                    expected_args=None, domains=None):
     """(record index, i, j, value) of the surviving records in file order (rules 1 and 2).  With window_bp: of the surviving
     records of the expanded file, the index being the position in it.  min_distance_bp, expected (None, a vector, or "auto":
     hicdist.expected_vector_host with this norm and expected_args): the minimum gap and the observed / expected value of the
-    module docstring."""
+    module docstring.  domains: the module docstring's; the indices stay those of the whole file."""
     up = _upsample(resolution_bp, window_bp)
+    domains = _host_domains(domains, pos1, pos2, count, resolution_bp)
     gap = _gap(min_distance_bp)
     ws = _windows(window_start).astype(np.int64)
     p1, p2 = np.asarray(pos1, dtype=np.int64), np.asarray(pos2, dtype=np.int64)
@@ -178,13 +196,18 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
     if n == 0 or p1.size == 0:
         e = np.zeros(0, np.int64)
         return e, e, e, np.zeros(0, np.float64)
+    keep = (np.abs(p1 - p2) >= gap) if gap else None   # the source records that take part
+    if domains is not None:
+        from . import insulation
+        same = insulation.same_domain_host(p1, p2, *domains)
+        keep = same if keep is None else keep & same
     if up > 1:
-        src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up, (np.abs(p1 - p2) >= gap) if gap else None)
+        src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up, keep)
         idx = src * (up * up) + a * up + b
     else:
         i = np.minimum(np.searchsorted(ws, p1), n - 1)
         j = np.minimum(np.searchsorted(ws, p2), n - 1)
-        idx = src = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2) & (np.abs(p1 - p2) >= gap))
+        idx = src = np.flatnonzero((p1 != p2) & (ws[i] == p1) & (ws[j] == p2) & (True if keep is None else keep))
         i, j = i[idx], j[idx]
     v = np.asarray(count)[src].astype(np.float64)
     if norm is not None:
@@ -208,11 +231,12 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
 
 
 def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None,
-                         norm_args=None, min_distance_bp=0, expected=None, expected_args=None) -> sp.csr_matrix:
+                         norm_args=None, min_distance_bp=0, expected=None, expected_args=None, domains=None) -> sp.csr_matrix:
     """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns).  With window_bp: of
     the expanded file, which is never written out (the CPU path for coarse records at full size).  norm = 'KR' / 'VC' /
     'SQRTVC': the vector computed from the records (hicnorm.hic_norm_vector_host with norm_args).  min_distance_bp, expected
-    (None, a vector, or "auto": hicdist.expected_vector_host with the same norm and expected_args = n_bins / min_count)."""
+    (None, a vector, or "auto": hicdist.expected_vector_host with the same norm and expected_args = n_bins / min_count).
+    domains: None, (domain_of_bin, domain_bp), or a dict of insulation.domains_host's keywords (the module docstring)."""
     ws = _windows(window_start)
     n = ws.size
     k = _budget(hic_edges)
@@ -224,7 +248,8 @@ def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, h
         norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **(norm_args or {}))
         hicnorm._require_converged(info)
         norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
-    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected)
+    _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected,
+                                 domains=domains)
     take = np.argsort(-v, kind="stable")[:k]
     i, j = i[take], j[take]
     a = sp.coo_matrix((np.ones(2 * i.size), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(n, n)).tocsr()
@@ -269,6 +294,8 @@ class HicContacts:
         self._norms = {}     # norm_vector's argument tuple -> (vector, info)
         self._dist_sums = {}       # distance_sums' argument tuple -> (raw, act, host syncs)
         self._expected = {}        # expected_vector's argument tuple -> (vector, info)
+        self._insulations = {}     # insulation's argument tuple -> insulation.Insulation
+        self._within = []          # (domain_of_bin, domain_bp, the HicContacts of the kept records): the last few selections
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
 
     @classmethod
@@ -418,6 +445,66 @@ class HicContacts:
         v, info = self._expected[key]
         return (v, dict(info)) if return_info else v
 
+    def insulation(self, norm="VC", resolution_bp=10000, windows_bp=(100000, 250000), n_bins=None, norm_args=None, **rule):
+        """The insulation profile of the records (chromegcn_amd/insulation.py's rule) at the windows `windows_bp`, multiples of
+        resolution_bp: the diamond sums on the device from contact_matrix(resolution_bp, n_bins) (cgcn_hicinsul_sums), one
+        read-back of the sums, the row sums and the vector, then insulation.insulation_from_sums.  norm: None, a vector at
+        resolution_bp, or 'KR' / 'VC' / 'SQRTVC' (norm_vector with norm_args; a KR that did not converge raises HicNormError);
+        VC is the default because it cannot fail to converge.  **rule: min_valid_share, span, min_strength.  Kept per
+        argument tuple for None and the three names."""
+        from . import insulation as INS
+        res = int(resolution_bp)
+        w = INS.windows_in_bins(windows_bp, res)
+        INS._rule(rule)
+        nk = self._norm_key(norm, norm_args)
+        span = rule.get("span")
+        key = None if nk is None else nk + (res, w, None if n_bins is None else int(n_bins)) + tuple(
+            sorted({**rule, "span": tuple(np.ravel(span).tolist()) if span is not None else None}.items()))
+        if key is not None and key in self._insulations:
+            return self._insulations[key]
+        a = self.contact_matrix(res, n_bins)
+        nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+        out = INS.insulation_of_matrix(a, nv, res, w, **rule)
+        if key is not None:
+            self._insulations[key] = out
+        return out
+
+    def domains(self, window_bp, norm="VC", resolution_bp=10000, n_bins=None, norm_args=None, **rule):
+        """(domain_of_bin int32 numpy [n_bins], resolution_bp) of insulation(...) at the one window `window_bp`: what the
+        builders' `domains` takes"""
+        ins = self.insulation(norm, resolution_bp, (int(window_bp),), n_bins=n_bins, norm_args=norm_args, **rule)
+        return ins.domain_of_bin(0), int(resolution_bp)
+
+    def within_domains(self, domain_of_bin, domain_bp) -> "HicContacts":
+        """the records whose two ends lie in one domain (a position beyond the vector never matches), in file order, as a
+        HicContacts of their own.  Boolean indexing: one host sync for the size."""
+        bp = int(domain_bp)
+        if bp < 1:
+            raise ValueError("domain_bp must be positive")
+        dom = self._up(domain_of_bin, torch.int32).ravel()
+        with torch.cuda.device(self.device):
+            b1 = torch.div(self.pos1, bp, rounding_mode="floor").long()
+            b2 = torch.div(self.pos2, bp, rounding_mode="floor").long()
+            n = int(dom.numel())
+            keep = (b1 >= 0) & (b2 >= 0) & (b1 < n) & (b2 < n)
+            if n:
+                keep &= dom[b1.clamp(0, n - 1)] == dom[b2.clamp(0, n - 1)]
+            return HicContacts(self.pos1[keep], self.pos2[keep], self.count[keep], self.device)
+
+    def _selection(self, domains, resolution_bp) -> "HicContacts":
+        """within_domains for the builders' `domains` (a pair or a dict of domains' keywords); the last few are kept, so
+        that a sweep over budgets or norms selects once"""
+        from . import insulation as INS
+        if isinstance(domains, dict):
+            domains = self.domains(**domains)
+        dom, bp = INS.check_domains(domains, resolution_bp)
+        for d, b, c in self._within:
+            if b == bp and d.shape == dom.shape and np.array_equal(d, dom):
+                return c
+        c = self.within_domains(dom, bp)
+        self._within = self._within[-3:] + [(dom, bp, c)]
+        return c
+
     def _norm(self, norm) -> Optional[torch.Tensor]:
         if norm is None:
             return None
@@ -489,13 +576,15 @@ class HicContacts:
         return self._survivors[key]
 
     def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None, min_distance_bp=0,
-                  expected=None, expected_args=None):
+                  expected=None, expected_args=None, domains=None):
         """(rowptr int32 [N + 1], col int32 [>= nnz], sizes int64 [2] = (nnz, survivors)), all on the device, enqueued
         on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors() -- and, for
         norm = 'KR' / 'VC' / 'SQRTVC', those of norm_vector(norm, resolution_bp, **norm_args) when it is not cached; a KR
         that did not converge raises HicNormError.  min_distance_bp, expected (None, a vector, or "auto": expected_vector
         with the same norm and expected_args = n_bins / min_count): the module docstring's rules 3 and 4; with the defaults
-        the entry points and the graph are the ones without them."""
+        the entry points and the graph are the ones without them.  domains (None, (domain_of_bin, domain_bp), or a dict of
+        domains()' keywords): names and "auto" are resolved on all records, then the same entry points build from the
+        records within domains (within_domains; one more host sync per new selection)."""
         from . import _lib
         k = _budget(hic_edges)
         gap = _gap(min_distance_bp)
@@ -506,6 +595,9 @@ class HicContacts:
             norm = self._named_norm(norm, resolution_bp, norm_args)
             ws_last = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
             norm = hicnorm.pad_vector(norm, int(ws_last[-1]) // int(resolution_bp) + 1 if ws_last.size else 0)
+        if domains is not None:
+            return self._selection(domains, resolution_bp).build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
+                                                                     min_distance_bp=gap, expected=expected)
         _upsample(resolution_bp, window_bp)
         self._set_windows(window_start)
         route = self._route(resolution_bp, window_bp)
@@ -537,15 +629,15 @@ class HicContacts:
         return rowptr, col, sizes
 
     def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
-              norm_args=None, min_distance_bp=0, expected=None, expected_args=None, null=None):
+              norm_args=None, min_distance_bp=0, expected=None, expected_args=None, null=None, domains=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
         host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back.  norm: a vector,
         None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords).  min_distance_bp,
-        expected, expected_args: build_raw's.  null = (model, seed): the matrix is replaced by its null graph
+        expected, expected_args, domains: build_raw's.  null = (model, seed): the matrix is replaced by its null graph
         (chromegcn_amd.nullgraph) before the normalisation; return_raw then returns the null matrix."""
         rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
                                             norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected,
-                                            expected_args=expected_args)
+                                            expected_args=expected_args, domains=domains)
         if null is not None:
             from . import nullgraph
             rowptr, col, sizes = nullgraph.null_graph((rowptr, col), model=null[0], seed=null[1], device=self.device)
@@ -560,16 +652,17 @@ class HicContacts:
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
                     return_raw=False, window_bp=None, norm_args=None, min_distance_bp=0, expected=None, expected_args=None,
-                    null=None):
+                    null=None, domains=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
     `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
     coarser than the windows and stand for their expanded file (the module's docstring).  min_distance_bp, expected (None, a
-    vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring).  null:
-    HicContacts.build's."""
+    vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring).  null,
+    domains: HicContacts.build's."""
     _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
     return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp,
-                   norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args, null=null)
+                   norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args, null=null,
+                   domains=domains)
 
 
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
@@ -580,7 +673,8 @@ def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
 def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_type: str = "hic", device="cuda",
                                sizes: Optional[Dict[str, int]] = None, window_bp=None,
                                compute_norm: bool = False, min_distance_bp=0, expected=None,
-                               expected_args=None, null=None) -> Dict[str, G.ChromGraph]:
+                               expected_args=None, null=None, domains=None,
+                               domain_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
@@ -590,7 +684,10 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
     with the vector the call scores with; any other name: the vector the cache stores under it, tools/hic_ingest.py
     --compute-expected writes eRAW / eKR / eVC / eSQRTVC), expected_args: build_hic_graph's.  null = (model, seed)
     (`-hic_null`, `-hic_null_seed`): every matrix is replaced by its null graph before the normalisation, chromosome index c
-    of the list with nullgraph.replicate_seed(seed, 0, c, len(chroms))."""
+    of the list with nullgraph.replicate_seed(seed, 0, c, len(chroms)).  domains (`-hic_domains`): a dict of
+    HicContacts.domains' keywords; every graph is built from the records within the domains computed from its cache's records.
+    domain_report: a dict that receives {chrom: (boundaries, same-domain entries, nnz)} of the UNRESTRICTED top-K matrix
+    (insulation.domain_edge_share)."""
     from . import hicnorm as HN
     from . import nullgraph
     out = {}
@@ -614,9 +711,19 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                 raise ValueError("%s holds no %r vector (has: %s)" % (contact_cache_path(root, chrom), expected,
                                                                      ", ".join(sorted(c.norms)) or "none"))
             ex = c.norms[expected]
-        out[chrom] = build_hic_graph(c.pos1, c.pos2, c.count, norm, c.resolution_bp,
+        rec, dom = (c.pos1, c.pos2, c.count), None
+        if domains is not None:
+            from . import insulation as INS
+            rec = (HicContacts(c.pos1, c.pos2, c.count, device), None, None)
+            dom = rec[0].domains(**domains)
+            if domain_report is not None:   # what the restriction removes: the unrestricted top-K matrix against the domains
+                rp, ci_, _ = rec[0].build_raw(norm, c.resolution_bp, c.window_start, int(hicsize), min_distance_bp=min_distance_bp,
+                                              expected=ex, expected_args=expected_args, **up)
+                domain_report[chrom] = (int(dom[0].max()) if dom[0].size else 0,) + INS.domain_edge_share(
+                    (rp, ci_), INS.domain_of_windows(c.window_start, *dom))
+        out[chrom] = build_hic_graph(*rec, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device,
                                      min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args,
                                      null=None if null is None else (null[0], nullgraph.replicate_seed(null[1], 0, ci, len(chroms))),
-                                     **up)
+                                     domains=dom, **up)
     return out

@@ -45,6 +45,13 @@ def parse(argv=None):
     ap.add_argument("-hic_expected", action="store_true",
                     help="-hic_contacts: score a contact by observed / expected, the expected vector computed from the cache's "
                          "records on the GPU with the run's -hicnorm")
+    ap.add_argument("-hic_domains", type=int, default=0, metavar="WINDOW_BP",
+                    help="-hic_contacts: build every graph from the contacts that stay inside one domain, the domains found "
+                         "from the cache's records by the insulation score at this window (chromegcn_amd.insulation; VC-balanced); "
+                         "prints per chromosome the boundary count and the same-domain share of the unrestricted graph.  0: off")
+    ap.add_argument("-hic_domain_res", type=int, default=10000, metavar="BP", help="-hic_domains: the bin size of the insulation score")
+    ap.add_argument("-hic_domain_strength", type=float, default=0.5, metavar="X",
+                    help="-hic_domains: the least boundary strength (log2 units)")
     ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
                     help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
                          "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
@@ -128,6 +135,9 @@ def _load_inputs(opt):
         graphs[sp] = None
         if opt.adj_type in ("hic", "both") and opt.hic_contacts:
             from . import hic
+            domains, report = None, {}
+            if getattr(opt, "hic_domains", 0):
+                domains = dict(window_bp=opt.hic_domains, resolution_bp=opt.hic_domain_res, min_strength=opt.hic_domain_strength)
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
@@ -136,7 +146,11 @@ def _load_inputs(opt):
                                                         min_distance_bp=opt.hic_min_distance,
                                                         expected="auto" if opt.hic_expected else None,
                                                         null=((opt.hic_null, getattr(opt, "hic_null_seed", 0))
-                                                              if getattr(opt, "hic_null", None) else None))
+                                                              if getattr(opt, "hic_null", None) else None),
+                                                        domains=domains, domain_report=report)
+            for c, (n_bound, same, nnz) in report.items():
+                print("[hic_domains] %s %s: %d boundaries, %d of %d entries of the unrestricted graph inside a domain (%.1f %%)"
+                      % (sp, c, n_bound, same, nnz, 100.0 * same / max(nnz, 1)))
         elif opt.adj_type in ("hic", "both"):
             path = os.path.join(opt.graph_root, sp + "_graphs_" + opt.hicsize + "_" + opt.hicnorm + "norm.pkl")  # finetune.py:21
             with open(path, "rb") as f:

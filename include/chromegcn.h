@@ -1258,6 +1258,26 @@ int cgcn_bootstrap_weights_in(cgcn_stream_t stream, long long n, int R, const in
 int cgcn_bootstrap_sums(cgcn_stream_t stream, long long n, int C, int R, const uint32_t *order, const unsigned char *tile,
                         const double *fdr_cutoff, long long *out);
 
+/*
+ * Diamond sums of a contact matrix, the input of the insulation score (chromegcn_amd/insulation.py, whose docstring is the
+ * rule).  An addition to ABI 26 like the functions above: CGCN_ABI_VERSION stays 26, nothing above
+ * changes.
+ *
+ * The matrix is what cgcn_hicnorm_fill writes: n bins, rowptr int32 [n + 1], col int32 and val fp64 [rowptr[n]], symmetric, the
+ * columns of a row ascending.  For window k (windows: a HOST array int32 [n_windows], read during the call, 1 <= n_windows <=
+ * 8, every window >= 1, strictly ascending) and bin i,
+ *   out[k n + i] = sum over a in [max(i - w_k, 0), i - 1], b in [i, min(i + w_k, n) - 1] of val[a, b] / (nv[a] * nv[b]),
+ * one fp64 multiplication and one fp64 division per term; norm fp64 [n_norm] or NULL (the terms are val itself) reads as in
+ * cgcn_hic_build: NaN, 0 and a bin outside the vector are +inf, such a term adds 0.  out fp64 [n_windows][n], every entry
+ * written; out[k n] = 0 and the diagonal never takes part.  One wavefront per bin adds its terms in a fixed order: the same
+ * bits in every run, exact for integer counts below 2^53, no floating-point atomics.
+ * Enqueue only: no workspace, no allocation, no synchronisation.  CGCN_ERR_BAD_ARG: a NULL pointer that would be read or
+ * written, n < 0, n_norm < 0, norm with n_norm < 1, n_windows < 1, a window < 1 or not above the one before it;
+ * CGCN_ERR_UNSUPPORTED: n_windows > 8.
+ */
+int cgcn_hicinsul_sums(cgcn_stream_t stream, int n, const int32_t *rowptr, const int32_t *col, const double *val,
+                       const double *norm, long long n_norm, int n_windows, const int32_t *windows, double *out);
+
 #ifdef __cplusplus
 }
 #endif
