@@ -1,8 +1,16 @@
 """Thresholded multi-label counts on the device (chromegcn_amd.thresholds, csrc/cgcn_threshold.hip) against the numpy
 restatement that tests/test_thresholds_host.py holds to the reference -- by exact equality (dtype, shape, values) of EVERY
 output array of every case.  Every case goes through the C ABI with a workspace of exactly the queried size full of stale
-bytes and sentinel-filled guard bands around every output (`device_counts`): every element is written, nothing else is."""
+bytes and sentinel-filled guard bands around every output (`device_counts`): every element is written, nothing else is.
+
+The second half of the file walks the launch plans: threshold_plan() picks one of six kernel instances, 1 to 8 waves per team
+(workgroups of 320, 384, 448 or 512 threads), the threshold groups of grid.y and a tile from (n, C, T).  threshold_cases.plan
+restates that arithmetic, is pinned here to the library for every (C, T), and every case below asserts through it the
+property it is there for before it launches -- a retuned plan fails the case instead of moving it onto another path.
+Out of scope: the bound of an LDS histogram word, rows * C < 2^26 (65 535 rows of 1 024 labels in ONE workgroup: about 270 GB
+of input), and the refusal of n >= 2^47."""
 import functools
+import time
 
 import numpy as np
 import pytest
@@ -248,3 +256,144 @@ def test_bad_inputs_raise():
     assert _lib.query("cgcn_threshold_counts", **dict(args, tpsum=None)) == -1
     assert _lib.query("cgcn_threshold_counts", **dict(args, C=1025)) == -2
     assert _lib.query("cgcn_threshold_counts", **dict(args, T=65)) == -2
+
+
+# ---- every instance, team shape and bound of the launch plan ----------------------------------------------------------------
+def equal_counts(got, want, what, T=None):
+    """all six arrays; with T, the first T thresholds of a reference that has more"""
+    assert len(got) == len(want) == len(FIELDS)
+    for g, w, f in zip(got, want, FIELDS):
+        assert same(g, w if T is None or f == "pos" else w[:T]), (what, f)
+
+
+def host_counts(p, y, thr):
+    c = th.threshold_counts_host(p, y, thr)
+    return tuple(getattr(c, f) for f in FIELDS)
+
+
+def test_the_restated_plan_gives_the_librarys_groups_at_every_C_and_T():
+    """host arithmetic on both sides, nothing is launched"""
+    for C in range(1, tc.THR_MAX_C + 1):
+        got = [_lib.query("cgcn_debug_threshold_route", n=tc.SWEEP_N, C=C, T=T) for T in range(1, tc.THR_MAX_T + 1)]
+        assert got == [tc.plan(tc.SWEEP_N, C, T)["groups"] for T in range(1, tc.THR_MAX_T + 1)], C
+
+
+@pytest.mark.parametrize("C", sorted(tc.CHUNK_EDGE_C))
+def test_every_instance_at_the_edges_of_its_label_chunks(C):
+    """193, 257, 449 and 513 have ONE live label in their last live chunk (257: three wholly dead chunks behind it); the dead
+    labels and the dead slot of the wave's last threshold hold NaN and must count nothing"""
+    q = tc.plan(300, C, tc.GRID7.size)
+    assert q["CH"] == tc.CHUNK_EDGE_C[C] and q["grid_x"] == 3 and q["last_nt"] < q["TT"]     # a dead slot
+    check("edge", (300, C))
+
+
+@pytest.mark.parametrize("C", [193, 257, 513])
+def test_one_live_label_in_the_last_chunk_against_the_brute_force_loop(C):
+    assert C % 64 == 1 and tc.plan(12, C, 7)["CH"] == tc.CHUNK_EDGE_C[C]
+    p, y = tc.quantised(12, C)
+    equal_counts(device_counts(p, y, tc.GRID7), tc.brute_force_counts(p, y, th.threshold_matrix(tc.GRID7, C)), C)
+
+
+@pytest.mark.parametrize("name,n,C", tc.WIDE_SPECIAL)
+def test_special_values_in_the_wide_instances(name, n, C):
+    p, y, thr = tc.special_at(name, n, C)
+    q = tc.plan(n, C, thr.size)
+    assert q["CH"] == (16 if C == 1024 else 8) and C % 64 in (0, 1) and q["grid_x"] == 2
+    got = device_counts(p, y, thr)
+    equal_counts(got, host_counts(p, y, thr), (name, C))
+    rows, tpsum = got[4], got[5]
+    if name == "all_ones":          # k = 2048 and both = 1024: the largest value of either field of the row record
+        assert 2 * C == 2048 and (rows[:-1, 2048] == n).all() and (tpsum[:-1, 2048] == n * 1024).all()
+        assert rows[-1, 1024] == n and tpsum[-1].sum() == 0 and rows.sum() == thr.size * n
+    if name == "infinities":
+        assert got[2][0].sum() == C and got[2][1].sum() == n * C and got[2][2].sum() == (p >= 0).sum() > (p > 0).sum()
+    if name == "nan":
+        assert got[2][0].sum() == (p >= thr[0]).sum() < np.isfinite(p).sum() + 1
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_reference(C):
+    return host_counts(*tc.sweep_case(C))
+
+
+@pytest.mark.parametrize("C", sorted(tc.SWEEP_C))
+def test_every_team_shape_one_call_per_T(C):
+    """T = 1 .. 64 against the first T rows of ONE host evaluation: every waves-per-team count this C has (5, 6 and 7 waves
+    are workgroups of 320, 384 and 448 threads), spare waves behind a short last group, every fill of the last wave, and --
+    the matrix being per label -- threshold rows read at blockIdx.y > 0"""
+    p, y, thr = tc.sweep_case(C)
+    want = _sweep_reference(C)
+    plans = [tc.plan(tc.SWEEP_N, C, T) for T in range(1, tc.THR_MAX_T + 1)]
+    assert {q["waves"] for q in plans} == set(range(1, tc.SWEEP_C[C] + 1)) and all(q["grid_x"] == 3 for q in plans)
+    assert {q["last_nt"] for q in plans} == set(range(1, plans[0]["TT"] + 1))
+    assert any(q["spare"] for q in plans) == (C != 5) and any(q["groups"] > 1 for q in plans) == (C != 5)
+    for T, q in enumerate(plans, 1):
+        equal_counts(device_counts(p, y, thr[:T]), want, (C, T, q), T)
+
+
+def test_a_second_group_reads_its_own_threshold_rows():
+    C, T = 103, 40
+    q = tc.plan(tc.SWEEP_N, C, T)
+    assert (q["groups"], q["TW"], q["spare"]) == (2, 32, 3)
+    p, y, thr = tc.sweep_case(C)
+    got = device_counts(p, y, thr[:T])
+    equal_counts(got, _sweep_reference(C), (C, T), T)
+    swapped = host_counts(p, y, thr[:T, ::-1].copy())
+    assert not same(got[2][:32], swapped[2][:32]) and not same(got[2][32:], swapped[2][32:])
+    assert not same(got[2][32:], got[2][:8])            # ... and not those of the first group again
+
+
+@pytest.mark.parametrize("n", [127, 128, 129])
+def test_either_side_of_the_smallest_row_block(n):
+    for C, T in tc.MIN_ROWS_SHAPES:
+        q = tc.plan(n, C, T)
+        assert q["rows_per_wg"] == tc.THR_MIN_ROWS == 128 and q["grid_x"] == (2 if n == 129 else 1)   # 129: one row
+        p, y = tc.quantised(n, C)
+        thr = tc.per_label_matrix(T, C)
+        equal_counts(device_counts(p, y, thr), host_counts(p, y, thr), (n, C, T))
+
+
+@pytest.mark.parametrize("CH", sorted(tc.TILE_PLANS))
+def test_one_row_less_and_more_than_whole_tiles(CH):
+    """as the rows of a single workgroup and of the last of three; tile_rows set by the LDS room in three of the plans and
+    by the registers in flight in the other three"""
+    C, T, tile_by = tc.TILE_PLANS[CH]
+    thr = tc.per_label_matrix(T, C)
+    for n, groups in tc.tile_edge_rows(C, T):
+        q = tc.plan(n, C, T)
+        tail = n - (groups - 1) * q["rows_per_wg"]
+        assert q["CH"] == CH and q["tile_by"] == tile_by and q["grid_x"] == groups
+        assert (tail + 1) % q["tile_rows"] <= 2 and tail >= q["tile_rows"] - 1
+        p, y = tc.quantised(n, C)
+        equal_counts(device_counts(p, y, thr), host_counts(p, y, thr), (n, C, T, q))
+
+
+def test_both_16_bit_halves_of_a_count_register_at_65535():
+    """C = 1, n = 512 * 65535 + 1: 513 workgroups of 65 535 rows (the last owns one row), one team, so every wave counts
+    every row of its workgroup.  The first workgroup's rows are all positive and theta_0 = -inf predicts them all: its
+    register of threshold 0 ends at 0xFFFFFFFF, 65 535 in both halves -- one more row would carry.  Expected values from the
+    joint histogram of (level, target), which tests/test_thresholds_host.py holds to threshold_counts_host."""
+    n, T = tc.HALVES_N, tc.HALVES_T
+    q = tc.plan(n, 1, T)
+    assert (q["rows_per_wg"], q["grid_x"], q["teams"], q["groups"]) == (65535, 513, 1, 1) and n - 512 * 65535 == 1
+    assert tc.plan(n - 1, 1, T)["grid_x"] == 512
+    idx, y = tc.halves_case(n)
+    thr = tc.HALVES_GRID
+    assert thr[0] == -np.inf and (y[:65535] == 1).all()
+    want = tc.single_label_counts(idx, y, thr)
+    assert want[2][0, 0] == n and want[1][0, 0] == want[0][0] > 65535
+    p = tc.LEVELS[idx].reshape(n, 1)
+    start = time.perf_counter()
+    got = device_counts(p, y, thr)
+    print("C = 1, n = %d, T = %d: %.2f s for upload, call and guard checks" % (n, T, time.perf_counter() - start))
+    equal_counts(got, want, "halves")
+
+
+@pytest.mark.parametrize("C,T,CH,waves", [(257, 12, 8, 3), (65, 40, 2, 5)])
+def test_two_runs_of_a_wide_and_of_a_five_wave_plan_give_the_same_bits(C, T, CH, waves):
+    q = tc.plan(tc.SWEEP_N, C, T)
+    assert (q["CH"], q["waves"], q["block"]) == (CH, waves, 64 * waves * (8 // waves))
+    p, y, thr = tc.sweep_case(C)
+    a, b = device_counts(p, y, thr[:T]), device_counts(p, y, thr[:T])
+    assert all(x.tobytes() == z.tobytes() for x, z in zip(a, b))
+    equal_counts(a, _sweep_reference(C), (C, T), T)

@@ -142,3 +142,95 @@ def test_best_thresholds_on_a_hand_made_table():
     thr = np.arange(16, dtype=np.float32).reshape(4, 4) / 16
     best = th.best_thresholds(c._replace(thresholds=thr))
     assert best[0] == thr[2, 0] and best[1] == thr[1, 1]
+
+
+# ---- the launch plan restated in threshold_cases.plan: its invariants, and what the GPU cases chosen with it reach -----------
+# (tests/test_gpu_thresholds.py pins plan()["groups"] to the library for every (C, T))
+ALL_CT = [(C, T) for C in range(1, tc.THR_MAX_C + 1) for T in range(1, tc.THR_MAX_T + 1)]
+
+
+def test_plan_invariants_over_every_label_and_threshold_count():
+    assert len(ALL_CT) == 65536
+    for C, T in ALL_CT:
+        q = tc.plan(300, C, T)
+        assert 1 <= q["waves"] <= 8 and q["teams"] == 8 // q["waves"] and q["block"] <= 512, (C, T)
+        assert q["tile_rows"] >= 1, (C, T)
+        assert q["tile_rows"] * C <= 64 * q["waves"] * q["teams"] * q["NLD"], (C, T)     # a tile fits the registers in flight
+        assert q["hist_bytes"] + q["tile_rows"] * C * 8 <= 65536, (C, T)                 # ... and the LDS beside the histograms
+        assert 64 * q["CH"] >= C and (q["TT"], q["NLD"]) == tc.INSTANCES[q["CH"]], (C, T)
+        assert q["TW"] == q["waves"] * q["TT"] and (q["groups"] - 1) * q["TW"] < T <= q["groups"] * q["TW"], (C, T)
+        assert 0 <= q["spare"] < q["waves"] and 1 <= q["last_nt"] <= q["TT"], (C, T)
+        assert (q["groups"] - 1) * q["TW"] + (q["waves"] - q["spare"] - 1) * q["TT"] + q["last_nt"] == T, (C, T)
+    for n in (1, 127, 128, 129, 65536, 65537, tc.HALVES_N - 1, tc.HALVES_N, 1 << 40):
+        q = tc.plan(n, 7, 3)
+        assert 128 <= q["rows_per_wg"] <= 65535 and (q["grid_x"] - 1) * q["rows_per_wg"] < n <= q["grid_x"] * q["rows_per_wg"]
+
+
+def test_the_plan_space_has_25_team_shapes_and_four_odd_blocks():
+    space = tc.plan_space()
+    assert len(space) == 25 and {ch for ch, _ in space} == set(tc.INSTANCES)
+    assert {w for ch, w in space if ch == 1} == set(range(1, 9))
+    assert {tc.plan(1, C, T)["block"] for C, T in ALL_CT} == {320, 384, 448, 512}
+
+
+def test_the_sweep_reaches_every_team_shape_spare_waves_and_full_and_single_last_waves():
+    plans = [tc.plan(tc.SWEEP_N, C, T) for C in tc.SWEEP_C for T in range(1, tc.THR_MAX_T + 1)]
+    assert {(q["CH"], q["waves"]) for q in plans} == tc.plan_space()
+    assert {q["block"] for q in plans} == {320, 384, 448, 512}
+    for CH, (TT, _) in tc.INSTANCES.items():
+        mine = [q for q in plans if q["CH"] == CH]
+        assert any(q["spare"] >= 1 for q in mine), CH
+        assert any(q["last_nt"] == 1 for q in mine) and any(q["last_nt"] == TT for q in mine), CH
+        assert any(q["groups"] > 1 and q["last_nt"] < TT for q in mine), CH       # a short wave read at blockIdx.y > 0
+    for C, most in tc.SWEEP_C.items():
+        assert {tc.plan(tc.SWEEP_N, C, T)["waves"] for T in range(1, tc.THR_MAX_T + 1)} == set(range(1, most + 1)), C
+    assert all(q["grid_x"] == 3 for q in plans)                                    # more than one workgroup, the last short
+
+
+def test_the_chosen_cases_are_on_the_paths_they_name():
+    for C, CH in tc.CHUNK_EDGE_C.items():
+        assert tc.plan(300, C, 7)["CH"] == CH
+    assert sorted(tc.TILE_PLANS) == sorted(tc.INSTANCES)
+    limits = set()
+    for CH, (C, T, tile_by) in tc.TILE_PLANS.items():
+        q = tc.plan(1, C, T)
+        assert q["CH"] == CH and q["tile_by"] == tile_by
+        limits.add(tile_by)
+        ns = tc.tile_edge_rows(C, T)
+        assert [g for _, g in ns] == [1, 1, 1, 3, 3, 3]
+        for n, g in ns:
+            qn = tc.plan(n, C, T)
+            tail = n - (g - 1) * qn["rows_per_wg"]
+            assert qn["grid_x"] == g and 0 < tail <= qn["rows_per_wg"] and tail > q["tile_rows"] - 2
+        assert [(n - ns[1][0]) for n, _ in ns[:3]] == [-1, 0, 1] and ns[1][0] % q["tile_rows"] == 0
+    assert limits == {"lds", "registers"}
+    assert {tc.plan(1, C, T)["waves"] for C, T, _ in tc.TILE_PLANS.values()} >= {1, 2, 4, 5}
+    q = tc.plan(tc.HALVES_N, 1, tc.HALVES_T)
+    assert (q["rows_per_wg"], q["grid_x"], q["teams"], q["groups"]) == (65535, 513, 1, 1)
+    assert tc.HALVES_N - 512 * 65535 == 1 and tc.HALVES_GRID.size == tc.HALVES_T and tc.HALVES_GRID[0] == -np.inf
+
+
+def test_single_label_shortcut_equals_the_restatement():
+    n = 100000
+    idx, y = tc.halves_case(n)
+    assert (y[:65535] == 1).all() and 0 < y[65535:].sum() < n - 65535
+    got = tc.single_label_counts(idx, y, tc.HALVES_GRID)
+    want = th.threshold_counts_host(tc.LEVELS[idx].reshape(n, 1), y, tc.HALVES_GRID)
+    for f, g in zip(FIELDS, got):
+        w = getattr(want, f)
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), f
+    assert got[2][0, 0] == n and got[1][0, 0] == got[0][0]                          # -inf: every row is predicted
+    small = tc.brute_force_counts(tc.LEVELS[idx[:300]].reshape(300, 1), y[:300], tc.HALVES_GRID.reshape(-1, 1))
+    for f, g, w in zip(FIELDS, tc.single_label_counts(idx[:300], y[:300], tc.HALVES_GRID), small):
+        assert np.array_equal(g, w), f
+
+
+def test_special_at_rebuilds_the_special_cases():
+    p, y, thr = tc.special_at("nan", 200, 449)
+    assert p.shape == (200, 449) and np.isnan(p[17]).all() and np.isnan(p[100]).all() and (y[100] == 0).all()
+    assert 0.03 < np.isnan(p).mean() < 0.08 and thr is tc.GRID7
+    p, y, thr = tc.special_at("infinities", 130, 257)
+    assert (p[3] == np.inf).all() and (p[5, ::2] == -np.inf).all() and np.signbit(p[0, 0]) and p[0, 0] == 0
+    p, y, thr = tc.special_at("all_ones", 150, 1024)
+    c = th.threshold_counts_host(p, y, thr)
+    assert (c.rows[:-1, 2048] == 150).all() and (c.tpsum[:-1, 2048] == 150 * 1024).all() and c.rows[-1, 1024] == 150
