@@ -12,6 +12,8 @@ from .bootstrap import (BootstrapComparison, BootstrapResult, bootstrap_compare,
                         bootstrap_summary, bootstrap_weights, bootstrap_weights_host, metrics_from_sums, weighted_metrics,
                         weighted_sums, weighted_sums_host)
 from .compare import compare_labels  # noqa: F401
+from .compartments import (Compartments, compartment_edge_share, compartment_metrics, compartments_host,  # noqa: F401
+                           compartments_of_matrix, label_density)
 from .handoff import FeatureCollector  # noqa: F401
 from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_from_text, expand_contacts_host,  # noqa: F401
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
@@ -48,4 +50,5 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "BootstrapResult", "BootstrapComparison", "bootstrap_weights_host", "bootstrap_weights", "weighted_sums_host",
            "weighted_sums", "metrics_from_sums", "weighted_metrics", "bootstrap_metrics", "bootstrap_compare",
            "bootstrap_summary", "Insulation", "diamond_sums", "diamond_sums_host", "insulation_from_sums", "insulation_host",
-           "domain_edge_share", "domain_of_windows"]
+           "domain_edge_share", "domain_of_windows", "Compartments", "compartments_host", "compartments_of_matrix",
+           "compartment_edge_share", "compartment_metrics", "label_density"]

@@ -159,6 +159,11 @@ _HEADER = {
     "cgcn_bootstrap_weights_in": (_c_int, "stream n:ll R:i weights tile flags"),
     "cgcn_bootstrap_sums": (_c_int, "stream n:ll C:i R:i order tile fdr_cutoff out"),
     "cgcn_hicinsul_sums": (_c_int, "stream n:i rowptr col val norm n_norm:ll n_windows:i windows out"),
+    "cgcn_hiccomp_dense": (_c_int, "stream n:i rowptr col val norm n_norm:ll rank m:i ld:i B"),
+    "cgcn_hiccomp_dist_sums": (_c_int, "stream n:i m:i ld:i B keep rank dsum"),
+    "cgcn_hiccomp_oe_rows": (_c_int, "stream m:i ld:i B keep e n_e:i ignore_diags:i stages:i mean ss"),
+    "cgcn_hiccomp_corr": (_c_int, "stream m:i ld:i Z C"),
+    "cgcn_hiccomp_step": (_c_int, "stream m:i C v prev n_prev:i y v_next rec"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -293,9 +293,9 @@ def domain_of_windows(window_start, domain_of_bin, domain_bp) -> np.ndarray:
     return np.where(inside, dom[np.clip(b, 0, max(dom.size - 1, 0))] if dom.size else -1, -1).astype(np.int64)
 
 
-def domain_edge_share(graph_or_csr, domain_of_window):
-    """(same_domain_entries, nnz) as exact integers: the stored entries of a graph (a ChromGraph, a scipy matrix, or
-    (rowptr, col[, nnz]) tensors or arrays) whose two windows lie in one domain.  A negative domain never matches."""
+def csr_of(graph_or_csr):
+    """(rowptr int64 [N + 1], col int64 [nnz], nnz) on the host of a graph: a ChromGraph, a scipy matrix, or (rowptr, col[, nnz])
+    tensors or arrays"""
     g = graph_or_csr
     if sp.issparse(g):
         g = sp.csr_matrix(g)
@@ -308,7 +308,13 @@ def domain_edge_share(graph_or_csr, domain_of_window):
         rowptr, col = rowptr.cpu().numpy(), col.cpu().numpy()
     rowptr = np.asarray(rowptr, dtype=np.int64)
     nnz = int(rowptr[-1]) if rowptr.size else 0
-    col = np.asarray(col, dtype=np.int64)[:nnz]
+    return rowptr, np.asarray(col, dtype=np.int64)[:nnz], nnz
+
+
+def domain_edge_share(graph_or_csr, domain_of_window):
+    """(same_domain_entries, nnz) as exact integers: the stored entries of a graph (csr_of's inputs) whose two windows lie in
+    one domain.  A negative domain never matches."""
+    rowptr, col, nnz = csr_of(graph_or_csr)
     dom = np.asarray(domain_of_window, dtype=np.int64).ravel()
     if dom.size != rowptr.size - 1:
         raise ValueError("the graph has %d windows but domain_of_window has %d" % (rowptr.size - 1, dom.size))

@@ -13,6 +13,7 @@ import os
 import time
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import metrics as M
@@ -103,6 +104,16 @@ def run_model(WindowModel, ChromeModel, train_data, valid_data, test_data, crit,
             boot = dict(n_boot=int(opt.bootstrap), block=int(getattr(opt, "bootstrap_block", 1)),   # the chromosomes as strata
                         lengths=[int(test_data[c]["target"].shape[0]) for c in test_data])
         rec["test"] = M.compute_metrics(p, t, tloss, opt, el, bootstrap=boot)
+        comp = (getattr(opt, "compartment_of_window", None) or {}).get("test") if epoch == opt.epochs else None
+        if comp is not None:   # -hic_compartments: the last epoch's test metrics in A and in B (the windows in test_data's order)
+            from . import compartments
+            by = compartments.compartment_metrics(p, t, comp)
+            rec["test"]["compartments"] = {ab: {k: float(np.nanmean(v)) if not np.isnan(v).all() else float("nan") for k, v in m.items()}
+                                          for ab, m in by.items()}
+            if verbose:
+                for ab, m in rec["test"]["compartments"].items():
+                    print("test, compartment %s (%d windows):  %s" % (ab, int(np.sum(comp > 0 if ab == "A" else comp < 0)),
+                                                                      "  ".join("%s %.4f" % kv for kv in m.items())))
         saved = False
         if "valid" in rec:
             saved = log.maybe_checkpoint(epoch, opt, ChromeModel, vloss, vsum)                 # runner.py:57

@@ -11,7 +11,10 @@ Inputs are the reference's own files: `<feat_dir>/chrom_f
 (data/7create_graph_new.py:197-202), or with `-hic_contacts DIR` the contact caches `DIR/<chrom>.cghic` from which the graphs
 are built on the GPU for any `-hicsize` / `-hicnorm` (chromegcn_amd/hic.py).  `-synthetic` replaces them by the seeded GM12878-shaped stand-in.
 `-hic_null distance|degree|uniform` replaces every Hi-C matrix, whatever its source, by its null graph (chromegcn_amd/nullgraph.py):
-the control run that tells what the real contacts add."""
+the control run that tells what the real contacts add.  `-hic_compartments RES_BP` (with `-hic_contacts`) calls every chromosome's A/B
+compartments from its cache's records (chromegcn_amd/compartments.py), oriented by the split's label density, prints the A share, the
+iteration's record and the AA / BB / AB share of the graph the run trains on, and after the last epoch the test metrics in A and in B;
+`-hic_compartment_restrict` trains on the graphs of the contacts within one compartment."""
 from __future__ import annotations
 
 import argparse
@@ -52,6 +55,15 @@ def parse(argv=None):
     ap.add_argument("-hic_domain_res", type=int, default=10000, metavar="BP", help="-hic_domains: the bin size of the insulation score")
     ap.add_argument("-hic_domain_strength", type=float, default=0.5, metavar="X",
                     help="-hic_domains: the least boundary strength (log2 units)")
+    ap.add_argument("-hic_compartments", type=int, default=0, metavar="RES_BP",
+                    help="-hic_contacts: call every chromosome's A/B compartments at this bin size from the cache's records "
+                         "(chromegcn_amd.compartments), oriented by the split's label density; prints per chromosome the A share of "
+                         "the called bins, the eigenvector iteration's record and the AA / BB / AB share of the graph, and after "
+                         "the last epoch the means of the test metrics in A and in B.  0: off")
+    ap.add_argument("-hic_compartment_norm", type=str, default="VC", choices=["KR", "VC", "SQRTVC", "NONE"],
+                    help="-hic_compartments: the balancing of the map the compartments are called on")
+    ap.add_argument("-hic_compartment_restrict", action="store_true",
+                    help="-hic_compartments: build every graph from the contacts within one compartment")
     ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
                     help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
                          "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
@@ -110,6 +122,24 @@ def null_graphs(graphs, opt, dev):
             for i, (c, a) in enumerate(graphs.items())}
 
 
+def report_compartments(opt, split, report, out=None):
+    """-hic_compartments: one line per chromosome of graphs_from_contact_caches' compartment_report, and the calls of the split's
+    windows in the order of its chromosomes kept in opt.compartment_of_window[split] for the metrics after the last epoch"""
+    import numpy as np
+    for c, (comp, _, share) in report.items():
+        info = {k: v[0] for k, v in comp.info.items() if isinstance(v, list)}
+        print("[hic_compartments] %s %s: %d of %d bins called, A share %.3f; converged %s after %d steps, eigenvalue %.4g, "
+              "residual %.2e, %d flat rows; graph entries AA %d BB %d AB %d uncalled %d of %d (%.1f / %.1f / %.1f %%)"
+              % (split, c, int(np.count_nonzero(comp.compartment_of_bin)), comp.n, comp.a_share(), info["converged"],
+                 info["iterations"], info["eigenvalue"], info["residual"], comp.info["flat_rows"], share["AA"], share["BB"],
+                 share["AB"], share["uncalled"], share["nnz"], 100.0 * share["AA"] / max(share["nnz"], 1),
+                 100.0 * share["BB"] / max(share["nnz"], 1), 100.0 * share["AB"] / max(share["nnz"], 1)), file=out)
+    if report:
+        if not hasattr(opt, "compartment_of_window"):
+            opt.compartment_of_window = {}
+        opt.compartment_of_window[split] = np.concatenate([cw for _, cw, _ in report.values()])
+
+
 def load_inputs(opt):
     data, graphs = _load_inputs(opt)
     if getattr(opt, "hic_null", None) and opt.adj_type in ("hic", "both") and not opt.hic_contacts:
@@ -138,6 +168,11 @@ def _load_inputs(opt):
             domains, report = None, {}
             if getattr(opt, "hic_domains", 0):
                 domains = dict(window_bp=opt.hic_domains, resolution_bp=opt.hic_domain_res, min_strength=opt.hic_domain_strength)
+            comps, comp_report = None, {}
+            if getattr(opt, "hic_compartments", 0):
+                comps = dict(resolution_bp=opt.hic_compartments, restrict=bool(opt.hic_compartment_restrict),
+                             norm=None if opt.hic_compartment_norm == "NONE" else opt.hic_compartment_norm,
+                             targets={c: f["target"] for c, f in data[sp].items()})
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
@@ -147,7 +182,9 @@ def _load_inputs(opt):
                                                         expected="auto" if opt.hic_expected else None,
                                                         null=((opt.hic_null, getattr(opt, "hic_null_seed", 0))
                                                               if getattr(opt, "hic_null", None) else None),
-                                                        domains=domains, domain_report=report)
+                                                        domains=domains, domain_report=report,
+                                                        compartments=comps, compartment_report=comp_report)
+            report_compartments(opt, sp, comp_report)
             for c, (n_bound, same, nnz) in report.items():
                 print("[hic_domains] %s %s: %d boundaries, %d of %d entries of the unrestricted graph inside a domain (%.1f %%)"
                       % (sp, c, n_bound, same, nnz, 100.0 * same / max(nnz, 1)))

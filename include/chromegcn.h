@@ -1278,6 +1278,52 @@ int cgcn_bootstrap_sums(cgcn_stream_t stream, long long n, int C, int R, const u
 int cgcn_hicinsul_sums(cgcn_stream_t stream, int n, const int32_t *rowptr, const int32_t *col, const double *val,
                        const double *norm, long long n_norm, int n_windows, const int32_t *windows, double *out);
 
+/*
+ * A/B compartments: the dense middle between the contact matrix and the eigenvector (chromegcn_amd/compartments.py, whose
+ * docstring is the rule).  These five functions are additions to ABI 26 like the functions above:
+ * CGCN_ABI_VERSION stays 26, nothing above changes.
+ *
+ * The dense operands are fp64 and row-major over the m kept bins, 0 <= m <= 8192 (CGCN_ERR_UNSUPPORTED beyond).  B (which
+ * becomes M and then Z in place) has m rows of ld doubles: ld >= m, ld even and B on a 16-byte boundary, so that every row can
+ * be read in 16-byte pieces (CGCN_ERR_BAD_ARG otherwise); the columns [m, ld) are never read or written.  C is m x m.
+ * keep int32 [m]: the kept bins, ascending; rank int32 [n]: the place of a bin in keep, or -1.  A rank outside [0, m), a
+ * column outside [0, n) or a kept bin outside [0, n) is passed over, never followed.
+ * Every sum is taken in a fixed order -- a wavefront per row or per distance, lane l the terms l, l + 64, ... ascending,
+ * one butterfly over the lanes -- without floating-point atomics: the same bits in every run.
+ * Enqueue only: no workspace, no allocation, no synchronisation.  CGCN_ERR_BAD_ARG besides: a NULL pointer that would be read
+ * or written, a negative size.
+ *
+ * cgcn_hiccomp_dense: the matrix of cgcn_hicnorm_fill (n bins; rowptr, col, val) scattered into B, which the caller has
+ *   zero-filled: B[rank[a] ld + rank[b]] = val[a, b] / (nv[a] * nv[b]) for every stored entry whose two bins are kept, one
+ *   fp64 multiplication and one fp64 division; norm fp64 [n_norm] or NULL (val itself) reads as in cgcn_hicinsul_sums.  Each
+ *   entry is written once.
+ * cgcn_hiccomp_dist_sums: dsum[d] = sum over i with keep[i] + d a kept bin of B[i, rank[keep[i] + d]], d in [0, n); every
+ *   entry of dsum fp64 [n] is written.  Zeros of B take part; each unordered pair is met once.
+ * cgcn_hiccomp_oe_rows: stages & 1: M[i, j] = B[i, j] / e[d] with d = |keep[j] - keep[i]| where d >= ignore_diags, d < n_e and
+ *   e[d] > 0, else 1.0, in place; mean[i] = (sum_j M[i, j]) / m; ss[i] = sum_j (M[i, j] - mean[i])^2.  stages & 2:
+ *   Z[i, j] = (M[i, j] - mean[i]) / sqrt(ss[i]) in place from mean and ss as they stand, 0 in a row with ss[i] == 0 (NaN
+ *   counts as not above 0).  stages is 1, 2 or 3 (both, in this order).
+ * cgcn_hiccomp_corr: C = Z Z^T on v_mfma_f64_16x16x4_f64, K ascending in one accumulator chain per element; an element with
+ *   column >= row is stored to both (i, j) and (j, i): C is symmetric bit for bit.
+ * cgcn_hiccomp_step: one step of the deflated power iteration, m >= 1: y = C v; dot_p = prev[p] . y for p < n_prev <= 2
+ *   (prev fp64 [n_prev][m]; CGCN_ERR_UNSUPPORTED beyond 2); y -= sum_p dot_p prev[p]; lambda = v . y;
+ *   rec[0] = lambda, rec[1] = |y|^2, rec[2] = |y - lambda v|^2, rec[3], rec[4] = dot_0, dot_1 (rec fp64 [8]);
+ *   v_next = y / |y| (y itself where |y| = 0).  y fp64 [m] is left as deflated; v_next must not be v.
+ */
+int cgcn_hiccomp_dense(cgcn_stream_t stream, int n, const int32_t *rowptr, const int32_t *col, const double *val,
+                       const double *norm, long long n_norm, const int32_t *rank, int m, int ld, double *B);
+
+int cgcn_hiccomp_dist_sums(cgcn_stream_t stream, int n, int m, int ld, const double *B, const int32_t *keep,
+                           const int32_t *rank, double *dsum);
+
+int cgcn_hiccomp_oe_rows(cgcn_stream_t stream, int m, int ld, double *B, const int32_t *keep, const double *e, int n_e,
+                         int ignore_diags, int stages, double *mean, double *ss);
+
+int cgcn_hiccomp_corr(cgcn_stream_t stream, int m, int ld, const double *Z, double *C);
+
+int cgcn_hiccomp_step(cgcn_stream_t stream, int m, const double *C, const double *v, const double *prev, int n_prev,
+                      double *y, double *v_next, double *rec);
+
 #ifdef __cplusplus
 }
 #endif
