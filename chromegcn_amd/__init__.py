@@ -19,10 +19,13 @@ from .hic import (HicContacts, build_hic_graph, build_hic_graph_host, contacts_f
                   parse_contacts_text_host, release_text_staging, windows_from_bed)
 from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_norm_vector_host,  # noqa: F401
                       kr_balance_host)
-from .hicdist import (distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
+from .hicdist import (distance_sums_device_order_host, distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
                       hic_expected_vector)
 from .insulation import (Insulation, diamond_sums, diamond_sums_host, domain_edge_share, domain_of_windows,  # noqa: F401
                          insulation_from_sums, insulation_host)
+from .loops import (Loops, chunk_boundaries, enriched_pixels, enriched_pixels_host, loop_band, loop_edge_share,  # noqa: F401
+                    loop_histograms, loop_histograms_host, loop_lambdas_host, loop_thresholds, loops_from_pixels, loops_host,
+                    loops_of_matrix, neighbourhood_offsets, same_loop_host)
 from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
 from .nullgraph import (NullGraphTest, null_chrom_graph, null_graph, null_graph_host, null_graph_test,  # noqa: F401
                         null_statistics)
@@ -51,4 +54,7 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "weighted_sums", "metrics_from_sums", "weighted_metrics", "bootstrap_metrics", "bootstrap_compare",
            "bootstrap_summary", "Insulation", "diamond_sums", "diamond_sums_host", "insulation_from_sums", "insulation_host",
            "domain_edge_share", "domain_of_windows", "Compartments", "compartments_host", "compartments_of_matrix",
-           "compartment_edge_share", "compartment_metrics", "label_density"]
+           "compartment_edge_share", "compartment_metrics", "label_density", "Loops", "neighbourhood_offsets",
+           "chunk_boundaries", "loop_thresholds", "loops_from_pixels", "loop_lambdas_host", "loop_histograms_host",
+           "enriched_pixels_host", "loops_host", "loop_band", "loop_histograms", "enriched_pixels", "loops_of_matrix",
+           "same_loop_host", "loop_edge_share"]

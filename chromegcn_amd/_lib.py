@@ -164,6 +164,13 @@ _HEADER = {
     "cgcn_hiccomp_oe_rows": (_c_int, "stream m:i ld:i B keep e n_e:i ignore_diags:i stages:i mean ss"),
     "cgcn_hiccomp_corr": (_c_int, "stream m:i ld:i Z C"),
     "cgcn_hiccomp_step": (_c_int, "stream m:i C v prev n_prev:i y v_next rec"),
+    "cgcn_hicloops_band": (_c_int, "stream n:i rowptr col val width:i band"),
+    "cgcn_hicloops_pass1": (_c_int, "stream n:i D:i width:i band vc norm n_norm:ll expected n_expected:ll p:i w:i ignore_diags:i "
+                                    "min_dist:i bounds n_chunks:i W:i hist flags lambda_out"),
+    "cgcn_hicloops_workspace_bytes": (_c_sz, "n:i D:i"),
+    "cgcn_hicloops_count": (_c_int, "stream n:i D:i width:i band flags thr n_chunks:i W:i workspace workspace_bytes:z total"),
+    "cgcn_hicloops_write": (_c_int, "stream n:i D:i width:i band vc norm n_norm:ll expected n_expected:ll p:i w:i ignore_diags:i "
+                                    "flags thr n_chunks:i W:i capacity:ll workspace workspace_bytes:z pix_ij pix_val"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

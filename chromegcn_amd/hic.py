@@ -55,7 +55,14 @@ rule above, bit for bit.
 
 Compartments (chromegcn_amd/compartments.py holds the rule).  HicContacts.compartments calls the A/B
 compartments of the records; its as_domains() with its resolution is a `domains` pair like any other, so the restriction to
-contacts within one compartment needs nothing of the builders."""
+contacts within one compartment needs nothing of the builders.
+
+Loops (loops; DESIGN.md section 4.19, chromegcn_amd/loops.py holds the rule).  loops = a Loops, (Loops, pad_bins) or a dict of
+HicContacts.loops' keywords (plus pad_bins) computed from the records: a record takes part only if its pixel
+(pos1 // res, pos2 // res), lower bin first and res the loops' resolution, lies within Chebyshev distance pad_bins (default 1)
+of some loop's peak.  The test is on the SOURCE record; named norms, expected = "auto" and a dict of loops are still computed
+from ALL records; the kept records stay in file order; with domains both tests must hold.  loops = None is the rule above, bit
+for bit."""
 from __future__ import annotations
 
 from typing import Dict, NamedTuple, Optional
@@ -71,6 +78,7 @@ from .compartments import (Compartments, compartment_edge_share, compartment_met
                            compartments_of_matrix, label_density)
 from .hiccache import (HostContacts, contact_cache_path, load_contacts_cache, load_contacts_text,  # noqa: F401
                        save_contacts_cache, windows_from_bed)
+from .loops import Loops, loop_edge_share, loops_host, loops_of_matrix, same_loop_host  # noqa: F401
 from .hictext import TEXT_LINE_MAX, TEXT_MALFORMED, TEXT_SLOW, parse_contacts_text, parse_contacts_text_host  # noqa: F401
 
 
@@ -185,14 +193,27 @@ def _host_domains(domains, pos1, pos2, count, resolution_bp):
     return insulation.check_domains(domains, resolution_bp)
 
 
+def _host_loops(loops, pos1, pos2, count):
+    """the builders' `loops` on the host: None, or (Loops, pad_bins) -- a dict is computed from the records"""
+    if loops is None:
+        return None
+    from . import loops as LP
+    if isinstance(loops, dict):
+        kw = dict(loops)
+        pad = kw.pop("pad_bins", 1)
+        loops = (LP.loops_host(pos1, pos2, count, **kw), pad)
+    return LP.check_loops(loops)
+
+
 def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp=None, min_distance_bp=0, expected=None,
-                    expected_args=None, domains=None):
+                    expected_args=None, domains=None, loops=None):
     """(record index, i, j, value) of the surviving records in file order (rules 1 and 2).  With window_bp: of the surviving
     records of the expanded file, the index being the position in it.  min_distance_bp, expected (None, a vector, or "auto":
     hicdist.expected_vector_host with this norm and expected_args): the minimum gap and the observed / expected value of the
-    module docstring.  domains: the module docstring's; the indices stay those of the whole file."""
+    module docstring.  domains, loops: the module docstring's; the indices stay those of the whole file."""
     up = _upsample(resolution_bp, window_bp)
     domains = _host_domains(domains, pos1, pos2, count, resolution_bp)
+    loops = _host_loops(loops, pos1, pos2, count)
     gap = _gap(min_distance_bp)
     ws = _windows(window_start).astype(np.int64)
     p1, p2 = np.asarray(pos1, dtype=np.int64), np.asarray(pos2, dtype=np.int64)
@@ -207,6 +228,9 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
         from . import insulation
         same = insulation.same_domain_host(p1, p2, *domains)
         keep = same if keep is None else keep & same
+    if loops is not None:
+        near = same_loop_host(p1, p2, *loops)
+        keep = near if keep is None else keep & near
     if up > 1:
         src, a, b, i, j = _survivors_up(p1, p2, ws, int(resolution_bp) // up, up, keep)
         idx = src * (up * up) + a * up + b
@@ -237,12 +261,14 @@ def survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window
 
 
 def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, window_bp=None,
-                         norm_args=None, min_distance_bp=0, expected=None, expected_args=None, domains=None) -> sp.csr_matrix:
+                         norm_args=None, min_distance_bp=0, expected=None, expected_args=None, domains=None,
+                         loops=None) -> sp.csr_matrix:
     """The {0,1} float64 CSR the reference's step 7 pickles (symmetric, zero diagonal, sorted columns).  With window_bp: of
     the expanded file, which is never written out (the CPU path for coarse records at full size).  norm = 'KR' / 'VC' /
     'SQRTVC': the vector computed from the records (hicnorm.hic_norm_vector_host with norm_args).  min_distance_bp, expected
     (None, a vector, or "auto": hicdist.expected_vector_host with the same norm and expected_args = n_bins / min_count).
-    domains: None, (domain_of_bin, domain_bp), or a dict of insulation.domains_host's keywords (the module docstring)."""
+    domains: None, (domain_of_bin, domain_bp), or a dict of insulation.domains_host's keywords (the module docstring).
+    loops: None, a Loops, (Loops, pad_bins), or a dict of loops.loops_host's keywords plus pad_bins (the module docstring)."""
     ws = _windows(window_start)
     n = ws.size
     k = _budget(hic_edges)
@@ -255,7 +281,7 @@ def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, h
         hicnorm._require_converged(info)
         norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
     _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected,
-                                 domains=domains)
+                                 domains=domains, loops=loops)
     take = np.argsort(-v, kind="stable")[:k]
     i, j = i[take], j[take]
     a = sp.coo_matrix((np.ones(2 * i.size), (np.concatenate([i, j]), np.concatenate([j, i]))), shape=(n, n)).tocsr()
@@ -303,6 +329,8 @@ class HicContacts:
         self._insulations = {}     # insulation's argument tuple -> insulation.Insulation
         self._compartments = {}    # compartments' argument tuple (without orient) -> compartments.Compartments
         self._within = []          # (domain_of_bin, domain_bp, the HicContacts of the kept records): the last few selections
+        self._loops = {}           # loops' argument tuple -> loops.Loops
+        self._within_loops = []    # (Loops, pad_bins, the HicContacts of the kept records): the last few selections
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
 
     @classmethod
@@ -534,6 +562,72 @@ class HicContacts:
         self._within = self._within[-3:] + [(dom, bp, c)]
         return c
 
+    def loops(self, norm="VC", resolution_bp=10000, expected="auto", n_bins=None, norm_args=None, expected_args=None, **rule):
+        """The chromatin loops of the records (chromegcn_amd/loops.py's rule): the band and the two stencil passes on the device
+        from contact_matrix(resolution_bp, n_bins), thresholds and clusters on the host.  norm: None, a vector at resolution_bp,
+        or 'KR' / 'VC' / 'SQRTVC' (norm_vector with norm_args; a KR that did not converge raises HicNormError); expected: "auto"
+        (expected_vector with this norm and expected_args = min_count) or a float64 vector.  **rule: loops.loop_rule's.  Kept per
+        argument tuple for None and the three names with expected = "auto"."""
+        from . import loops as LP
+        res = int(resolution_bp)
+        checked = LP.loop_rule(res, 0, **rule)
+        if isinstance(expected, str) and expected != "auto":
+            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
+        nk = self._norm_key(norm, norm_args) if isinstance(expected, str) else None
+        key = None if nk is None else nk + (res, None if n_bins is None else int(n_bins), checked) + tuple(
+            sorted((expected_args or {}).items()))
+        if key is not None and key in self._loops:
+            return self._loops[key]
+        a = self.contact_matrix(res, n_bins)
+        LP.loop_rule(res, a.n, **rule)   # the size guard, before anything is allocated
+        if isinstance(expected, str):
+            ex = self.expected_vector(norm, res, n_bins=a.n, norm_args=norm_args, **(expected_args or {}))
+        else:
+            ex = self._norm(expected)
+        nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+        out = LP.loops_of_matrix(a, nv, ex, res, **rule)
+        if key is not None:
+            self._loops[key] = out
+        return out
+
+    def within_loops(self, loops, pad_bins=1) -> "HicContacts":
+        """the records whose pixel lies in some loop's footprint (loops.py's rule 12), in file order, as a HicContacts of their
+        own: a sorted int64 key table, torch.searchsorted, boolean indexing -- one host sync for the size"""
+        from . import loops as LP
+        loops, pad = LP.check_loops((loops, pad_bins))
+        res = loops.resolution_bp
+        with torch.cuda.device(self.device):
+            keys = torch.from_numpy(loops.footprint_keys(pad)).to(self.device)
+            b1 = torch.div(self.pos1, res, rounding_mode="floor").long()
+            b2 = torch.div(self.pos2, res, rounding_mode="floor").long()
+            lo, hi = torch.minimum(b1, b2), torch.maximum(b1, b2)
+            keep = (lo >= 0) & (hi < loops.n)
+            if keys.numel():
+                key = lo * LP._KEY + hi
+                at = torch.searchsorted(keys, key).clamp(max=keys.numel() - 1)
+                keep &= keys[at] == key
+            else:
+                keep &= False
+            return HicContacts(self.pos1[keep], self.pos2[keep], self.count[keep], self.device)
+
+    def _resolve_loops(self, loops):
+        """(Loops, pad_bins) of the builders' `loops`; a dict is computed from THESE records"""
+        from . import loops as LP
+        if isinstance(loops, dict):
+            kw = dict(loops)
+            pad = kw.pop("pad_bins", 1)
+            loops = (self.loops(**kw), pad)
+        return LP.check_loops(loops)
+
+    def _loop_selection(self, loops, pad) -> "HicContacts":
+        """within_loops, the last few kept"""
+        for lp, pd, c in self._within_loops:
+            if lp is loops and pd == pad:
+                return c
+        c = self.within_loops(loops, pad)
+        self._within_loops = self._within_loops[-3:] + [(loops, pad, c)]
+        return c
+
     def _norm(self, norm) -> Optional[torch.Tensor]:
         if norm is None:
             return None
@@ -605,7 +699,7 @@ class HicContacts:
         return self._survivors[key]
 
     def build_raw(self, norm, resolution_bp, window_start, hic_edges, window_bp=None, norm_args=None, min_distance_bp=0,
-                  expected=None, expected_args=None, domains=None):
+                  expected=None, expected_args=None, domains=None, loops=None):
         """(rowptr int32 [N + 1], col int32 [>= nnz], sizes int64 [2] = (nnz, survivors)), all on the device, enqueued
         on the current stream: the {0,1} CSR of the reference's matrix.  No host sync beyond survivors() -- and, for
         norm = 'KR' / 'VC' / 'SQRTVC', those of norm_vector(norm, resolution_bp, **norm_args) when it is not cached; a KR
@@ -613,7 +707,9 @@ class HicContacts:
         with the same norm and expected_args = n_bins / min_count): the module docstring's rules 3 and 4; with the defaults
         the entry points and the graph are the ones without them.  domains (None, (domain_of_bin, domain_bp), or a dict of
         domains()' keywords): names and "auto" are resolved on all records, then the same entry points build from the
-        records within domains (within_domains; one more host sync per new selection)."""
+        records within domains (within_domains; one more host sync per new selection).  loops (None, a Loops, (Loops,
+        pad_bins), or a dict of loops()' keywords plus pad_bins): resolved on all records like domains, then the records within
+        the loops' footprints are selected (within_loops; one more host sync per new selection), after those within domains."""
         from . import _lib
         k = _budget(hic_edges)
         gap = _gap(min_distance_bp)
@@ -624,9 +720,15 @@ class HicContacts:
             norm = self._named_norm(norm, resolution_bp, norm_args)
             ws_last = _windows(window_start.cpu().numpy() if torch.is_tensor(window_start) else window_start)
             norm = hicnorm.pad_vector(norm, int(ws_last[-1]) // int(resolution_bp) + 1 if ws_last.size else 0)
-        if domains is not None:
-            return self._selection(domains, resolution_bp).build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
-                                                                     min_distance_bp=gap, expected=expected)
+        if domains is not None or loops is not None:
+            sel = self
+            found = None if loops is None else self._resolve_loops(loops)
+            if domains is not None:
+                sel = self._selection(domains, resolution_bp)
+            if found is not None:
+                sel = sel._loop_selection(*found)
+            return sel.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp, min_distance_bp=gap,
+                                 expected=expected)
         _upsample(resolution_bp, window_bp)
         self._set_windows(window_start)
         route = self._route(resolution_bp, window_bp)
@@ -658,15 +760,15 @@ class HicContacts:
         return rowptr, col, sizes
 
     def build(self, norm, resolution_bp, window_start, hic_edges, adj_type="hic", return_raw=False, window_bp=None,
-              norm_args=None, min_distance_bp=0, expected=None, expected_args=None, null=None, domains=None):
+              norm_args=None, min_distance_bp=0, expected=None, expected_args=None, null=None, domains=None, loops=None):
         """ChromGraph of process_graph(adj_type, ...) over the top-K contact matrix; the matrix itself never visits the
         host.  return_raw=True: (graph, the {0,1} scipy CSR the reference pickles) -- one more read-back.  norm: a vector,
         None, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; norm_args: norm_vector's keywords).  min_distance_bp,
-        expected, expected_args, domains: build_raw's.  null = (model, seed): the matrix is replaced by its null graph
+        expected, expected_args, domains, loops: build_raw's.  null = (model, seed): the matrix is replaced by its null graph
         (chromegcn_amd.nullgraph) before the normalisation; return_raw then returns the null matrix."""
         rowptr, col, sizes = self.build_raw(norm, resolution_bp, window_start, hic_edges, window_bp=window_bp,
                                             norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected,
-                                            expected_args=expected_args, domains=domains)
+                                            expected_args=expected_args, domains=domains, loops=loops)
         if null is not None:
             from . import nullgraph
             rowptr, col, sizes = nullgraph.null_graph((rowptr, col), model=null[0], seed=null[1], device=self.device)
@@ -681,17 +783,17 @@ class HicContacts:
 
 def build_hic_graph(pos1, pos2, count, norm, resolution_bp, window_start, hic_edges, adj_type="hic", device="cuda",
                     return_raw=False, window_bp=None, norm_args=None, min_distance_bp=0, expected=None, expected_args=None,
-                    null=None, domains=None):
+                    null=None, domains=None, loops=None):
     """build_hic_graph_host on the device, handed straight to the device normaliser: contacts in, ChromGraph out.
     `pos1` may be a HicContacts (then pos2 and count are ignored): nothing is uploaded again.  window_bp: the records are
     coarser than the windows and stand for their expanded file (the module's docstring).  min_distance_bp, expected (None, a
     vector, "auto"), expected_args: the minimum gap and the observed / expected value (the module's docstring).  null,
-    domains: HicContacts.build's."""
+    domains, loops: HicContacts.build's."""
     _upsample(resolution_bp, window_bp)
     c = pos1 if isinstance(pos1, HicContacts) else HicContacts(pos1, pos2, count, device)
     return c.build(norm, resolution_bp, window_start, hic_edges, adj_type=adj_type, return_raw=return_raw, window_bp=window_bp,
                    norm_args=norm_args, min_distance_bp=min_distance_bp, expected=expected, expected_args=expected_args, null=null,
-                   domains=domains)
+                   domains=domains, loops=loops)
 
 
 def contacts_from_text(path_or_bytes, device="cuda", **kw) -> HicContacts:
@@ -704,7 +806,8 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                                compute_norm: bool = False, min_distance_bp=0, expected=None,
                                expected_args=None, null=None, domains=None,
                                domain_report: Optional[dict] = None, compartments: Optional[dict] = None,
-                               compartment_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
+                               compartment_report: Optional[dict] = None, loops: Optional[dict] = None,
+                               loop_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
@@ -721,7 +824,10 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
     `targets` ({chrom: label matrix}: every vector is oriented by compartments.label_density of the chromosome's windows) and
     `restrict` (`-hic_compartment_restrict`: every graph is built with domains = as_domains(), the contacts within one
     compartment; not together with `domains`).  compartment_report: a dict that receives {chrom: (Compartments,
-    compartment_of_windows, compartments.compartment_edge_share of the graph that is returned)}."""
+    compartment_of_windows, compartments.compartment_edge_share of the graph that is returned)}.  loops (`-hic_loops`): a dict
+    of HicContacts.loops' keywords plus `pad_bins` and `restrict` (`-hic_loop_restrict`: every graph is built from the records
+    inside the footprints of the loops called from its cache's records; with `domains` both tests hold).  loop_report: a dict
+    that receives {chrom: (Loops, entries in a footprint, nnz)} of the UNRESTRICTED top-K matrix (loops.loop_edge_share)."""
     from . import hicnorm as HN
     from . import nullgraph
     out = {}
@@ -768,11 +874,23 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                                  CP.label_density(labels[chrom], c.window_start, comp.resolution_bp, comp.n))
             if restrict:
                 dom = (comp.as_domains(), comp.resolution_bp)
+        found = None
+        if loops is not None:
+            kw = dict(loops)
+            restrict, pad = kw.pop("restrict", False), kw.pop("pad_bins", 1)
+            if not isinstance(rec[0], HicContacts):
+                rec = (HicContacts(c.pos1, c.pos2, c.count, device), None, None)
+            called = rec[0].loops(**kw)
+            if loop_report is not None:
+                rp, ci_, _ = rec[0].build_raw(norm, c.resolution_bp, c.window_start, int(hicsize), min_distance_bp=min_distance_bp,
+                                              expected=ex, expected_args=expected_args, **up)
+                loop_report[chrom] = (called,) + loop_edge_share((rp, ci_), called, c.window_start, pad)
+            found = (called, pad) if restrict else None
         out[chrom] = build_hic_graph(*rec, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device,
                                      min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args,
                                      null=None if null is None else (null[0], nullgraph.replicate_seed(null[1], 0, ci, len(chroms))),
-                                     domains=dom, **up)
+                                     domains=dom, loops=found, **up)
         if compartments is not None and compartment_report is not None:
             cw = comp.compartment_of_windows(c.window_start)
             compartment_report[chrom] = (comp, cw, CP.compartment_edge_share(out[chrom], cw))

@@ -12,6 +12,7 @@ that is negative or not finite, or a negative position (as in hicnorm).
      the records at distance d, diagonal records at d = 0; both float64 [n_bins].  Host statement: np.bincount(d, weights=...,
      minlength=n_bins), that is, record order; the device adds the same terms in another fixed order, so raw is bit-equal
      for integer counts below 2^53 and act[d] is within 2 (k_d - 1) 2^-53 relative, k_d the records at that distance.
+     distance_sums_device_order_host restates the device's order in numpy, bit for bit.
   2. Expected vector.  poss[d] = n_bins - d.  For each d, w_d is the smallest w >= 0 whose window [max(d - w, 0),
      min(d + w, n_bins - 1)] has sum raw >= min_count; if no window reaches min_count the whole range is used.  min_count
      defaults to 400, Juicer's shot-noise mark.  The window is chosen from the RAW sums for every kind of norm: shot noise is a
@@ -73,6 +74,66 @@ def distance_sums_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         w = c / (nv[i] * nv[j])
     return raw, np.bincount(d, weights=w, minlength=n).astype(np.float64)
+
+
+def _device_order_sum(d_sorted, v_sorted, n):
+    """out[d] = the sum of v over the records at distance d in the order of csrc/cgcn_hicdist.hip, from the values sorted by
+    (distance, record): tiles of 64 sorted values, a segmented scan over a tile's lanes in six doubling steps, then per distance
+    lane l adds the partials of its tiles l, l + 64, ... in tile order and one butterfly (32, 16, ..., 1) joins the lanes"""
+    M = d_sorted.size
+    out = np.zeros(n)
+    if M == 0 or n == 0:
+        return out
+    T = (M + 63) // 64
+    d = np.full(T * 64, -1, np.int64)
+    v = np.zeros(T * 64)
+    d[:M], v[:M] = d_sorted, v_sorted
+    d, v = d.reshape(T, 64), v.reshape(T, 64)
+    o = 1
+    while o < 64:   # every lane reads the values of the step before
+        nxt = v.copy()
+        nxt[:, o:] = np.where(d[:, o:] == d[:, :-o], v[:, :-o] + v[:, o:], v[:, o:])
+        v, o = nxt, o * 2
+    v = v.reshape(-1)
+    s = np.searchsorted(d_sorted, np.arange(n), side="left")
+    e = np.searchsorted(d_sorted, np.arange(n), side="right")
+    has = e > s
+    t0, t1 = s // 64, (np.maximum(e, 1) - 1) // 64
+    lane = np.arange(64, dtype=np.int64)[None, :]
+    acc = np.zeros((n, 64))
+    for k in range(int(np.max(np.where(has, t1 - t0, 0))) // 64 + 1):
+        t = t0[:, None] + lane + 64 * k
+        ok = has[:, None] & (t <= t1[:, None])
+        at = np.minimum(e[:, None], 64 * (t + 1)) - 1          # the last lane of the run inside tile t
+        acc += np.where(ok, v[np.clip(at, 0, v.size - 1)], 0.0)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, np.arange(64) ^ o]
+    out[has] = acc[has, 0]
+    return out
+
+
+def distance_sums_device_order_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm_args=None):
+    """(raw, act) of rule 1 with the terms added in the DEVICE's fixed order (csrc/cgcn_hicdist.hip) instead of record order:
+    bit for bit what HicContacts.distance_sums returns for the same records and vector.  For host restatements that must
+    reproduce a device result that depends on the expected vector to the last bit (chromegcn_amd/loops.py)."""
+    res = int(resolution_bp)
+    raw, _ = distance_sums_host(pos1, pos2, count, norm, res, n_bins, norm_args)    # the checks; raw sizes the vectors
+    n = raw.size
+    p1, p2 = np.asarray(pos1, dtype=np.int64).ravel(), np.asarray(pos2, dtype=np.int64).ravel()
+    c = np.asarray(count, dtype=np.float64).ravel()
+    i, j = p1 // res, p2 // res
+    d = np.abs(i - j)
+    order = np.argsort(d, kind="stable")                                            # the key is (distance, record)
+    norm = _resolve_norm_host(pos1, pos2, count, norm, res, n_bins, norm_args)
+    w = c
+    if norm is not None:
+        nv = np.full(max(n, 1), np.inf)
+        given = np.array(norm, dtype=np.float64).ravel()[:n]
+        nv[:given.size] = given
+        nv[np.isnan(nv) | (nv == 0.0)] = np.inf
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            w = c / (nv[i] * nv[j])
+    return _device_order_sum(d[order], c[order], n), _device_order_sum(d[order], w[order], n)
 
 
 def expected_from_sums(raw, act, min_count=MIN_COUNT, return_info=False):

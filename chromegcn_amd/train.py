@@ -14,7 +14,9 @@ are built on the GPU for any `-hicsize` / `-hicnorm` (chromegcn_amd/hic.py).  `-
 the control run that tells what the real contacts add.  `-hic_compartments RES_BP` (with `-hic_contacts`) calls every chromosome's A/B
 compartments from its cache's records (chromegcn_amd/compartments.py), oriented by the split's label density, prints the A share, the
 iteration's record and the AA / BB / AB share of the graph the run trains on, and after the last epoch the test metrics in A and in B;
-`-hic_compartment_restrict` trains on the graphs of the contacts within one compartment."""
+`-hic_compartment_restrict` trains on the graphs of the contacts within one compartment.  `-hic_loops RES_BP` (with `-hic_contacts`) calls
+every chromosome's chromatin loops from its cache's records (chromegcn_amd/loops.py) and prints the loop count and the share of the
+unrestricted graph inside loop footprints; `-hic_loop_restrict` trains on the graphs of the contacts inside the footprints."""
 from __future__ import annotations
 
 import argparse
@@ -64,6 +66,16 @@ def parse(argv=None):
                     help="-hic_compartments: the balancing of the map the compartments are called on")
     ap.add_argument("-hic_compartment_restrict", action="store_true",
                     help="-hic_compartments: build every graph from the contacts within one compartment")
+    ap.add_argument("-hic_loops", type=int, default=0, metavar="RES_BP",
+                    help="-hic_contacts: call every chromosome's chromatin loops at this bin size (5000, 10000 or 25000) from the "
+                         "cache's records (chromegcn_amd.loops); prints per chromosome the loop count and the share of the "
+                         "unrestricted graph inside loop footprints.  0: off")
+    ap.add_argument("-hic_loop_norm", type=str, default="VC", choices=["KR", "VC", "SQRTVC", "NONE"],
+                    help="-hic_loops: the balancing of the map the loops are called on")
+    ap.add_argument("-hic_loop_fdr", type=float, default=0.1, metavar="Q", help="-hic_loops: the false discovery rate of the thresholds")
+    ap.add_argument("-hic_loop_pad", type=int, default=1, metavar="BINS", help="-hic_loops: a footprint reaches this far around a peak")
+    ap.add_argument("-hic_loop_restrict", action="store_true",
+                    help="-hic_loops: build every graph from the contacts inside loop footprints")
     ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
                     help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
                          "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
@@ -173,6 +185,10 @@ def _load_inputs(opt):
                 comps = dict(resolution_bp=opt.hic_compartments, restrict=bool(opt.hic_compartment_restrict),
                              norm=None if opt.hic_compartment_norm == "NONE" else opt.hic_compartment_norm,
                              targets={c: f["target"] for c, f in data[sp].items()})
+            loops, loop_report = None, {}
+            if getattr(opt, "hic_loops", 0):
+                loops = dict(resolution_bp=opt.hic_loops, norm=None if opt.hic_loop_norm == "NONE" else opt.hic_loop_norm,
+                             fdr=opt.hic_loop_fdr, pad_bins=opt.hic_loop_pad, restrict=bool(opt.hic_loop_restrict))
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
@@ -183,8 +199,14 @@ def _load_inputs(opt):
                                                         null=((opt.hic_null, getattr(opt, "hic_null_seed", 0))
                                                               if getattr(opt, "hic_null", None) else None),
                                                         domains=domains, domain_report=report,
-                                                        compartments=comps, compartment_report=comp_report)
+                                                        compartments=comps, compartment_report=comp_report,
+                                                        loops=loops, loop_report=loop_report)
             report_compartments(opt, sp, comp_report)
+            for c, (called, inside, nnz) in loop_report.items():
+                print("[hic_loops] %s %s: %d loops from %d candidates (%d enriched pixels, %d after the ratios); %d of %d entries of the "
+                      "unrestricted graph inside a footprint (%.1f %%)"
+                      % (sp, c, len(called), called.info["candidates"], called.info["enriched"], called.info["kept_after_ratios"],
+                         inside, nnz, 100.0 * inside / max(nnz, 1)))
             for c, (n_bound, same, nnz) in report.items():
                 print("[hic_domains] %s %s: %d boundaries, %d of %d entries of the unrestricted graph inside a domain (%.1f %%)"
                       % (sp, c, n_bound, same, nnz, 100.0 * same / max(nnz, 1)))

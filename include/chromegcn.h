@@ -1324,6 +1324,58 @@ int cgcn_hiccomp_corr(cgcn_stream_t stream, int m, int ld, const double *Z, doub
 int cgcn_hiccomp_step(cgcn_stream_t stream, int m, const double *C, const double *v, const double *prev, int n_prev,
                       double *y, double *v_next, double *rec);
 
+/*
+ * Chromatin loops after HiCCUPS: pixels enriched over four local backgrounds (chromegcn_amd/loops.py, whose docstring is the
+ * rule).  These five functions are additions to ABI 26 like the functions above: CGCN_ABI_VERSION
+ * stays 26, nothing above changes.
+ *
+ * The matrix is what cgcn_hicnorm_fill writes (n bins; rowptr, col, val; vc fp64 [n] its row sums).  band fp64 [n][width] is
+ * the raw band, band[i width + d] = A[i, i + d], 0 where i + d >= n.  A pixel is (i, d), 0 <= i < n, 0 <= d <= D, in the order
+ * q = i (D + 1) + d, which is ascending (i, j = i + d).  p < w <= 10 are the peak and window half-widths; width >= D + 2 w + 1
+ * (CGCN_ERR_BAD_ARG below it: the neighbourhoods of the pixels at distance D reach that far).  norm fp64 [n_norm] or NULL: a
+ * bin is valid iff vc > 0 and its norm value is finite, not NaN and not 0 (a bin outside the vector is not valid); expected
+ * fp64 [n_expected], n_expected >= min(n, D + 1), is read at the distance of every cell that takes part and reads as 0 beyond
+ * its length.  n_chunks <= 64 chunks have the n_chunks - 1 ascending boundaries `bounds` (fp64, device); counts are clipped to
+ * W - 1, W <= 65 536.  n (D + 1) must not exceed 2^28.  CGCN_ERR_UNSUPPORTED beyond these limits.
+ *
+ * cgcn_hicloops_band: fills band from the matrix; the caller has zero-filled it.  Any width >= 1.
+ * cgcn_hicloops_pass1: per pixel the sums S, T and the counts C of the four neighbourhoods (donut, lower-left, horizontal,
+ *   vertical), each ONE sequential fp64 sum over its cells in row-major (da, db) order; the candidate test (both bins valid,
+ *   min_dist <= d, T > 0 and 2 C >= the full size for all four); lambda_x = ((S_x / T_x) * expected[d]) * (nv[i] * nv[j]);
+ *   k_x = the number of bounds <= lambda_x (all of them for a NaN).  flags uint32 [n (D + 1)], every entry written: 0, or
+ *   1 << 31 | k_v << 18 | k_h << 12 | k_ll << 6 | k_donut for a candidate.  hist int32 [4][n_chunks][W], zeroed by the caller:
+ *   hist[x][k_x][min(rint(A[i, j]), W - 1)] += 1 per candidate (integer atomics).  lambda_out fp64 [4][n][D + 1] or NULL: the
+ *   four lambda, NaN off the candidates, every entry written.
+ * cgcn_hicloops_count: total[0] (int64, device) = the number of enriched pixels: candidates with
+ *   min(rint(A[i, j]), W - 1) >= thr[x n_chunks + k_x] for all four x; thr int32 [4][n_chunks] on the device.  It leaves the
+ *   per-tile offsets in the workspace for cgcn_hicloops_write, which must be given the same workspace, flags and thr.
+ * cgcn_hicloops_write: the enriched pixels in ascending (i, j): pix_ij int32 [capacity][2] = (i, j), pix_val fp64
+ *   [capacity][5] = (A[i, j], lambda_donut, lambda_ll, lambda_h, lambda_v), the sums repeated for these pixels alone in pass
+ *   1's order (the same bits).  Pixels beyond capacity are dropped.
+ *
+ * Every sum runs in a fixed order and the only atomics are integer ones: the same bits in every run.  Enqueue only: no
+ * allocation, no synchronisation.  CGCN_ERR_BAD_ARG: a NULL pointer that would be read or written, a negative size, w < 1,
+ * p outside [0, w), n_chunks < 2, W < 1, norm with n_norm < 1; CGCN_ERR_WORKSPACE: workspace_bytes below
+ * cgcn_hicloops_workspace_bytes (0 for an unsupported shape).
+ */
+int cgcn_hicloops_band(cgcn_stream_t stream, int n, const int32_t *rowptr, const int32_t *col, const double *val, int width,
+                       double *band);
+
+int cgcn_hicloops_pass1(cgcn_stream_t stream, int n, int D, int width, const double *band, const double *vc, const double *norm,
+                        long long n_norm, const double *expected, long long n_expected, int p, int w, int ignore_diags,
+                        int min_dist, const double *bounds, int n_chunks, int W, int32_t *hist, uint32_t *flags,
+                        double *lambda_out);
+
+size_t cgcn_hicloops_workspace_bytes(int n, int D);
+
+int cgcn_hicloops_count(cgcn_stream_t stream, int n, int D, int width, const double *band, const uint32_t *flags,
+                        const int32_t *thr, int n_chunks, int W, void *workspace, size_t workspace_bytes, long long *total);
+
+int cgcn_hicloops_write(cgcn_stream_t stream, int n, int D, int width, const double *band, const double *vc, const double *norm,
+                        long long n_norm, const double *expected, long long n_expected, int p, int w, int ignore_diags,
+                        const uint32_t *flags, const int32_t *thr, int n_chunks, int W, long long capacity, void *workspace,
+                        size_t workspace_bytes, int32_t *pix_ij, double *pix_val);
+
 #ifdef __cplusplus
 }
 #endif
