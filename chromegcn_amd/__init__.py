@@ -26,6 +26,9 @@ from .insulation import (Insulation, diamond_sums, diamond_sums_host, domain_edg
 from .loops import (Loops, chunk_boundaries, enriched_pixels, enriched_pixels_host, loop_band, loop_edge_share,  # noqa: F401
                     loop_histograms, loop_histograms_host, loop_lambdas_host, loop_thresholds, loops_from_pixels, loops_host,
                     loops_of_matrix, neighbourhood_offsets, same_loop_host)
+from .pileup import (Pileup, PileupRule, apa_scores, centres_of_graph, distance_groups, pileup_host,  # noqa: F401
+                     pileup_of_matrix, pileup_rule, pileup_sums, pileup_sums_host, quantile_groups, shifted_centres,
+                     value_band, value_band_host)
 from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
 from .nullgraph import (NullGraphTest, null_chrom_graph, null_graph, null_graph_host, null_graph_test,  # noqa: F401
                         null_statistics)
@@ -57,4 +60,6 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "compartment_edge_share", "compartment_metrics", "label_density", "Loops", "neighbourhood_offsets",
            "chunk_boundaries", "loop_thresholds", "loops_from_pixels", "loop_lambdas_host", "loop_histograms_host",
            "enriched_pixels_host", "loops_host", "loop_band", "loop_histograms", "enriched_pixels", "loops_of_matrix",
-           "same_loop_host", "loop_edge_share"]
+           "same_loop_host", "loop_edge_share", "Pileup", "PileupRule", "pileup_rule", "apa_scores", "value_band_host",
+           "pileup_sums_host", "pileup_host", "value_band", "pileup_sums", "pileup_of_matrix", "centres_of_graph",
+           "shifted_centres", "distance_groups", "quantile_groups"]

@@ -171,6 +171,11 @@ _HEADER = {
     "cgcn_hicloops_count": (_c_int, "stream n:i D:i width:i band flags thr n_chunks:i W:i workspace workspace_bytes:z total"),
     "cgcn_hicloops_write": (_c_int, "stream n:i D:i width:i band vc norm n_norm:ll expected n_expected:ll p:i w:i ignore_diags:i "
                                     "flags thr n_chunks:i W:i capacity:ll workspace workspace_bytes:z pix_ij pix_val"),
+    "cgcn_pileup_values": (_c_int, "stream n:i width:i band vc norm n_norm:ll expected n_expected:ll kind:i vband"),
+    "cgcn_pileup_workspace_bytes": (_c_sz, "n_slices:ll w:i"),
+    "cgcn_pileup_slices": (_c_int, "stream n:i width:i vband w:i n_slices:ll slice_off n_centres:ll ci cj workspace "
+                                   "workspace_bytes:z"),
+    "cgcn_pileup_fold": (_c_int, "stream n_groups:i w:i n_slices:ll group_off workspace workspace_bytes:z P N"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -62,7 +62,10 @@ HicContacts.loops' keywords (plus pad_bins) computed from the records: a record 
 (pos1 // res, pos2 // res), lower bin first and res the loops' resolution, lies within Chebyshev distance pad_bins (default 1)
 of some loop's peak.  The test is on the SOURCE record; named norms, expected = "auto" and a dict of loops are still computed
 from ALL records; the kept records stay in file order; with domains both tests must hold.  loops = None is the rule above, bit
-for bit."""
+for bit.
+
+Pile-ups (chromegcn_amd/pileup.py holds the rule).  HicContacts.pileup sums the map in a window around
+every centre of a list (loops, graph edges, their shifted controls), per group; it reads the records and changes no graph."""
 from __future__ import annotations
 
 from typing import Dict, NamedTuple, Optional
@@ -79,6 +82,7 @@ from .compartments import (Compartments, compartment_edge_share, compartment_met
 from .hiccache import (HostContacts, contact_cache_path, load_contacts_cache, load_contacts_text,  # noqa: F401
                        save_contacts_cache, windows_from_bed)
 from .loops import Loops, loop_edge_share, loops_host, loops_of_matrix, same_loop_host  # noqa: F401
+from .pileup import Pileup, apa_scores, centres_of_graph, pileup_host, pileup_of_matrix, shifted_centres  # noqa: F401
 from .hictext import TEXT_LINE_MAX, TEXT_MALFORMED, TEXT_SLOW, parse_contacts_text, parse_contacts_text_host  # noqa: F401
 
 
@@ -331,6 +335,8 @@ class HicContacts:
         self._within = []          # (domain_of_bin, domain_bp, the HicContacts of the kept records): the last few selections
         self._loops = {}           # loops' argument tuple -> loops.Loops
         self._within_loops = []    # (Loops, pad_bins, the HicContacts of the kept records): the last few selections
+        self._pileup_bands = {}    # (resolution_bp, n_bins, width) -> the raw band of pileup()
+        self._pileup_values = {}   # pileup's norm, band and value tuple -> the value band
         self.text_info = None   # from_text: {n_bytes, slow_lines, parse_calls}
 
     @classmethod
@@ -590,6 +596,43 @@ class HicContacts:
             self._loops[key] = out
         return out
 
+    def pileup(self, centres, group=None, n_groups=None, norm="VC", resolution_bp=10000, expected="auto", value="oe", w=None,
+               corner=None, min_dist=None, max_distance_bp=2_000_000, n_bins=None, norm_args=None, expected_args=None):
+        """The pile-up of the map around `centres` (chromegcn_amd/pileup.py's rule): a Loops (its peaks), a pair of integer
+        arrays or a pair of device tensors, in bins of resolution_bp; group: a group id per centre (None: one group), n_groups
+        its range (None: the largest id + 1, one read-back for a device tensor).  norm, expected: loops()'s; expected is read
+        for value = "oe" alone.  The raw band and the value band are kept per argument tuple for None and the three names with
+        expected = "auto", so that loops, graph edges and their controls on one map share them."""
+        from . import loops as LP, pileup as PU
+        res = int(resolution_bp)
+        G = PU._n_groups(group, n_groups)
+        rule = dict(value=value, w=w, corner=corner, min_dist=min_dist, max_distance_bp=max_distance_bp)
+        PU.pileup_rule(res, 0, G, **rule)
+        ci, cj = PU._centres_of(centres)
+        if not torch.is_tensor(ci):
+            PU._centre_arrays(ci, cj, None if torch.is_tensor(group) else group)
+        if isinstance(expected, str) and expected != "auto":
+            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
+        a = self.contact_matrix(res, n_bins)
+        r = PU.pileup_rule(res, a.n, G, **rule)   # the size guard, before anything is allocated
+        bkey = (res, a.n, r.width)
+        if bkey not in self._pileup_bands:
+            self._pileup_bands[bkey] = LP.loop_band(a, r.width)
+        nk = self._norm_key(norm, norm_args) if (isinstance(expected, str) or r.value != "oe") else None
+        key = None if nk is None else nk + bkey + (r.value,) + (tuple(sorted((expected_args or {}).items())) if r.value == "oe"
+                                                                 else ())
+        vb = None if key is None else self._pileup_values.get(key)
+        if vb is None:
+            ex = None
+            if r.value == "oe":
+                ex = (self.expected_vector(norm, res, n_bins=a.n, norm_args=norm_args, **(expected_args or {}))
+                      if isinstance(expected, str) else self._norm(expected))
+            nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+            vb = PU.value_band(self._pileup_bands[bkey], a.vc, nv, ex, r)
+            if key is not None:
+                self._pileup_values[key] = vb
+        return PU.pileup_sums(vb, ci, cj, group, G, r)
+
     def within_loops(self, loops, pad_bins=1) -> "HicContacts":
         """the records whose pixel lies in some loop's footprint (loops.py's rule 12), in file order, as a HicContacts of their
         own: a sorted int64 key table, torch.searchsorted, boolean indexing -- one host sync for the size"""
@@ -807,7 +850,8 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                                expected_args=None, null=None, domains=None,
                                domain_report: Optional[dict] = None, compartments: Optional[dict] = None,
                                compartment_report: Optional[dict] = None, loops: Optional[dict] = None,
-                               loop_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
+                               loop_report: Optional[dict] = None, apa: Optional[dict] = None,
+                               apa_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
@@ -827,7 +871,10 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
     compartment_of_windows, compartments.compartment_edge_share of the graph that is returned)}.  loops (`-hic_loops`): a dict
     of HicContacts.loops' keywords plus `pad_bins` and `restrict` (`-hic_loop_restrict`: every graph is built from the records
     inside the footprints of the loops called from its cache's records; with `domains` both tests hold).  loop_report: a dict
-    that receives {chrom: (Loops, entries in a footprint, nnz)} of the UNRESTRICTED top-K matrix (loops.loop_edge_share)."""
+    that receives {chrom: (Loops, entries in a footprint, nnz)} of the UNRESTRICTED top-K matrix (loops.loop_edge_share).
+    apa (`-hic_apa`): a dict of HicContacts.pileup's keywords; apa_report: a dict that receives {chrom: {"edges", "control"[,
+    "loops"]: Pileup}}: the pile-up around the edges of the UNRESTRICTED top-K matrix (pileup.centres_of_graph), around the
+    same edges shifted by 3 w bins along the diagonal and, with `loops`, around the loops.  No graph depends on it."""
     from . import hicnorm as HN
     from . import nullgraph
     out = {}
@@ -886,6 +933,20 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                                               expected=ex, expected_args=expected_args, **up)
                 loop_report[chrom] = (called,) + loop_edge_share((rp, ci_), called, c.window_start, pad)
             found = (called, pad) if restrict else None
+        if apa is not None:
+            from . import pileup as PU
+            kw = dict(apa)
+            if not isinstance(rec[0], HicContacts):
+                rec = (HicContacts(c.pos1, c.pos2, c.count, device), None, None)
+            rp, ci_, _ = rec[0].build_raw(norm, c.resolution_bp, c.window_start, int(hicsize), min_distance_bp=min_distance_bp,
+                                          expected=ex, expected_args=expected_args, **up)
+            ei, ej, _ = PU.centres_of_graph((rp, ci_), c.window_start, kw.get("resolution_bp", 10000))
+            w = PU.pileup_rule(kw.get("resolution_bp", 10000), **{k: v for k, v in kw.items() if k in PU._RULE}).w
+            piles = {"edges": rec[0].pileup((ei, ej), **kw), "control": rec[0].pileup(PU.shifted_centres(ei, ej, 3 * w), **kw)}
+            if loops is not None:
+                piles["loops"] = rec[0].pileup(called, **kw)
+            if apa_report is not None:
+                apa_report[chrom] = piles
         out[chrom] = build_hic_graph(*rec, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device,
                                      min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args,

@@ -16,7 +16,9 @@ compartments from its cache's records (chromegcn_amd/compartments.py), oriented 
 iteration's record and the AA / BB / AB share of the graph the run trains on, and after the last epoch the test metrics in A and in B;
 `-hic_compartment_restrict` trains on the graphs of the contacts within one compartment.  `-hic_loops RES_BP` (with `-hic_contacts`) calls
 every chromosome's chromatin loops from its cache's records (chromegcn_amd/loops.py) and prints the loop count and the share of the
-unrestricted graph inside loop footprints; `-hic_loop_restrict` trains on the graphs of the contacts inside the footprints."""
+unrestricted graph inside loop footprints; `-hic_loop_restrict` trains on the graphs of the contacts inside the footprints.
+`-hic_apa W` (with `-hic_contacts`) prints the aggregate peak analysis (chromegcn_amd/pileup.py) of the unrestricted graph's edges,
+of their shifted control and, with `-hic_loops`, of the loops; it changes no graph."""
 from __future__ import annotations
 
 import argparse
@@ -76,6 +78,11 @@ def parse(argv=None):
     ap.add_argument("-hic_loop_pad", type=int, default=1, metavar="BINS", help="-hic_loops: a footprint reaches this far around a peak")
     ap.add_argument("-hic_loop_restrict", action="store_true",
                     help="-hic_loops: build every graph from the contacts inside loop footprints")
+    ap.add_argument("-hic_apa", type=int, default=0, metavar="W",
+                    help="-hic_contacts: pile the observed / expected map up in a (2 W + 1)^2 window (chromegcn_amd.pileup) around the "
+                         "edges of every chromosome's unrestricted graph, around the same edges shifted by 3 W bins and, with "
+                         "-hic_loops, around the loops; prints P2LL, P2M and ZscoreLL of each.  0: off")
+    ap.add_argument("-hic_apa_res", type=int, default=10000, metavar="BP", help="-hic_apa: the bin size of the piled-up map")
     ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
                     help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
                          "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
@@ -108,7 +115,24 @@ def parse(argv=None):
     ap.add_argument("-summarize_data", action="store_true",     # config_args.py:35
                     help="print labels per window and windows per label (mean, median, max) of train + valid before the "
                          "first epoch (utils/util_methods.py:64-74; chromegcn_amd.labelstats)")
-    return ap.parse_args(argv)
+    opt = ap.parse_args(argv)
+    if opt.hic_apa:
+        if not opt.hic_contacts:
+            ap.error("-hic_apa needs -hic_contacts: the pile-up reads the contact records")
+        if not 1 <= opt.hic_apa <= 10:
+            ap.error("-hic_apa: the window half-width is 1 to 10 bins")
+        if opt.hic_apa_res < 1:
+            ap.error("-hic_apa_res must be positive")
+    return opt
+
+
+def report_apa(split, report, out=None):
+    """-hic_apa: P2LL, P2M and ZscoreLL per chromosome and centre set of graphs_from_contact_caches' apa_report"""
+    for c, piles in report.items():
+        for name, p in piles.items():
+            s = p.scores()
+            print("[hic_apa] %s %s %s: %d centres kept (%d skipped), P2LL %.4g, P2M %.4g, ZscoreLL %.4g"
+                  % (split, c, name, int(p.kept[0]), sum(p.skipped.values()), s["P2LL"][0], s["P2M"][0], s["ZscoreLL"][0]), file=out)
 
 
 def summarize_data(data, dev, out=None):
@@ -189,6 +213,9 @@ def _load_inputs(opt):
             if getattr(opt, "hic_loops", 0):
                 loops = dict(resolution_bp=opt.hic_loops, norm=None if opt.hic_loop_norm == "NONE" else opt.hic_loop_norm,
                              fdr=opt.hic_loop_fdr, pad_bins=opt.hic_loop_pad, restrict=bool(opt.hic_loop_restrict))
+            apa = {}
+            if getattr(opt, "hic_apa", 0):
+                apa = dict(apa=dict(w=opt.hic_apa, resolution_bp=opt.hic_apa_res), apa_report={})
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
@@ -200,8 +227,9 @@ def _load_inputs(opt):
                                                               if getattr(opt, "hic_null", None) else None),
                                                         domains=domains, domain_report=report,
                                                         compartments=comps, compartment_report=comp_report,
-                                                        loops=loops, loop_report=loop_report)
+                                                        loops=loops, loop_report=loop_report, **apa)
             report_compartments(opt, sp, comp_report)
+            report_apa(sp, apa.get("apa_report", {}))
             for c, (called, inside, nnz) in loop_report.items():
                 print("[hic_loops] %s %s: %d loops from %d candidates (%d enriched pixels, %d after the ratios); %d of %d entries of the "
                       "unrestricted graph inside a footprint (%.1f %%)"

@@ -1376,6 +1376,49 @@ int cgcn_hicloops_write(cgcn_stream_t stream, int n, int D, int width, const dou
                         const uint32_t *flags, const int32_t *thr, int n_chunks, int W, long long capacity, void *workspace,
                         size_t workspace_bytes, int32_t *pix_ij, double *pix_val);
 
+/* ---- Pile-ups: aggregate peak analysis of a list of pixel centres (chromegcn_amd/pileup.py holds the rule; DESIGN.md
+ * section 4.20).  These four functions are additions to ABI 26 like the functions above: CGCN_ABI_VERSION stays 26, nothing
+ * above changes.
+ *
+ * band fp64 [n][width] is cgcn_hicloops_band's raw band; vc, norm, n_norm and expected, n_expected are read as the loop
+ * functions read them (a bin is valid iff vc > 0 and its norm value is finite, not NaN and not 0; expected reads as 0 beyond
+ * its length).  w <= 10 is the window half-width, S = 2 w + 1; n width must not exceed 2^28; at most 65 536 groups and 2^24
+ * slices.  CGCN_ERR_UNSUPPORTED beyond these limits.
+ *
+ * cgcn_pileup_values: the value band vband fp64 [n][width], every entry written: for the cell (a, a + dd) the value
+ *   A (CGCN_PILEUP_OBSERVED), A / (nv[a] * nv[b]) (CGCN_PILEUP_BALANCED) or (A / (nv[a] * nv[b])) / expected[dd]
+ *   (CGCN_PILEUP_OE), in exactly this order; a quiet NaN where a + dd >= n, a bin is not valid, the value is not finite or,
+ *   for CGCN_PILEUP_OE, expected[dd] is not > 0.  expected may be NULL for the other two kinds.
+ * cgcn_pileup_slices: slice s holds the centres slice_off[s] .. slice_off[s + 1] - 1 (int32 [n_slices + 1], device; at most
+ *   256 of them, clipped to that and to n_centres) of ci, cj (int32 [n_centres], device; i < j).  Per slice and offset
+ *   (da, db), row-major with da = -w .. w, then db = -w .. w: ONE sequential fp64 sum, from 0.0 and in centre order, of
+ *   vband at the cell (i + da, j + db) where that is not NaN, and the int32 count of those cells; both are left in the
+ *   workspace for cgcn_pileup_fold.  A centre with i < w, j + w > n - 1, j - i < 2 w or j - i + 2 w >= width adds nothing.
+ * cgcn_pileup_fold: the slices group_off[g] .. group_off[g + 1] - 1 (int32 [n_groups + 1], device) belong to group g:
+ *   P fp64 [n_groups][S][S] is ONE sequential fp64 sum, from 0.0 and in slice order, of the slice sums; N int64
+ *   [n_groups][S][S] the sum of the counts.  Every entry is written; a group without slices gets zeros.  The workspace,
+ *   n_slices and w are those of cgcn_pileup_slices.
+ *
+ * No atomics and a fixed order: the same bits in every run.  Enqueue only: no allocation, no synchronisation.
+ * CGCN_ERR_BAD_ARG: a NULL pointer that would be read or written, a negative size, w < 1, width < 1, an unknown kind, norm
+ * with n_norm < 1; CGCN_ERR_WORKSPACE: workspace_bytes below cgcn_pileup_workspace_bytes (0 for an unsupported shape).
+ */
+#define CGCN_PILEUP_OBSERVED 0
+#define CGCN_PILEUP_BALANCED 1
+#define CGCN_PILEUP_OE 2
+
+int cgcn_pileup_values(cgcn_stream_t stream, int n, int width, const double *band, const double *vc, const double *norm,
+                       long long n_norm, const double *expected, long long n_expected, int kind, double *vband);
+
+size_t cgcn_pileup_workspace_bytes(long long n_slices, int w);
+
+int cgcn_pileup_slices(cgcn_stream_t stream, int n, int width, const double *vband, int w, long long n_slices,
+                       const int32_t *slice_off, long long n_centres, const int32_t *ci, const int32_t *cj, void *workspace,
+                       size_t workspace_bytes);
+
+int cgcn_pileup_fold(cgcn_stream_t stream, int n_groups, int w, long long n_slices, const int32_t *group_off,
+                     const void *workspace, size_t workspace_bytes, double *P, long long *N);
+
 #ifdef __cplusplus
 }
 #endif
