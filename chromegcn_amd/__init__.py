@@ -21,9 +21,10 @@ from .hicnorm import (HicNormError, contact_matrix_host, hic_norm_vector, hic_no
                       kr_balance_host)
 from .hicdist import (distance_sums_device_order_host, distance_sums_host, expected_from_sums, expected_vector_host,  # noqa: F401
                       hic_expected_vector)
+from .hicmap import device_band  # noqa: F401
 from .insulation import (Insulation, diamond_sums, diamond_sums_host, domain_edge_share, domain_of_windows,  # noqa: F401
                          insulation_from_sums, insulation_host)
-from .loops import (Loops, chunk_boundaries, enriched_pixels, enriched_pixels_host, loop_band, loop_edge_share,  # noqa: F401
+from .loops import (Loops, chunk_boundaries, enriched_pixels, enriched_pixels_host, loop_edge_share,  # noqa: F401
                     loop_histograms, loop_histograms_host, loop_lambdas_host, loop_thresholds, loops_from_pixels, loops_host,
                     loops_of_matrix, neighbourhood_offsets, same_loop_host)
 from .pileup import (Pileup, PileupRule, apa_scores, centres_of_graph, distance_groups, pileup_host,  # noqa: F401
@@ -59,7 +60,7 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "domain_edge_share", "domain_of_windows", "Compartments", "compartments_host", "compartments_of_matrix",
            "compartment_edge_share", "compartment_metrics", "label_density", "Loops", "neighbourhood_offsets",
            "chunk_boundaries", "loop_thresholds", "loops_from_pixels", "loop_lambdas_host", "loop_histograms_host",
-           "enriched_pixels_host", "loops_host", "loop_band", "loop_histograms", "enriched_pixels", "loops_of_matrix",
+           "enriched_pixels_host", "loops_host", "device_band", "loop_histograms", "enriched_pixels", "loops_of_matrix",
            "same_loop_host", "loop_edge_share", "Pileup", "PileupRule", "pileup_rule", "apa_scores", "value_band_host",
            "pileup_sums_host", "pileup_host", "value_band", "pileup_sums", "pileup_of_matrix", "centres_of_graph",
            "shifted_centres", "distance_groups", "quantile_groups"]

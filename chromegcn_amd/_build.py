@@ -26,7 +26,7 @@ SRC = [os.path.join(PKG, "csrc", "cgcn_kernels.hip"), os.path.join(PKG, "csrc", 
        os.path.join(PKG, "csrc", "cgcn_insulation.hip"), os.path.join(PKG, "csrc", "cgcn_compartment.hip"),
        os.path.join(PKG, "csrc", "cgcn_loops.hip"), os.path.join(PKG, "csrc", "cgcn_pileup.hip")]
 HDR = [os.path.join(ROOT, "include", "chromegcn.h"), os.path.join(PKG, "csrc", "cgcn_common.hpp"),
-       os.path.join(PKG, "csrc", "cgcn_compact.hpp")]
+       os.path.join(PKG, "csrc", "cgcn_compact.hpp"), os.path.join(PKG, "csrc", "cgcn_hicmap.hpp")]
 LIB = os.path.join(PKG, "libchromegcn_hip.so")
 HASH = LIB + ".srchash"
 # what the compiler reports for every kernel of the build (registers, spills, scratch, LDS, occupancy), written next to the

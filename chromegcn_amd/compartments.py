@@ -6,9 +6,9 @@ host numpy shared by the device path and the restatement.
 
 The rule, per chromosome.  res = resolution_bp (default 100 000); A = hicnorm's contact matrix at res (n bins, symmetric, fp64).
   1. Matrix and balancing.  B[a, b] = A[a, b] / (nv[a] * nv[b]), one float64 multiplication and one float64 division, exactly
-     insulation's rule 1; nv = insulation.clean_norm(norm).  With norm = None, B = A.  norm: None, a vector, or 'KR' / 'VC' /
+     insulation's rule 1; nv = hicnorm.clean_norm(norm).  With norm = None, B = A.  norm: None, a vector, or 'KR' / 'VC' /
      'SQRTVC' (computed from the records); the default is 'VC', which cannot fail to converge.
-  2. Kept bins.  valid = insulation.valid_bins(VC, norm), VC the matrix's row sums; keep = the valid bins ascending,
+  2. Kept bins.  valid = hicmap.valid_bins(VC, norm), VC the matrix's row sums; keep = the valid bins ascending,
      m = len(keep); everything dense is m x m over keep.  m > 8192 is a ValueError that names a coarser resolution (two m^2
      float64 arrays are allocated); m < 3 gives an all-NaN result with converged = False.
   3. Expected by distance.  For d = keep[j] - keep[i] >= 0 (i <= j): dsum[d] = sum of B[keep[i], keep[j]], cnt[d] = the number
@@ -45,7 +45,7 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import hicnorm, insulation
+from . import hicmap, hicnorm
 
 MAX_KEPT = 8192
 RESOLUTION_BP, IGNORE_DIAGS, TOL, MAX_ITER, CHECK_EVERY, MAX_EIGS = 100000, 2, 1e-10, 1000, 4, 3
@@ -222,7 +222,7 @@ def balanced_dense_host(A, norm, keep) -> np.ndarray:
     keep = np.asarray(keep, dtype=np.int64)
     B = A[keep][:, keep].toarray()
     if norm is not None:
-        nv = insulation.clean_norm(norm, A.shape[0])[keep]
+        nv = hicnorm.clean_norm(norm, A.shape[0])[keep]
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             B = B / (nv[:, None] * nv[None, :])
     return B
@@ -312,12 +312,9 @@ def compartments_host(pos1, pos2, count, norm="VC", resolution_bp=RESOLUTION_BP,
                       orient=None, tol=TOL, max_iter=MAX_ITER, norm_args=None) -> Compartments:
     """The whole rule in numpy, with the same iteration and start vector as the device path (not eigh)."""
     rule = _rule(dict(n_eigs=n_eigs, ignore_diags=ignore_diags, tol=tol, max_iter=max_iter))
-    A = hicnorm.contact_matrix_host(pos1, pos2, count, resolution_bp, n_bins)
-    if isinstance(norm, str):
-        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, n_bins, **(norm_args or {}))
-        hicnorm._require_converged(info)
+    A, vc, norm, _ = hicmap.resolve_host(pos1, pos2, count, norm, resolution_bp, n_bins, norm_args)
     n = A.shape[0]
-    valid = insulation.valid_bins(np.asarray(A.sum(axis=1)).ravel(), norm)
+    valid = hicmap.valid_bins(vc, norm)
     keep, _ = kept_bins(valid, resolution_bp)
     cnt = pair_counts(valid)
     if keep.size < 3:
@@ -358,9 +355,7 @@ def balanced_dense(A: hicnorm.DeviceContactMatrix, norm, keep) -> torch.Tensor:
     m = int(keep.size)
     if m > MAX_KEPT or (m and (keep[0] < 0 or keep[-1] >= A.n or np.any(np.diff(keep) <= 0))):
         raise ValueError("keep must be at most %d strictly ascending bins of the matrix" % MAX_KEPT)
-    if norm is not None and not (torch.is_tensor(norm) and norm.device == dev and norm.dtype == torch.float64
-                                 and norm.is_contiguous() and norm.numel() > 0):
-        raise ValueError("norm must be a non-empty contiguous float64 vector on the matrix's device")
+    hicmap.device_vector(norm, dev, "norm", optional=True)
     rank = np.full(A.n, -1, np.int32)
     rank[keep] = np.arange(m, dtype=np.int32)
     B = torch.zeros(m, _ld(m), dtype=torch.float64, device=dev)
@@ -465,7 +460,7 @@ def compartments_of_matrix(A: hicnorm.DeviceContactMatrix, norm, resolution_bp=R
     distance sums, the m row sums of squares, three doubles every check_every steps, the vectors."""
     rule = _rule(rule)
     nv = None if norm is None else norm.cpu().numpy()
-    valid = insulation.valid_bins(A.vc.cpu().numpy(), nv)
+    valid = hicmap.valid_bins(A.vc.cpu().numpy(), nv)
     keep, _ = kept_bins(valid, resolution_bp)
     if keep.size < 3:
         return _no_result(A.n, keep, np.zeros(A.n), rule["n_eigs"], 1, resolution_bp)
@@ -483,13 +478,11 @@ def compartments_of_matrix(A: hicnorm.DeviceContactMatrix, norm, resolution_bp=R
 # graphs and metrics by compartment
 # ----------------------------------------------------------------------------------------------
 def compartment_edge_share(graph_or_csr, comp_of_window) -> dict:
-    """{"AA", "BB", "AB", "uncalled", "nnz"} as exact integers: the stored entries of a graph (insulation.domain_edge_share's
+    """{"AA", "BB", "AB", "uncalled", "nnz"} as exact integers: the stored entries of a graph (hicmap.csr_of's
     inputs) by the calls of their two windows (+1 A, -1 B, 0 none; an entry with an end without a call is "uncalled")"""
-    rowptr, col, nnz = insulation.csr_of(graph_or_csr)
     comp = np.asarray(comp_of_window, dtype=np.int64).ravel()
-    if comp.size != rowptr.size - 1:
-        raise ValueError("the graph has %d windows but comp_of_window has %d" % (rowptr.size - 1, comp.size))
-    a, b = comp[np.repeat(np.arange(comp.size), np.diff(rowptr))], comp[col]
+    row, col, nnz = hicmap.edge_rows(graph_or_csr, comp.size, "comp_of_window")
+    a, b = comp[row], comp[col]
     return {"AA": int(np.sum((a > 0) & (b > 0))), "BB": int(np.sum((a < 0) & (b < 0))), "AB": int(np.sum(a * b < 0)),
             "uncalled": int(np.sum(a * b == 0)), "nnz": nnz}
 

@@ -151,6 +151,28 @@ __device__ __forceinline__ float wave_sum(float v) {
   return rl_f(v, 63);
 }
 
+// The fp64 sum over the 64 lanes: the xor butterfly over 32, 16, ..., 1, one plain IEEE add per step (a lone add cannot
+// contract).  Each step adds the same two values on both sides, so every lane ends with the same bits.
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = WAVE / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// ... over the NW wavefronts of a workgroup, the same value in every thread: a butterfly per wavefront, then the wavefronts'
+// sums in ascending order.  All threads call it; `sh` holds one double per wavefront and is free again after the call's
+// first barrier, so consecutive calls may share it as long as nothing else touches it in between.
+template <int NW>
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x / WAVE] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) t += sh[w];
+  return t;
+}
+
 // Sum over each 32-lane half of the wave, the half's total in every lane of the half (all lanes active).
 __device__ __forceinline__ float half_sum(float v, bool upper) {
   v += dpp_get<0xB1, 0xF>(v);    // quad_perm [1,0,3,2]

@@ -24,7 +24,7 @@
 // No floating-point atomic, no split K, no order that scheduling could change: the same bits in every run.  The sums that the
 // numpy restatement mirrors term by term (dist, mean, ss) use __dadd_rn / __dmul_rn so that nothing is contracted.  Nothing
 // is allocated, nothing synchronises.
-#include "cgcn_common.hpp"
+#include "cgcn_hicmap.hpp"
 
 #define CMP_THREADS 256
 #define CMP_WAVES (CMP_THREADS / WAVE)
@@ -38,18 +38,6 @@
 
 typedef double cmp_d4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double cmp_norm_at(const double* __restrict__ norm, long long n_norm, int b) {
-  if (b >= n_norm) return __longlong_as_double(0x7FF0000000000000ll);
-  const double x = norm[b];
-  return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
-}
-
-__device__ __forceinline__ double cmp_wave_sum(double v) {
-#pragma unroll
-  for (int o = WAVE / 2; o >= 1; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o));
-  return v;
-}
-
 __global__ __launch_bounds__(CMP_THREADS) void k_comp_dense(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
                                                             const double* __restrict__ val, const double* __restrict__ norm,
                                                             long long n_norm, const int* __restrict__ rank, int m, int ld,
@@ -59,7 +47,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_comp_dense(int n, const int* __
   for (long long bin = (long long)blockIdx.x * CMP_WAVES + threadIdx.x / WAVE; bin < n; bin += waves) {
     const int ra = rank[bin];
     if (ra < 0 || ra >= m) continue;   // the whole wavefront
-    const double na = norm ? cmp_norm_at(norm, n_norm, (int)bin) : 1.0;
+    const double na = norm ? hm_norm_at(norm, n_norm, bin) : 1.0;
     const int end = rowptr[bin + 1];
     for (int p = rowptr[bin] + lane; p < end; p += WAVE) {
       const int c = col[p];
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_comp_dense(int n, const int* __
       const int rc = rank[c];
       if (rc < 0 || rc >= m) continue;
       double v = val[p];
-      if (norm) v = v / (na * cmp_norm_at(norm, n_norm, c));   // one multiply, one divide
+      if (norm) v = v / (na * hm_norm_at(norm, n_norm, c));   // one multiply, one divide
       B[(long long)ra * ld + rc] = v;
     }
   }
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_comp_dist(int n, int m, int ld,
       if (r < 0 || r >= m) continue;
       acc = __dadd_rn(acc, B[(long long)i * ld + r]);
     }
-    acc = cmp_wave_sum(acc);
+    acc = wave_sum_d(acc);
     if (lane == 0) dsum[d] = acc;
   }
 }
@@ -111,13 +99,13 @@ __global__ __launch_bounds__(CMP_THREADS) void k_comp_oe_stats(int m, int ld, do
       r[j] = v;
       acc = __dadd_rn(acc, v);
     }
-    const double mu = cmp_wave_sum(acc) / (double)m;
+    const double mu = wave_sum_d(acc) / (double)m;
     acc = 0.0;
     for (int j = lane; j < m; j += WAVE) {   // a lane reads back what it wrote itself
       const double t = __dsub_rn(r[j], mu);
       acc = __dadd_rn(acc, __dmul_rn(t, t));
     }
-    acc = cmp_wave_sum(acc);
+    acc = wave_sum_d(acc);
     if (lane == 0) {
       mean[row] = mu;
       ss[row] = acc;
@@ -195,14 +183,16 @@ __global__ __launch_bounds__(CMP_THREADS) void k_comp_matvec(int m, const double
     const double* __restrict__ r = C + row * m;
     double acc = 0.0;
     for (int j = lane; j < m; j += WAVE) acc += r[j] * v[j];
-    acc = cmp_wave_sum(acc);
+    acc = wave_sum_d(acc);
     if (lane == 0) y[row] = acc;
   }
 }
 
-// the sum over the workgroup, the same value in every thread: a butterfly per wavefront, then the wavefronts in order
+// The sum over the workgroup, the same value in every thread: a butterfly per wavefront, then the wavefronts in order.  Not
+// block_sum_d: its barriers stand in front of the write and of the read, none behind the read, and without that one the
+// compiler moves k_comp_finish's next loads up into the sum and takes two more registers.
 __device__ __forceinline__ double cmp_block_sum(double v, double* s) {
-  v = cmp_wave_sum(v);
+  v = wave_sum_d(v);
   if ((threadIdx.x & (WAVE - 1)) == 0) s[threadIdx.x / WAVE] = v;
   __syncthreads();
   double t = 0.0;

@@ -24,6 +24,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "cgcn_compact.hpp"
+#include "cgcn_hicmap.hpp"
 
 #define HIC_THREADS 256
 #define HIC_STEPS 8                                    // records per lane of the filter pass
@@ -52,10 +53,7 @@ __device__ __forceinline__ u64 hic_value_key(double v) {
 // nv[] of get_normalization_values (:62-63): NaN and 0 become +inf.  A bin outside the vector (the reference raises
 // IndexError) reads as +inf too: never out of bounds.
 __device__ __forceinline__ double hic_norm_at(const double* __restrict__ norm, long long n_bins, int pos, int res) {
-  const long long b = pos / res;
-  if (b < 0 || b >= n_bins) return __longlong_as_double(0x7FF0000000000000ll);
-  const double x = norm[b];
-  return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
+  return hm_norm_at(norm, n_bins, pos / res);
 }
 
 // Distance-aware variants (DIST = true in the filter passes below): a record takes part only if
@@ -71,9 +69,9 @@ __device__ __forceinline__ long long hic_floor_bin(int pos, int res) {   // nump
 }
 __device__ __forceinline__ double hic_expected_at(const double* __restrict__ ex, long long n_ex, int p1, int p2, int res) {
   const long long g = hic_floor_bin(p1, res) - hic_floor_bin(p2, res), d = g < 0 ? -g : g;
-  if (d >= n_ex) return __longlong_as_double(0x7FF0000000000000ll);
+  if (d >= n_ex) return hm_inf();
   const double x = ex[d];
-  return x > 0.0 ? x : __longlong_as_double(0x7FF0000000000000ll);
+  return x > 0.0 ? x : hm_inf();
 }
 
 // Wave w of a workgroup owns the 512 consecutive records [tile + 512 w, tile + 512 (w + 1)) and walks them in 8 steps of

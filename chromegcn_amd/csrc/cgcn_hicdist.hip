@@ -22,6 +22,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "cgcn_compact.hpp"
+#include "cgcn_hicmap.hpp"
 
 #define HD_THREADS 256
 #define HD_NONE 0xFFFFFFFFu                            // no distance: the lanes behind the last key, a tile without a second partial
@@ -30,12 +31,6 @@ static inline int hd_bits(long long n) {
   int b = 1;
   while (b < 32 && (1ll << b) < n) ++b;
   return b;
-}
-
-__device__ __forceinline__ double hd_norm_at(const double* __restrict__ norm, long long n_norm, long long b) {
-  if (b < 0 || b >= n_norm) return __longlong_as_double(0x7FF0000000000000ll);
-  const double x = norm[b];
-  return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
 }
 
 // sizes[0] |= 1: a count that is negative or not finite; |= 2: a negative position; |= 4: a bin >= n_bins (n_bins > 0).
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_keys(long long M, const int* 
     const int a = pos1[r], c = pos2[r];
     const double v = count[r];
     long long d = n_bins;
-    bad = (v >= 0.0 && v < __longlong_as_double(0x7FF0000000000000ll)) ? 0u : 1u;
+    bad = (v >= 0.0 && v < hm_inf()) ? 0u : 1u;
     if (a < 0 || c < 0) {
       bad |= 2u;
     } else {
@@ -72,17 +67,6 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_keys(long long M, const int* 
     if ((u64)g > __atomic_load_n(&sizes[1], __ATOMIC_RELAXED)) atomicMax(&sizes[1], (u64)g);
   }
   if (bad) atomicOr(&sizes[0], (u64)bad);
-}
-
-__device__ __forceinline__ double hd_shfl_up(double v, int o) {
-  const long long x = __double_as_longlong(v);
-  const int lo = __shfl_up((int)(x & 0xFFFFFFFFll), o), hi = __shfl_up((int)(x >> 32), o);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
-__device__ __forceinline__ double hd_shfl_xor(double v, int o) {
-  const long long x = __double_as_longlong(v);
-  const int lo = __shfl_xor((int)(x & 0xFFFFFFFFll), o), hi = __shfl_xor((int)(x >> 32), o);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
 // tile t = sorted keys [64 t, 64 t + 64).  tile_key[2 t], tile_sum[4 t .. 4 t + 1]: the distance and the (raw, act) sums of
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_tiles(long long M, const u64*
       const long long r = (long long)(key & ((1ull << rb) - 1ull));
       raw = act = count[r];
       if (norm) {
-        const double den = hd_norm_at(norm, n_norm, pos1[r] / res) * hd_norm_at(norm, n_norm, pos2[r] / res);   // positions >= 0
+        const double den = hm_norm_at(norm, n_norm, pos1[r] / res) * hm_norm_at(norm, n_norm, pos2[r] / res);   // positions >= 0
         act = raw / den;   // one multiply, one divide; a NaN or 0 norm bin: the record adds 0
       }
     }
@@ -114,7 +98,7 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_tiles(long long M, const u64*
 #pragma unroll
   for (int o = 1; o < WAVE; o <<= 1) {
     const unsigned ud = (unsigned)__shfl_up((int)d, o);
-    const double ur = hd_shfl_up(raw, o), ua = hd_shfl_up(act, o);
+    const double ur = __shfl_up(raw, o), ua = __shfl_up(act, o);
     if (lane >= o && ud == d) {   // sorted: equal ends mean one run
       raw = ur + raw;
       act = ua + act;
@@ -137,6 +121,15 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_tiles(long long M, const u64*
     raw_out[d] = raw;
     act_out[d] = act;
   }
+}
+
+// The double shuffle in two explicit halves: with HIP's own overload (wave_sum_d) k_hd_fold's two butterflies compile to
+// another block layout, and the one run that timed it had chr21's distance sums at 0.532 ms against 0.519 / 0.520 ms before.
+// One run is not proof, but nothing speaks for the change either: this one kernel keeps the code it had.
+__device__ __forceinline__ double hd_shfl_xor(double v, int o) {
+  const long long x = __double_as_longlong(v);
+  const int lo = __shfl_xor((int)(x & 0xFFFFFFFFll), o), hi = __shfl_xor((int)(x >> 32), o);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
 }
 
 // first index of keys[0..M) whose distance is >= d
@@ -176,7 +169,7 @@ __global__ __launch_bounds__(HD_THREADS) void k_hd_fold(long long M, const u64* 
     }
   }
 #pragma unroll
-  for (int o = WAVE / 2; o >= 1; o >>= 1) {
+  for (int o = WAVE / 2; o >= 1; o >>= 1) {   // the two butterflies step by step: their shuffles share one wait
     raw += hd_shfl_xor(raw, o);
     act += hd_shfl_xor(act, o);
   }

@@ -24,6 +24,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "cgcn_compact.hpp"
+#include "cgcn_hicmap.hpp"
 
 #define HN_THREADS 256
 #define HN_ROWS 16                  // rows per workgroup of the product
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_keys(long long M, const int* 
   if (r < M) {
     const int a = pos1[r], c = pos2[r];
     const double v = count[r];
-    bad = (v >= 0.0 && v < __longlong_as_double(0x7FF0000000000000ll)) ? 0u : 1u;
+    bad = (v >= 0.0 && v < hm_inf()) ? 0u : 1u;
     if (a < 0 || c < 0) {
       bad |= 2u;
     } else {
@@ -215,8 +216,6 @@ enum { OP_MASK = 0, OP_RES, OP_FIRST, OP_DIR, OP_W, OP_Y, OP_CLIP, OP_COUNT };
 // the record: 0 rho1, 1 rho2, 2 p.w, 3 min ynew, 4 max ynew, 5 gamma (lower bound), 6 gamma (upper bound), 7 rho1 of the
 // accepted step, 8 rout, 9 alpha, 10 kept rows, 11 non-empty rows
 
-__device__ __forceinline__ double hn_inf() { return __longlong_as_double(0x7FF0000000000000ll); }
-
 __global__ __launch_bounds__(HN_THREADS) void k_hn_vec(int n, int op, int flag, int c, const double* __restrict__ vc,
                                                        const int* __restrict__ row_nnz, double* __restrict__ st, size_t ns) {
   __shared__ double red[HN_NPART][HN_THREADS];
@@ -233,7 +232,7 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_vec(int n, int op, int flag, 
   double* rk2 = vec + (HN_RK0 + (c ^ 1)) * ns;
   double* Z = vec + (HN_Z0 + c) * ns;
   double* Z2 = vec + (HN_Z0 + (c ^ 1)) * ns;
-  double s0 = 0.0, s1 = 0.0, mn0 = hn_inf(), mx0 = -hn_inf(), mn1 = hn_inf(), mn2 = hn_inf();
+  double s0 = 0.0, s1 = 0.0, mn0 = hm_inf(), mx0 = -hm_inf(), mn1 = hm_inf(), mn2 = hm_inf();
   const double beta = op == OP_DIR ? rec[7] / rec[0] : 0.0;
   const double alpha = rec[9];
   const double gamma = op == OP_CLIP ? rec[flag ? 6 : 5] : 0.0;
@@ -325,7 +324,7 @@ __global__ __launch_bounds__(HN_THREADS) void k_hn_finish(int nblk, int op, int 
   __shared__ double red[HN_NPART][HN_THREADS];
   const double* part = st + HN_REC;
   const int t = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0, mn0 = hn_inf(), mx0 = -hn_inf(), mn1 = hn_inf(), mn2 = hn_inf();
+  double s0 = 0.0, s1 = 0.0, mn0 = hm_inf(), mx0 = -hm_inf(), mn1 = hm_inf(), mn2 = hm_inf();
   for (int b = t; b < nblk; b += HN_THREADS) {
     const double* q = part + (size_t)b * HN_NPART;
     s0 += q[0];

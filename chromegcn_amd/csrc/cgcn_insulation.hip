@@ -12,7 +12,7 @@
 // A lane's terms come in (row, column) order and the butterfly is the same in every run: no floating-point atomic, no order
 // that scheduling could change, so the same bits in every run and exact sums for integer counts below 2^53.  No workspace,
 // nothing is allocated, nothing synchronises.
-#include "cgcn_common.hpp"
+#include "cgcn_hicmap.hpp"
 
 #define INS_THREADS 256
 #define INS_MAX_WINDOWS 8
@@ -21,18 +21,6 @@
 struct InsWindows {
   int w[INS_MAX_WINDOWS];   // ascending; 0 behind the last one: no term is that close
 };
-
-__device__ __forceinline__ double ins_norm_at(const double* __restrict__ norm, long long n_norm, int b) {
-  if (b >= n_norm) return __longlong_as_double(0x7FF0000000000000ll);
-  const double x = norm[b];
-  return (x != x || x == 0.0) ? __longlong_as_double(0x7FF0000000000000ll) : x;
-}
-
-__device__ __forceinline__ double ins_shfl_xor(double v, int o) {
-  const long long x = __double_as_longlong(v);
-  const int lo = __shfl_xor((int)(x & 0xFFFFFFFFll), o), hi = __shfl_xor((int)(x >> 32), o);
-  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
-}
 
 __global__ __launch_bounds__(INS_THREADS) void k_insul_sums(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
                                                             const double* __restrict__ val, const double* __restrict__ norm,
@@ -47,18 +35,14 @@ __global__ __launch_bounds__(INS_THREADS) void k_insul_sums(int n, const int* __
     for (int k = 0; k < INS_MAX_WINDOWS; ++k) acc[k] = 0.0;
     for (int a = i - 1 - lane; a >= lo; a -= WAVE) {
       const int end = rowptr[a + 1];
-      int s = rowptr[a], e = end;
-      while (s < e) {   // the first entry of row a with a column >= i
-        const int mid = (int)(((long long)s + e) >> 1);
-        if (col[mid] < i) s = mid + 1; else e = mid;
-      }
-      const double na = norm ? ins_norm_at(norm, n_norm, a) : 1.0;
+      const int s = hm_row_lower(col, rowptr[a], end, i);   // the first entry of row a with a column >= i
+      const double na = norm ? hm_norm_at(norm, n_norm, a) : 1.0;
       const int up = i - a;
       for (int p = s; p < end; ++p) {
         const int c = col[p];
         if (c >= hi) break;
         double v = val[p];
-        if (norm) v = v / (na * ins_norm_at(norm, n_norm, c));   // one multiply, one divide; a NaN or 0 norm bin: the term is 0
+        if (norm) v = v / (na * hm_norm_at(norm, n_norm, c));   // one multiply, one divide; a NaN or 0 norm bin: the term is 0
         const int t = max(up, c - i + 1);
 #pragma unroll
         for (int k = 0; k < INS_MAX_WINDOWS; ++k)
@@ -66,10 +50,7 @@ __global__ __launch_bounds__(INS_THREADS) void k_insul_sums(int n, const int* __
       }
     }
 #pragma unroll
-    for (int k = 0; k < INS_MAX_WINDOWS; ++k) {
-#pragma unroll
-      for (int o = WAVE / 2; o >= 1; o >>= 1) acc[k] += ins_shfl_xor(acc[k], o);
-    }
+    for (int k = 0; k < INS_MAX_WINDOWS; ++k) acc[k] = wave_sum_d(acc[k]);
     if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < INS_MAX_WINDOWS; ++k)

@@ -20,6 +20,7 @@
 // Every floating-point sum is sequential in a fixed order and the only atomics are integer ones: the same bits in every run.
 // An fp64 division is IEEE here; contraction is off, so that no sum is fused with a product.
 #include "cgcn_compact.hpp"
+#include "cgcn_hicmap.hpp"
 
 #pragma clang fp contract(off)
 
@@ -49,14 +50,7 @@ __device__ __forceinline__ bool lp_bin(const double* __restrict__ vc, const doub
                                        long long b, double& nv) {
   nv = 1.0;
   if (b < 0 || b >= n) return false;
-  bool ok = vc[b] > 0.0;
-  if (norm) {
-    if (b >= n_norm) return false;
-    const double x = norm[b];
-    ok = ok && x == x && x != 0.0 && __builtin_fabs(x) != __longlong_as_double(0x7FF0000000000000ll);
-    nv = x;
-  }
-  return ok;
+  return hm_bin(vc, norm, n_norm, b, nv);
 }
 
 // The four sums of one pixel.  cell(da, db, B, E, part): the balanced value (0 where the cell takes no part), the expected
@@ -114,11 +108,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_loops_band(int n, const int* __r
   const long long waves = (long long)gridDim.x * (LP_THREADS / WAVE);
   for (long long row = (long long)blockIdx.x * (LP_THREADS / WAVE) + threadIdx.x / WAVE; row < n; row += waves) {
     const int i = (int)row, end = rowptr[i + 1];
-    int s = rowptr[i], e = end;
-    while (s < e) {   // the first entry of row i with a column >= i
-      const int mid = (int)(((long long)s + e) >> 1);
-      if (col[mid] < i) s = mid + 1; else e = mid;
-    }
+    const int s = hm_row_lower(col, rowptr[i], end, i);   // the first entry of row i with a column >= i
     for (int q = s + lane; q < end; q += WAVE) {
       const long long d = (long long)col[q] - i;
       if (d >= width || col[q] >= n) break;   // the columns ascend: every later entry of this lane is outside too
@@ -191,7 +181,7 @@ __global__ __launch_bounds__(LP_THREADS) void k_loops_pass1(int n, int D, int wi
   const LpCellLds cell = {Bs, Ps, Es, r * lc + c, c, lc};
   const LpAcc acc = lp_sums(cell, p, w);
   const bool cand = active && oka[r] && okb[r + c] && d >= rule.min_dist && lp_enough(acc, rule);
-  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const double nan = hm_nan();
   double lam[4] = {nan, nan, nan, nan};
   int k[4] = {0, 0, 0, 0}, o = 0;
   if (cand) {

@@ -67,12 +67,6 @@ __global__ __launch_bounds__(256) void k_metrics_unpack(long long items, const u
   val[i] = (unsigned char)(k & 1ull);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-  return v;
-}
-
 // Curve points are the ends of runs of equal scores in the descending-sorted list of one label:
 // (tp_k, fp_k), k = 1..K, plus the origin.
 //   AUROC   = sum (fp_k - fp_{k-1}) (tp_k + tp_{k-1}) / 2 / (P N)                       roc_auc_score

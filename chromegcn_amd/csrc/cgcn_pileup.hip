@@ -18,6 +18,7 @@
 // Every floating-point sum is sequential in a fixed order and there are no atomics: the same bits in every run.  Contraction
 // is off, an fp64 division is IEEE here.
 #include "cgcn_compact.hpp"
+#include "cgcn_hicmap.hpp"
 
 #pragma clang fp contract(off)
 
@@ -29,33 +30,19 @@
 #define PU_MAX_GROUPS 65536
 #define PU_VAL_THREADS 256
 
-// validity of bin b < n and its norm value (1.0 without a vector): loops' and insulation's rule
-__device__ __forceinline__ bool pu_bin(const double* __restrict__ vc, const double* __restrict__ norm, long long n_norm, long long b,
-                                       double& nv) {
-  nv = 1.0;
-  bool ok = vc[b] > 0.0;
-  if (norm) {
-    if (b >= n_norm) return false;
-    const double x = norm[b];
-    ok = ok && x == x && x != 0.0 && __builtin_fabs(x) != __longlong_as_double(0x7FF0000000000000ll);
-    nv = x;
-  }
-  return ok;
-}
-
 __global__ __launch_bounds__(PU_VAL_THREADS) void k_pileup_values(int n, int width, const double* __restrict__ band,
                                                                   const double* __restrict__ vc, const double* __restrict__ norm,
                                                                   long long n_norm, const double* __restrict__ ex, long long n_ex,
                                                                   int kind, double* __restrict__ vband) {
-  const double nan = __longlong_as_double(0x7FF8000000000000ll), inf = __longlong_as_double(0x7FF0000000000000ll);
+  const double nan = hm_nan(), inf = hm_inf();
   const long long total = (long long)n * width, step = (long long)gridDim.x * PU_VAL_THREADS;
   for (long long q = (long long)blockIdx.x * PU_VAL_THREADS + threadIdx.x; q < total; q += step) {
     const long long a = q / width, dd = q - a * width, b = a + dd;
     double out = nan;
     if (b < n) {
       double na, nb;
-      bool part = pu_bin(vc, norm, n_norm, a, na);
-      part = pu_bin(vc, norm, n_norm, b, nb) && part;
+      bool part = hm_bin(vc, norm, n_norm, a, na);
+      part = hm_bin(vc, norm, n_norm, b, nb) && part;
       if (part) {
         double v = band[q];
         if (kind >= CGCN_PILEUP_BALANCED) v = v / (na * nb);
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(PU_THREADS) void k_pileup_slices(int n, int width, 
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int2 p = my[c + u];
-      v[u] = p.x >= 0 ? vband[(long long)p.x * width + (p.y - p.x) + shift] : __longlong_as_double(0x7FF8000000000000ll);
+      v[u] = p.x >= 0 ? vband[(long long)p.x * width + (p.y - p.x) + shift] : hm_nan();
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)

@@ -31,25 +31,6 @@
 
 static inline bool ts_misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
-// the same bits in every lane: each butterfly step adds the same two values on both sides
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-// all threads of the workgroup call it; `sh` holds one double per wave and is free again after the call's first barrier
-template <int NW>
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-  v = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x / WAVE] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += sh[w];
-  return t;
-}
-
 // ------------------------------------------------------------------------------------------
 // squared distances
 // ------------------------------------------------------------------------------------------
@@ -121,8 +102,8 @@ __global__ __launch_bounds__(256) void k_tsne_affinities(int n, int ld, const fl
       s0 += e;
       s1 += dd * e;
     }
-    s0 = block_sum_f64<4>(s0, sh0);
-    s1 = block_sum_f64<4>(s1, sh1);
+    s0 = block_sum_d<4>(s0, sh0);
+    s1 = block_sum_d<4>(s1, sh1);
     if (s0 == 0.0) s0 = 1e-8;
     used = beta;
     total = s0;
@@ -149,7 +130,7 @@ __global__ __launch_bounds__(256) void k_tsne_rowsum(int n, int ld, const float*
   const float* row = C + (size_t)blockIdx.x * ld;
   double s = 0.0;
   for (int j = threadIdx.x; j < n; j += 256) s += (double)row[j];
-  s = block_sum_f64<4>(s, sh);
+  s = block_sum_d<4>(s, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -158,7 +139,7 @@ __global__ __launch_bounds__(SUM_THREADS) void k_tsne_total(int n, const T* __re
   __shared__ double sh[SUM_THREADS / WAVE];
   double s = 0.0;
   for (int t = threadIdx.x; t < n; t += SUM_THREADS) s += (double)part[t];
-  s = block_sum_f64<SUM_THREADS / WAVE>(s, sh);
+  s = block_sum_d<SUM_THREADS / WAVE>(s, sh);
   if (threadIdx.x == 0) out[0] = s * scale;
 }
 
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(TG_THREADS) void k_tsne_pass(int n, int ld, const f
         grad[2 * row[r] + 1] = 4.f * s1;
       }
       if (MODE == 2) {
-        const double k = wave_sum_f64(kl[r]);
+        const double k = wave_sum_d(kl[r]);
         if (live) klrow[row[r]] = k;
       }
     }
@@ -315,8 +296,8 @@ __global__ __launch_bounds__(SUM_THREADS) void k_tsne_update(int n, float* __res
   }
   if (have_kl)
     for (int t = threadIdx.x; t < n; t += SUM_THREADS) kl += klrow[t];
-  gn = block_sum_f64<SUM_THREADS / WAVE>(gn, sh0);
-  kl = block_sum_f64<SUM_THREADS / WAVE>(kl, sh1);
+  gn = block_sum_d<SUM_THREADS / WAVE>(gn, sh0);
+  kl = block_sum_d<SUM_THREADS / WAVE>(kl, sh1);
   if (threadIdx.x == 0) {
     record[0] = have_kl ? kl : (double)NAN;
     record[1] = sqrt(gn);

@@ -281,8 +281,7 @@ def build_hic_graph_host(pos1, pos2, count, norm, resolution_bp, window_start, h
         expected = hicdist.expected_vector_host(pos1, pos2, count, norm, resolution_bp, norm_args=norm_args, **(expected_args or {}))
     if isinstance(norm, str):
         from . import hicnorm
-        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **(norm_args or {}))
-        hicnorm._require_converged(info)
+        norm = hicnorm.resolve_norm_host(pos1, pos2, count, norm, resolution_bp, norm_args=norm_args)
         norm = hicnorm.pad_vector(norm, int(ws[-1]) // int(resolution_bp) + 1 if n else 0)
     _, i, j, v = survivor_values(pos1, pos2, count, norm, resolution_bp, window_start, window_bp, min_distance_bp, expected,
                                  domains=domains, loops=loops)
@@ -402,6 +401,18 @@ class HicContacts:
         hicnorm._require_converged(info)
         return v
 
+    def _map_vectors(self, a, norm, resolution_bp, norm_args, expected=None, expected_args=None):
+        """(nv, ex): the device norm vector (or None) and expected vector of an analysis of the map `a` = contact_matrix(...).
+        norm: None, a vector, or a name (_named_norm at a's size); expected: None (the analysis reads none: ex is None), a
+        vector, or "auto" (expected_vector with this norm and expected_args).  A caller's own vector is uploaded, never kept."""
+        ex = None
+        if isinstance(expected, str):
+            ex = self.expected_vector(norm, resolution_bp, n_bins=a.n, norm_args=norm_args, **(expected_args or {}))
+        elif expected is not None:
+            ex = self._norm(expected)
+        nv = self._named_norm(norm, resolution_bp, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+        return nv, ex
+
     @staticmethod
     def _norm_key(norm, norm_args):
         """the part of a cache key that names the norm; None for a caller's vector (not cached)"""
@@ -504,7 +515,7 @@ class HicContacts:
         if key is not None and key in self._insulations:
             return self._insulations[key]
         a = self.contact_matrix(res, n_bins)
-        nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+        nv, _ = self._map_vectors(a, norm, res, norm_args)
         out = INS.insulation_of_matrix(a, nv, res, w, **rule)
         if key is not None:
             self._insulations[key] = out
@@ -532,7 +543,7 @@ class HicContacts:
         out = None if key is None else self._compartments.get(key)
         if out is None:
             a = self.contact_matrix(res, n_bins)
-            nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+            nv, _ = self._map_vectors(a, norm, res, norm_args)
             out = CP.compartments_of_matrix(a, nv, res, **rule)
             if key is not None:
                 self._compartments[key] = out
@@ -574,23 +585,17 @@ class HicContacts:
         or 'KR' / 'VC' / 'SQRTVC' (norm_vector with norm_args; a KR that did not converge raises HicNormError); expected: "auto"
         (expected_vector with this norm and expected_args = min_count) or a float64 vector.  **rule: loops.loop_rule's.  Kept per
         argument tuple for None and the three names with expected = "auto"."""
-        from . import loops as LP
+        from . import hicmap, loops as LP
         res = int(resolution_bp)
         checked = LP.loop_rule(res, 0, **rule)
-        if isinstance(expected, str) and expected != "auto":
-            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
-        nk = self._norm_key(norm, norm_args) if isinstance(expected, str) else None
+        nk = self._norm_key(norm, norm_args) if hicmap.auto_expected(expected) else None
         key = None if nk is None else nk + (res, None if n_bins is None else int(n_bins), checked) + tuple(
             sorted((expected_args or {}).items()))
         if key is not None and key in self._loops:
             return self._loops[key]
         a = self.contact_matrix(res, n_bins)
         LP.loop_rule(res, a.n, **rule)   # the size guard, before anything is allocated
-        if isinstance(expected, str):
-            ex = self.expected_vector(norm, res, n_bins=a.n, norm_args=norm_args, **(expected_args or {}))
-        else:
-            ex = self._norm(expected)
-        nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+        nv, ex = self._map_vectors(a, norm, res, norm_args, expected, expected_args)
         out = LP.loops_of_matrix(a, nv, ex, res, **rule)
         if key is not None:
             self._loops[key] = out
@@ -603,7 +608,7 @@ class HicContacts:
         its range (None: the largest id + 1, one read-back for a device tensor).  norm, expected: loops()'s; expected is read
         for value = "oe" alone.  The raw band and the value band are kept per argument tuple for None and the three names with
         expected = "auto", so that loops, graph edges and their controls on one map share them."""
-        from . import loops as LP, pileup as PU
+        from . import hicmap, pileup as PU
         res = int(resolution_bp)
         G = PU._n_groups(group, n_groups)
         rule = dict(value=value, w=w, corner=corner, min_dist=min_dist, max_distance_bp=max_distance_bp)
@@ -611,23 +616,18 @@ class HicContacts:
         ci, cj = PU._centres_of(centres)
         if not torch.is_tensor(ci):
             PU._centre_arrays(ci, cj, None if torch.is_tensor(group) else group)
-        if isinstance(expected, str) and expected != "auto":
-            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
+        auto = hicmap.auto_expected(expected)
         a = self.contact_matrix(res, n_bins)
         r = PU.pileup_rule(res, a.n, G, **rule)   # the size guard, before anything is allocated
         bkey = (res, a.n, r.width)
         if bkey not in self._pileup_bands:
-            self._pileup_bands[bkey] = LP.loop_band(a, r.width)
-        nk = self._norm_key(norm, norm_args) if (isinstance(expected, str) or r.value != "oe") else None
+            self._pileup_bands[bkey] = hicmap.device_band(a, r.width)
+        nk = self._norm_key(norm, norm_args) if (auto or r.value != "oe") else None
         key = None if nk is None else nk + bkey + (r.value,) + (tuple(sorted((expected_args or {}).items())) if r.value == "oe"
                                                                  else ())
         vb = None if key is None else self._pileup_values.get(key)
         if vb is None:
-            ex = None
-            if r.value == "oe":
-                ex = (self.expected_vector(norm, res, n_bins=a.n, norm_args=norm_args, **(expected_args or {}))
-                      if isinstance(expected, str) else self._norm(expected))
-            nv = self._named_norm(norm, res, norm_args, n_bins=a.n) if isinstance(norm, str) else self._norm(norm)
+            nv, ex = self._map_vectors(a, norm, res, norm_args, expected if r.value == "oe" else None, expected_args)
             vb = PU.value_band(self._pileup_bands[bkey], a.vc, nv, ex, r)
             if key is not None:
                 self._pileup_values[key] = vb

@@ -38,15 +38,6 @@ def clean_vector(v) -> np.ndarray:
     return ex
 
 
-def _resolve_norm_host(pos1, pos2, count, norm, resolution_bp, n_bins, norm_args):
-    """None, a vector, or 'KR' / 'VC' / 'SQRTVC' (computed from the records; a KR that did not converge raises) -> vector"""
-    if not isinstance(norm, str):
-        return norm
-    v, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, n_bins, **(norm_args or {}))
-    hicnorm._require_converged(info)
-    return v
-
-
 def distance_sums_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm_args=None):
     """(raw, act) of rule 1, float64 [n_bins] each, by np.bincount in record order"""
     res = int(resolution_bp)
@@ -64,13 +55,10 @@ def distance_sums_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm
         raise ValueError("n_bins=%d but the records reach bin %d" % (n, top - 1))
     d = np.abs(i - j)
     raw = np.bincount(d, weights=c, minlength=n).astype(np.float64)
-    norm = _resolve_norm_host(pos1, pos2, count, norm, res, n_bins, norm_args)
+    norm = hicnorm.resolve_norm_host(pos1, pos2, count, norm, res, n_bins, norm_args)
     if norm is None:
         return raw, raw.copy()
-    nv = np.full(max(n, 1), np.inf)
-    given = np.array(norm, dtype=np.float64).ravel()[:n]
-    nv[:given.size] = given
-    nv[np.isnan(nv) | (nv == 0.0)] = np.inf
+    nv = hicnorm.clean_norm(norm, n)   # n == 0: no records, nothing is read
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         w = c / (nv[i] * nv[j])
     return raw, np.bincount(d, weights=w, minlength=n).astype(np.float64)
@@ -124,13 +112,10 @@ def distance_sums_device_order_host(pos1, pos2, count, norm, resolution_bp, n_bi
     i, j = p1 // res, p2 // res
     d = np.abs(i - j)
     order = np.argsort(d, kind="stable")                                            # the key is (distance, record)
-    norm = _resolve_norm_host(pos1, pos2, count, norm, res, n_bins, norm_args)
+    norm = hicnorm.resolve_norm_host(pos1, pos2, count, norm, res, n_bins, norm_args)
     w = c
     if norm is not None:
-        nv = np.full(max(n, 1), np.inf)
-        given = np.array(norm, dtype=np.float64).ravel()[:n]
-        nv[:given.size] = given
-        nv[np.isnan(nv) | (nv == 0.0)] = np.inf
+        nv = hicnorm.clean_norm(norm, n)
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             w = c / (nv[i] * nv[j])
     return _device_order_sum(d[order], c[order], n), _device_order_sum(d[order], w[order], n)

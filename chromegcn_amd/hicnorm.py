@@ -248,6 +248,26 @@ def hic_norm_vector_host(pos1, pos2, count, kind, resolution_bp, n_bins=None, **
         return 1.0 / x, info
 
 
+def resolve_norm_host(pos1, pos2, count, norm, resolution_bp, n_bins=None, norm_args=None):
+    """None or a vector: as given; 'KR' / 'VC' / 'SQRTVC': the vector computed from the records (hic_norm_vector_host with
+    norm_args), HicNormError for a KR that did not converge"""
+    if not isinstance(norm, str):
+        return norm
+    size = {} if n_bins is None else {"n_bins": n_bins}   # build_hic_graph_host's norm_args may name n_bins themselves
+    v, info = hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, **size, **(norm_args or {}))
+    _require_converged(info)
+    return v
+
+
+def clean_norm(norm, n):
+    """the norm vector at n bins as a balanced value reads it: NaN, 0 and the bins beyond its length are +inf"""
+    nv = np.full(n, np.inf)
+    given = np.array(norm, dtype=np.float64).ravel()[:n]
+    nv[:given.size] = given
+    nv[np.isnan(nv) | (nv == 0.0)] = np.inf
+    return nv
+
+
 def pad_vector(v, n):
     """the vector with NaN bins appended up to n bins (windows beyond the last bin in contact)"""
     if torch.is_tensor(v):

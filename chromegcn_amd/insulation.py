@@ -39,7 +39,9 @@ import numpy as np
 import scipy.sparse as sp
 import torch
 
-from . import hicnorm
+from . import hicmap, hicnorm
+from .hicmap import valid_bins  # noqa: F401  (the tests of the commit before the move call insulation.valid_bins / clean_norm)
+from .hicnorm import clean_norm  # noqa: F401
 
 MAX_WINDOWS = 8
 MIN_VALID_SHARE, MIN_STRENGTH = 0.66, 0.5
@@ -67,21 +69,6 @@ def windows_in_bins(windows_bp, resolution_bp):
     return _check_windows([x // res for x in wbp])
 
 
-def clean_norm(norm, n):
-    """the norm vector at n bins as rule 1 reads it: NaN, 0 and the bins beyond its length are +inf"""
-    nv = np.full(n, np.inf)
-    given = np.array(norm, dtype=np.float64).ravel()[:n]
-    nv[:given.size] = given
-    nv[np.isnan(nv) | (nv == 0.0)] = np.inf
-    return nv
-
-
-def valid_bins(vc, norm):
-    """rule 3's valid[b] from the row sums and the norm vector (None: every bin in contact is valid)"""
-    vc = np.asarray(vc, dtype=np.float64).ravel()
-    return (vc > 0) if norm is None else (vc > 0) & np.isfinite(clean_norm(norm, vc.size))
-
-
 # ----------------------------------------------------------------------------------------------
 # host restatement of the sums
 # ----------------------------------------------------------------------------------------------
@@ -98,7 +85,7 @@ def diamond_sums_host(A, norm, windows):
     up = coo.col > coo.row
     a, b, v = coo.row[up].astype(np.int64), coo.col[up].astype(np.int64), coo.data[up]
     if norm is not None:
-        nv = clean_norm(norm, n)
+        nv = hicnorm.clean_norm(norm, n)
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             v = v / (nv[a] * nv[b])
     S = np.zeros((len(w_all), n))
@@ -216,12 +203,9 @@ def insulation_host(pos1, pos2, count, norm, resolution_bp, windows_bp, n_bins=N
     """The whole rule on the host.  norm: None, a vector at resolution_bp, or 'KR' / 'VC' / 'SQRTVC' (computed from the records:
     hicnorm.hic_norm_vector_host with norm_args); **rule: min_valid_share, span, min_strength."""
     w = windows_in_bins(windows_bp, resolution_bp)
-    A = hicnorm.contact_matrix_host(pos1, pos2, count, resolution_bp, n_bins)
-    if isinstance(norm, str):
-        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, resolution_bp, n_bins, **(norm_args or {}))
-        hicnorm._require_converged(info)
+    A, vc, norm, _ = hicmap.resolve_host(pos1, pos2, count, norm, resolution_bp, n_bins, norm_args)
     S = diamond_sums_host(A, norm, w)
-    valid = valid_bins(np.asarray(A.sum(axis=1)).ravel(), norm)
+    valid = hicmap.valid_bins(vc, norm)
     return Insulation(w, resolution_bp, S, valid, insulation_from_sums(S, valid, w, **_rule(rule)))
 
 
@@ -242,9 +226,7 @@ def diamond_sums(A: hicnorm.DeviceContactMatrix, norm, windows) -> torch.Tensor:
     out = torch.zeros(len(w), A.n, dtype=torch.float64, device=dev)
     if A.n == 0:
         return out
-    if norm is not None and not (torch.is_tensor(norm) and norm.device == dev and norm.dtype == torch.float64
-                                 and norm.is_contiguous() and norm.numel() > 0):
-        raise ValueError("norm must be a non-empty contiguous float64 vector on the matrix's device")
+    hicmap.device_vector(norm, dev, "norm", optional=True)
     with torch.cuda.device(dev):
         _lib.call("cgcn_hicinsul_sums", n=A.n, rowptr=A.rowptr, col=A.col, val=A.val, norm=norm,
                   n_norm=0 if norm is None else int(norm.numel()), n_windows=len(w), windows=(ctypes.c_int32 * len(w))(*w), out=out)
@@ -255,7 +237,7 @@ def insulation_of_matrix(A: hicnorm.DeviceContactMatrix, norm, resolution_bp, wi
     """rules 2 to 5 from the device matrix: the sums on the device, one read-back of S, VC and the vector, the shared function"""
     S = diamond_sums(A, norm, windows)
     nv = None if norm is None else norm.cpu().numpy()
-    valid = valid_bins(A.vc.cpu().numpy(), nv)
+    valid = hicmap.valid_bins(A.vc.cpu().numpy(), nv)
     return Insulation(windows, resolution_bp, S, valid, insulation_from_sums(S.cpu().numpy(), valid, windows, **_rule(rule)))
 
 
@@ -293,30 +275,9 @@ def domain_of_windows(window_start, domain_of_bin, domain_bp) -> np.ndarray:
     return np.where(inside, dom[np.clip(b, 0, max(dom.size - 1, 0))] if dom.size else -1, -1).astype(np.int64)
 
 
-def csr_of(graph_or_csr):
-    """(rowptr int64 [N + 1], col int64 [nnz], nnz) on the host of a graph: a ChromGraph, a scipy matrix, or (rowptr, col[, nnz])
-    tensors or arrays"""
-    g = graph_or_csr
-    if sp.issparse(g):
-        g = sp.csr_matrix(g)
-        rowptr, col = g.indptr, g.indices
-    elif isinstance(g, (tuple, list)):
-        rowptr, col = g[0], g[1]
-    else:
-        rowptr, col = g.rowptr, g.col
-    if torch.is_tensor(rowptr):
-        rowptr, col = rowptr.cpu().numpy(), col.cpu().numpy()
-    rowptr = np.asarray(rowptr, dtype=np.int64)
-    nnz = int(rowptr[-1]) if rowptr.size else 0
-    return rowptr, np.asarray(col, dtype=np.int64)[:nnz], nnz
-
-
 def domain_edge_share(graph_or_csr, domain_of_window):
-    """(same_domain_entries, nnz) as exact integers: the stored entries of a graph (csr_of's inputs) whose two windows lie in
-    one domain.  A negative domain never matches."""
-    rowptr, col, nnz = csr_of(graph_or_csr)
+    """(same_domain_entries, nnz) as exact integers: the stored entries of a graph (hicmap.csr_of's inputs) whose two windows
+    lie in one domain.  A negative domain never matches."""
     dom = np.asarray(domain_of_window, dtype=np.int64).ravel()
-    if dom.size != rowptr.size - 1:
-        raise ValueError("the graph has %d windows but domain_of_window has %d" % (rowptr.size - 1, dom.size))
-    row = np.repeat(np.arange(dom.size), np.diff(rowptr))
+    row, col, nnz = hicmap.edge_rows(graph_or_csr, dom.size, "domain_of_window")
     return int(np.sum((dom[row] == dom[col]) & (dom[row] >= 0))), nnz

@@ -9,13 +9,13 @@ enriched pixels is host code that the device path and the numpy restatement shar
 insulation.insulation_from_sums is shared.
 
 The rule, per chromosome.  res = resolution_bp (default 10 000); A = hicnorm's contact matrix at res (n bins); nv =
-insulation.clean_norm(norm), norm None, a vector, or 'KR' / 'VC' / 'SQRTVC' (default 'VC'); ex = a per-distance expected vector
+hicnorm.clean_norm(norm), norm None, a vector, or 'KR' / 'VC' / 'SQRTVC' (default 'VC'); ex = a per-distance expected vector
 for the same norm (expected = "auto": HicContacts.expected_vector(norm, res), on the host its restatement in the device's
-summation order, hicdist.distance_sums_device_order_host + expected_from_sums; or an explicit
+summation order, hicmap.resolve_host; or an explicit
 float64 vector, which reads as 0 beyond its length and must reach min(n, D + 1) entries); p the peak half-width and w the window
 half-width, 0 <= p < w <= 10, by default (4, 7) at 5 kb, (2, 5) at 10 kb, (1, 3) at 25 kb (any other resolution needs them
 given); D = max_distance_bp // res, max_distance_bp = 2 Mb by default: a convention, not a measurement.
-  1. Balanced value.  B[a, b] = A[a, b] / (nv[a] * nv[b]): insulation's rule 1.  valid = insulation.valid_bins(VC, norm), VC
+  1. Balanced value.  B[a, b] = A[a, b] / (nv[a] * nv[b]): insulation's rule 1.  valid = hicmap.valid_bins(VC, norm), VC
      the matrix's row sums.
   2. Cells.  A cell (a, b) takes part iff 0 <= a, b < n, b - a >= ignore_diags (default 2) and both bins are valid.
   3. Neighbourhoods of pixel (i, j), j = i + d; offsets (da, db) listed row-major, da ascending, then db ascending.
@@ -60,11 +60,10 @@ from __future__ import annotations
 from typing import NamedTuple
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
-from . import hicnorm
-from . import insulation as INS
+from . import hicmap, hicnorm
+from .hicmap import band_host, device_band as loop_band  # noqa: F401  (the tests of the commit before the move call them here)
 
 NAMES = ("donut", "lower_left", "horizontal", "vertical")
 N_CHUNKS, MAX_COUNT, FDR = 40, 10000, 0.1
@@ -296,43 +295,17 @@ def loops_from_pixels(pix: Pixels, resolution_bp, n, ratios=RATIOS, cluster_radi
 # ----------------------------------------------------------------------------------------------
 # host restatement of the stencil: band-shaped [n, D + 1], vectorised over pixels, sequential over offsets
 # ----------------------------------------------------------------------------------------------
-def band_host(A, width) -> np.ndarray:
-    """band float64 [n, width], band[i, d] = A[i, i + d] (0 beyond the matrix), from anything scipy makes a CSR of"""
-    width = int(width)
-    if width < 1:
-        raise ValueError("the band is at least one distance wide")
-    coo = sp.csr_matrix(A, dtype=np.float64).tocoo()
-    band = np.zeros((coo.shape[0], width))
-    d = coo.col.astype(np.int64) - coo.row
-    k = (d >= 0) & (d < width)
-    band[coo.row[k], d[k]] = coo.data[k]
-    return band
-
-
-def _expected_at(ex, n, size, D):
-    given = np.asarray(ex, dtype=np.float64).ravel()
-    if given.size < min(n, D + 1):
-        raise ValueError("the expected vector has %d entries but the pixels reach distance %d" % (given.size, min(n, D + 1) - 1))
-    out = np.zeros(size)
-    out[:min(size, given.size)] = given[:size]
-    return out
-
-
 def loop_lambdas_host(band, vc, norm, ex, p, w, D, ignore_diags=IGNORE_DIAGS, min_dist=None):
     """Rules 1 to 6 on the band: (lam float64 [4, n, D + 1], NaN off the candidates; candidate bool [n, D + 1]).  band is
-    band_host's with a width of at least D + 2 w + 1, vc the matrix's row sums, norm None or a vector, ex the expected vector."""
+    hicmap.band_host's with a width of at least D + 2 w + 1, vc the matrix's row sums, norm None or a vector, ex the expected vector."""
     band = np.asarray(band, dtype=np.float64)
     n, width = band.shape
     p, w, ig, md = _check_pw(p, w, ignore_diags, min_dist)
     D = int(D)
     if D < 0 or width < D + 2 * w + 1:
         raise ValueError("the band is %d wide but D=%d and w=%d need %d" % (width, D, w, D + 2 * w + 1))
-    vc = np.asarray(vc, dtype=np.float64).ravel()
-    if vc.size != n:
-        raise ValueError("vc has %d bins but the band has %d" % (vc.size, n))
-    valid = INS.valid_bins(vc, norm)
-    nv = np.ones(n) if norm is None else INS.clean_norm(norm, n)
-    exv = _expected_at(ex, n, D + 2 * w + 1, D)
+    valid, nv = hicmap.bins_of_band_host(vc, norm, n)
+    exv = hicmap.expected_at_host(ex, n, D + 2 * w + 1, D + 1, "pixels")
     lam, cand = np.full((4, n, D + 1), np.nan), np.zeros((n, D + 1), bool)
     if n == 0:
         return lam, cand
@@ -398,27 +371,17 @@ def enriched_pixels_host(band, lam, cand, thr, bounds=None, max_count=MAX_COUNT)
 def loops_host(pos1, pos2, count, norm="VC", resolution_bp=10000, expected="auto", n_bins=None, norm_args=None,
                expected_args=None, **rule) -> Loops:
     """The whole rule on the host.  norm: None, a vector at resolution_bp, or 'KR' / 'VC' / 'SQRTVC' (computed from the records);
-    expected: "auto" (hicdist.expected_from_sums with expected_args = min_count, of the distance sums under this norm added in the
-    device's order, hicdist.distance_sums_device_order_host: the vector HicContacts.expected_vector returns, bit for bit, so that
-    the local expected values are the device's too) or a vector; **rule: loop_rule's."""
-    from . import hicdist
+    expected: "auto" (hicmap.resolve_host's, with expected_args = min_count: the vector HicContacts.expected_vector returns, bit
+    for bit, so that the local expected values are the device's too) or a vector; **rule: loop_rule's."""
     res = int(resolution_bp)
     loop_rule(res, 0, **rule)
-    A = hicnorm.contact_matrix_host(pos1, pos2, count, res, n_bins)
+    A, vc = hicmap.matrix_host(pos1, pos2, count, res, n_bins)
     n = A.shape[0]
     r = loop_rule(res, n, **rule)
-    if isinstance(norm, str):
-        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, res, n_bins, **(norm_args or {}))
-        hicnorm._require_converged(info)
-    if isinstance(expected, str):
-        if expected != "auto":
-            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
-        # the distance sums in the device's order: "auto" is then HicContacts.expected_vector to the last bit
-        sums = hicdist.distance_sums_device_order_host(pos1, pos2, count, norm, res, n)
-        expected = hicdist.expected_from_sums(*sums, **(expected_args or {}))
-    band = band_host(A, r.width)
+    norm, expected = hicmap.vectors_host(pos1, pos2, count, n, norm, res, n_bins, norm_args, expected, expected_args)
+    band = hicmap.band_host(A, r.width)
     t = chunk_boundaries(r.K)
-    lam, cand = loop_lambdas_host(band, np.asarray(A.sum(axis=1)).ravel(), norm, expected, r.p, r.w, r.D, r.ignore_diags, r.min_dist)
+    lam, cand = loop_lambdas_host(band, vc, norm, expected, r.p, r.w, r.D, r.ignore_diags, r.min_dist)
     thr = loop_thresholds(loop_histograms_host(band, lam, cand, t, r.W - 1), r.fdr, t)
     pix = enriched_pixels_host(band, lam, cand, thr, t, r.W - 1)
     info = {"candidates": int(cand.sum()), "enriched": int(pix.i.size), "thresholds": thr, "host_syncs": 0}
@@ -428,49 +391,18 @@ def loops_host(pos1, pos2, count, norm="VC", resolution_bp=10000, expected="auto
 # ----------------------------------------------------------------------------------------------
 # device
 # ----------------------------------------------------------------------------------------------
-def _vector(v, dev, what, optional=False):
-    if v is None and optional:
-        return None
-    if not (torch.is_tensor(v) and v.device == dev and v.dtype == torch.float64 and v.is_contiguous() and v.ndim == 1
-            and v.numel() > 0):
-        raise ValueError("%s must be a non-empty contiguous float64 vector on the matrix's device" % what)
-    return v
-
-
-def loop_band(A: hicnorm.DeviceContactMatrix, width) -> torch.Tensor:
-    """band float64 [n, width] on the device, band[i, d] = A[i, i + d] (cgcn_hicloops_band: enqueue only)"""
-    from . import _lib
-    width = int(width)
-    if width < 1:
-        raise ValueError("the band is at least one distance wide")
-    dev = A.rowptr.device
-    band = torch.zeros(A.n, width, dtype=torch.float64, device=dev)
-    if A.n:
-        with torch.cuda.device(dev):
-            _lib.call("cgcn_hicloops_band", n=A.n, rowptr=A.rowptr, col=A.col, val=A.val, width=width, band=band)
-    return band
-
-
 def _stencil_args(band, vc, norm, ex, r: LoopRule):
     dev = band.device
-    n, width = int(band.shape[0]), int(band.shape[1])
-    if band.dtype != torch.float64 or not band.is_contiguous() or width < r.width:
-        raise ValueError("the band must be contiguous float64 [n, >= %d]" % r.width)
-    if n * (r.D + 1) > MAX_PIXELS:
-        raise ValueError("%d bins x %d distances are more than 2^28 band elements" % (n, r.D + 1))
-    _vector(vc, dev, "vc")
-    if int(vc.numel()) != n:
-        raise ValueError("vc has %d bins but the band has %d" % (int(vc.numel()), n))
-    norm, ex = _vector(norm, dev, "norm", optional=True), _vector(ex, dev, "the expected vector")
-    if int(ex.numel()) < min(n, r.D + 1):
-        raise ValueError("the expected vector has %d entries but the pixels reach distance %d" % (int(ex.numel()), min(n, r.D + 1) - 1))
+    n, width = hicmap.check_band(band, vc, r.width, r.D + 1)
+    norm, ex = hicmap.device_vector(norm, dev, "norm", optional=True), hicmap.device_vector(ex, dev, "the expected vector")
+    hicmap.expected_reach(int(ex.numel()), n, r.D + 1, "pixels")
     return dict(n=n, D=r.D, width=width, band=band, vc=vc, norm=norm, n_norm=0 if norm is None else int(norm.numel()),
                 expected=ex, n_expected=int(ex.numel()), p=r.p, w=r.w, ignore_diags=r.ignore_diags)
 
 
 def loop_histograms(band, vc, norm, ex, r: LoopRule, bounds=None, want_lambda=False):
     """Pass 1 on the device (cgcn_hicloops_pass1: enqueue only): (hist int32 [4, K, W], flags uint32-as-int32 [n, D + 1]: the
-    packed candidate bit and chunk indices that enriched_pixels reads, lambda float64 [4, n, D + 1] or None).  band: loop_band's,
+    packed candidate bit and chunk indices that enriched_pixels reads, lambda float64 [4, n, D + 1] or None).  band: hicmap.device_band's,
     at least r.width wide; vc, norm (or None), ex: float64 device vectors; bounds: the chunk boundaries (host), K - 1 of them."""
     from . import _lib
     args = _stencil_args(band, vc, norm, ex, r)
@@ -517,7 +449,7 @@ def loops_of_matrix(A: hicnorm.DeviceContactMatrix, norm, ex, resolution_bp, **r
     the histograms, of the count and of the list."""
     r = loop_rule(resolution_bp, A.n, **rule)
     t = chunk_boundaries(r.K)
-    band = loop_band(A, r.width)
+    band = hicmap.device_band(A, r.width)
     hist, flags, _ = loop_histograms(band, A.vc, norm, ex, r, t)
     hist = hist.cpu().numpy()
     thr = loop_thresholds(hist, r.fdr, t)
@@ -552,11 +484,8 @@ def same_loop_host(pos1, pos2, loops: Loops, pad_bins=1) -> np.ndarray:
 
 
 def loop_edge_share(graph_or_csr, loops: Loops, window_start, pad_bins=1):
-    """(entries in a footprint, nnz) as exact integers: the stored entries of a graph (insulation.csr_of's inputs) whose two
+    """(entries in a footprint, nnz) as exact integers: the stored entries of a graph (hicmap.csr_of's inputs) whose two
     windows, binned at the loops' resolution and lower bin first, lie in some loop's footprint"""
-    rowptr, col, nnz = INS.csr_of(graph_or_csr)
     ws = np.asarray(window_start, dtype=np.int64).ravel()
-    if ws.size != rowptr.size - 1:
-        raise ValueError("the graph has %d windows but window_start has %d" % (rowptr.size - 1, ws.size))
-    row = np.repeat(np.arange(ws.size), np.diff(rowptr))
+    row, col, nnz = hicmap.edge_rows(graph_or_csr, ws.size, "window_start")
     return int(np.sum(same_loop_host(ws[row], ws[col], loops, pad_bins))), nnz

@@ -8,8 +8,8 @@ Juicer's normed and rank APA matrices, per-centre enhancement histograms, saddle
 band, the slice sums and their fold run on the device (csrc/cgcn_pileup.hip); the keep test, the stable sort and the slice
 table are torch plumbing there and numpy here; apa_scores is host code that both paths share.
 
-The rule, per chromosome.  res = resolution_bp; A = hicnorm's contact matrix at res (n bins); nv = insulation.clean_norm(norm);
-valid = insulation.valid_bins(VC, norm), VC the matrix's row sums; ex = the expected vector exactly as loops' rule resolves
+The rule, per chromosome.  res = resolution_bp; A = hicnorm's contact matrix at res (n bins); nv = hicnorm.clean_norm(norm);
+valid = hicmap.valid_bins(VC, norm), VC the matrix's row sums; ex = the expected vector exactly as hicmap.resolve_host resolves
 `expected=` ("auto" or a float64 vector that reads as 0 beyond its length and reaches min(n, max_dist + 1) entries), needed for
 value = "oe" alone; w the window half-width, 1 <= w <= 10 (by default 10 at res <= 10 kb and 5 above), S = 2 w + 1; c the corner
 width, w // 2 + 1 by default (6 at w = 10), 1 <= c <= w.
@@ -44,9 +44,8 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import hicnorm
-from . import insulation as INS
-from . import loops as LP
+from . import hicmap, hicnorm
+from .loops import Loops
 
 SLICE = 256
 MAX_W, MAX_GROUPS, MAX_ELEMS, MAX_DISTANCE_BP = 10, 65536, 1 << 28, 2000000
@@ -211,26 +210,17 @@ def keep_centres_host(ci, cj, group, G, n, rule: PileupRule):
 # host restatement
 # ----------------------------------------------------------------------------------------------
 def value_band_host(band, vc, norm, ex, rule: PileupRule) -> np.ndarray:
-    """rule 1: the value band float64 [n, width] from loops.band_host's raw band (at least rule.width wide; the result is as
+    """rule 1: the value band float64 [n, width] from hicmap.band_host's raw band (at least rule.width wide; the result is as
     wide as the band), the matrix's row sums vc, norm None or a vector, ex the expected vector (None unless value = "oe")"""
     band = np.asarray(band, dtype=np.float64)
     n, width = band.shape
     if width < rule.width:
         raise ValueError("the band is %d wide but max_dist=%d and w=%d need %d" % (width, rule.max_dist, rule.w, rule.width))
-    vc = np.asarray(vc, dtype=np.float64).ravel()
-    if vc.size != n:
-        raise ValueError("vc has %d bins but the band has %d" % (vc.size, n))
-    valid = INS.valid_bins(vc, norm)
-    nv = np.ones(n) if norm is None else INS.clean_norm(norm, n)
+    valid, nv = hicmap.bins_of_band_host(vc, norm, n)
     if rule.value == "oe":
         if ex is None:
             raise ValueError('value="oe" needs an expected vector')
-        given = np.asarray(ex, dtype=np.float64).ravel()
-        if given.size < min(n, rule.max_dist + 1):
-            raise ValueError("the expected vector has %d entries but the centres reach distance %d"
-                             % (given.size, min(n, rule.max_dist + 1) - 1))
-        exv = np.zeros(width)
-        exv[:min(width, given.size)] = given[:width]
+        exv = hicmap.expected_at_host(ex, n, width, rule.max_dist + 1, "centres")
     if n == 0:
         return np.zeros((0, width))
     # bin b = a + dd of every cell as a window [n, width] over the vectors padded behind the matrix: a view, no index arrays
@@ -287,7 +277,7 @@ def pileup_sums_host(value_band, ci, cj, group, G, rule: PileupRule) -> Pileup:
 
 def _centres_of(centres):
     """(ci, cj) of the `centres` argument: a Loops (its peaks) or a pair"""
-    if isinstance(centres, LP.Loops):
+    if isinstance(centres, Loops):
         return centres.peak_i, centres.peak_j
     if not isinstance(centres, (tuple, list)) or len(centres) != 2:
         raise ValueError("centres must be a Loops or a pair (i, j) of integer arrays or device tensors")
@@ -308,28 +298,18 @@ def _n_groups(group, n_groups):
 def pileup_host(pos1, pos2, count, centres, group=None, n_groups=None, norm="VC", resolution_bp=10000, expected="auto",
                 n_bins=None, norm_args=None, expected_args=None, **rule) -> Pileup:
     """The whole rule on the host from the records.  norm: None, a vector at resolution_bp, or 'KR' / 'VC' / 'SQRTVC'; expected:
-    "auto" (as loops.loops_host forms it: the distance sums in the device's order) or a vector, read for value = "oe" alone;
+    "auto" (hicmap.resolve_host's: the distance sums in the device's order) or a vector, read for value = "oe" alone;
     **rule: pileup_rule's."""
-    from . import hicdist
     res = int(resolution_bp)
     G = _n_groups(group, n_groups)
-    pileup_rule(res, 0, G, **rule)
+    value = pileup_rule(res, 0, G, **rule).value   # decides whether an expected vector is read at all
     ci, cj = _centres_of(centres)
     _centre_arrays(ci, cj, group)
-    A = hicnorm.contact_matrix_host(pos1, pos2, count, res, n_bins)
-    n = A.shape[0]
-    r = pileup_rule(res, n, G, **rule)
-    if isinstance(norm, str):
-        norm, info = hicnorm.hic_norm_vector_host(pos1, pos2, count, norm, res, n_bins, **(norm_args or {}))
-        hicnorm._require_converged(info)
-    if r.value != "oe":
-        expected = None
-    elif isinstance(expected, str):
-        if expected != "auto":
-            raise ValueError("expected=%r is neither a vector nor 'auto'" % (expected,))
-        sums = hicdist.distance_sums_device_order_host(pos1, pos2, count, norm, res, n)
-        expected = hicdist.expected_from_sums(*sums, **(expected_args or {}))
-    vb = value_band_host(LP.band_host(A, r.width), np.asarray(A.sum(axis=1)).ravel(), norm, expected, r)
+    A, vc = hicmap.matrix_host(pos1, pos2, count, res, n_bins)
+    r = pileup_rule(res, A.shape[0], G, **rule)
+    norm, expected = hicmap.vectors_host(pos1, pos2, count, A.shape[0], norm, res, n_bins, norm_args,
+                                         expected if value == "oe" else None, expected_args)
+    vb = value_band_host(hicmap.band_host(A, r.width), vc, norm, expected, r)
     return pileup_sums_host(vb, ci, cj, group, G, r)
 
 
@@ -337,24 +317,15 @@ def pileup_host(pos1, pos2, count, centres, group=None, n_groups=None, norm="VC"
 # device
 # ----------------------------------------------------------------------------------------------
 def value_band(band, vc, norm, ex, rule: PileupRule) -> torch.Tensor:
-    """rule 1 on the device (cgcn_pileup_values: enqueue only): the value band float64 [n, width] from loops.loop_band's raw
+    """rule 1 on the device (cgcn_pileup_values: enqueue only): the value band float64 [n, width] from hicmap.device_band's raw
     band (at least rule.width wide); vc, norm (or None), ex (or None unless value = "oe"): float64 device vectors"""
     from . import _lib
     dev = band.device
-    n, width = int(band.shape[0]), int(band.shape[1])
-    if band.dtype != torch.float64 or not band.is_contiguous() or width < rule.width:
-        raise ValueError("the band must be contiguous float64 [n, >= %d]" % rule.width)
-    if n * width > MAX_ELEMS:
-        raise ValueError("%d bins x %d distances are more than 2^28 band elements" % (n, width))
-    LP._vector(vc, dev, "vc")
-    if int(vc.numel()) != n:
-        raise ValueError("vc has %d bins but the band has %d" % (int(vc.numel()), n))
-    norm = LP._vector(norm, dev, "norm", optional=True)
+    n, width = hicmap.check_band(band, vc, rule.width)
+    norm = hicmap.device_vector(norm, dev, "norm", optional=True)
     if rule.value == "oe":
-        ex = LP._vector(ex, dev, "the expected vector")
-        if int(ex.numel()) < min(n, rule.max_dist + 1):
-            raise ValueError("the expected vector has %d entries but the centres reach distance %d"
-                             % (int(ex.numel()), min(n, rule.max_dist + 1) - 1))
+        ex = hicmap.device_vector(ex, dev, "the expected vector")
+        hicmap.expected_reach(int(ex.numel()), n, rule.max_dist + 1, "centres")
     else:
         ex = None
     out = torch.empty(n, width, dtype=torch.float64, device=dev)
@@ -410,14 +381,10 @@ def pileup_sums(value_band, ci, cj, group, G, rule: PileupRule) -> Pileup:
     from . import _lib
     vb = value_band
     dev = vb.device
-    n, width = int(vb.shape[0]), int(vb.shape[1])
-    G = int(G)
+    n, G = int(vb.shape[0]), int(G)
     pileup_rule(rule.res, n, G, value=rule.value, w=rule.w, corner=rule.corner, min_dist=rule.min_dist,
                 max_distance_bp=rule.max_dist * rule.res)
-    if vb.dtype != torch.float64 or not vb.is_contiguous() or width < rule.width:
-        raise ValueError("the value band must be contiguous float64 [n, >= %d]" % rule.width)
-    if n * width > MAX_ELEMS:
-        raise ValueError("%d bins x %d distances are more than 2^28 band elements" % (n, width))
+    n, width = hicmap.check_band(vb, None, rule.width, what="value band")
     S = rule.S
     with torch.cuda.device(dev):
         ci, cj, g = _device_centres(ci, cj, group, dev)
@@ -437,14 +404,14 @@ def pileup_sums(value_band, ci, cj, group, G, rule: PileupRule) -> Pileup:
 
 def pileup_of_matrix(A: hicnorm.DeviceContactMatrix, norm, ex, centres, group=None, n_groups=None, resolution_bp=10000,
                      **rule) -> Pileup:
-    """Rules 1 to 4 from the device matrix: loops.loop_band, value_band and pileup_sums.  norm: None or a float64 device
+    """Rules 1 to 4 from the device matrix: hicmap.device_band, value_band and pileup_sums.  norm: None or a float64 device
     vector; ex: a float64 device vector (None unless value = "oe")."""
     G = _n_groups(group, n_groups)
     r = pileup_rule(resolution_bp, A.n, G, **rule)
     ci, cj = _centres_of(centres)
     if not torch.is_tensor(ci):
         _centre_arrays(ci, cj, None if torch.is_tensor(group) else group)
-    vb = value_band(LP.loop_band(A, r.width), A.vc, norm, ex, r)
+    vb = value_band(hicmap.device_band(A, r.width), A.vc, norm, ex, r)
     return pileup_sums(vb, ci, cj, group, G, r)
 
 
@@ -452,17 +419,14 @@ def pileup_of_matrix(A: hicnorm.DeviceContactMatrix, norm, ex, centres, group=No
 # centre lists
 # ----------------------------------------------------------------------------------------------
 def centres_of_graph(graph_or_csr, window_start, resolution_bp):
-    """(i, j, entry) int64: one centre per stored entry of a graph (insulation.csr_of's inputs) with col > row -- its two
+    """(i, j, entry) int64: one centre per stored entry of a graph (hicmap.csr_of's inputs) with col > row -- its two
     windows binned at resolution_bp as loops.loop_edge_share bins them, lower bin first -- and the entry's index into the
     graph's col / val arrays, so that per-entry values such as saliency can be carried along"""
-    rowptr, col, nnz = INS.csr_of(graph_or_csr)
     ws = np.asarray(window_start, dtype=np.int64).ravel()
-    if ws.size != rowptr.size - 1:
-        raise ValueError("the graph has %d windows but window_start has %d" % (rowptr.size - 1, ws.size))
+    row, col, _ = hicmap.edge_rows(graph_or_csr, ws.size, "window_start")
     res = int(resolution_bp)
     if res < 1:
         raise ValueError("resolution_bp must be positive")
-    row = np.repeat(np.arange(ws.size, dtype=np.int64), np.diff(rowptr))
     entry = np.nonzero(col > row)[0].astype(np.int64)
     b1, b2 = ws[row[entry]] // res, ws[col[entry]] // res
     return np.minimum(b1, b2), np.maximum(b1, b2), entry

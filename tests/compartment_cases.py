@@ -74,36 +74,45 @@ KERNEL_M = (1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65, 130, 257)
 LARGE_M = 1500
 
 
-def _holes(m, with_holes):
-    """the emptied bins of a kernel case with m kept bins: none, or one near each end (one only below 5 bins)"""
+def _holes(m, with_holes, with_norm=False):
+    """the emptied bins of a kernel case with m kept bins: none, or one near each end (one only below 5 bins); with_norm =
+    "short": five, the last of them the map's last bin"""
     if not with_holes:
         return ()
+    if with_norm == "short":
+        return (2, 20, 40, 50, m + 4)
     return (1,) if m < 5 else (2, m - 1)       # bins of the n = m + len(holes) map
 
 
 @functools.lru_cache(maxsize=None)
 def kernel_case(m, with_holes, with_norm):
     """a planted map that keeps exactly m bins: dict(planted's, norm: None or float64 [n], keep).  With a norm and holes, the
-    second hole is a NaN of the vector over a bin that HAS contacts, and the counts are fractional."""
-    holes = _holes(m, with_holes)
+    second hole is a NaN of the vector over a bin that HAS contacts, and the counts are fractional.  with_norm = "short" (with
+    holes, m >= 51): the holes behind the first are a NaN, a 0 and a +inf of the vector and a last bin beyond its end, all
+    over bins that have contacts."""
+    holes = _holes(m, with_holes, with_norm)
     n = m + len(holes)
     by_norm = holes[1:] if with_norm else ()
-    c = planted(n, 100 + m, tuple(h for h in holes if h not in by_norm), frac=with_norm)
+    c = planted(n, 100 + m, tuple(h for h in holes if h not in by_norm), frac=bool(with_norm))
     norm = None
     if with_norm:
         norm = np.random.default_rng(7 + m).lognormal(0.0, 0.4, n)
         norm[list(by_norm)] = np.nan
+    if with_norm == "short":
+        norm[holes[2]], norm[holes[3]] = 0.0, np.inf
+        norm = norm[:n - 1].copy()
     keep = np.setdiff1d(np.arange(n), holes).astype(np.int32)
     assert keep.size == m
     return dict(c, norm=norm, keep=keep)
 
 
 KERNEL_CASES = [(m, h, v) for m in KERNEL_M for h in (False, True) for v in (False, True)] + [(LARGE_M, False, False),
-                                                                                             (LARGE_M, True, True)]
+                                                                                             (LARGE_M, True, True),
+                                                                                             (65, True, "short")]
 
 
 def case_id(c):
-    return "m%d%s%s" % (c[0], "_holes" if c[1] else "", "_norm" if c[2] else "")
+    return "m%d%s%s" % (c[0], "_holes" if c[1] else "", "_shortnorm" if c[2] == "short" else "_norm" if c[2] else "")
 
 
 # ----------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ import functools
 import numpy as np
 import scipy.sparse as sp
 
-from chromegcn_amd import insulation
+from chromegcn_amd import hicnorm, insulation
 
 from hicnorm_cases import GRAPH_EDGES, RES, case, dense, full_row, graph_case, hic_like  # noqa: F401
 
@@ -66,13 +66,16 @@ def planted_host(name, seed=1):
                                       n_bins=c["n_bins"], min_strength=RECOVERY_STRENGTH)
 
 
-def noisy_norm(n, seed):
-    """a norm vector with NaN and 0 bins, one bin short of n (the last bin reads as +inf)"""
+def noisy_norm(n, seed, inf=False):
+    """a norm vector with NaN and 0 bins, one bin short of n (the last bin reads as +inf); inf: one +inf entry as well"""
     rng = np.random.default_rng(seed)
     v = rng.lognormal(0.0, 0.4, max(n - 1, 1))
     if n > 4:
         v[rng.choice(v.size, 2, replace=False)] = np.nan
         v[rng.choice(v.size, 2, replace=False)] = 0.0
+    if inf:
+        good = np.flatnonzero(np.isfinite(v) & (v != 0.0))
+        v[good[good.size // 2]] = np.inf
     return v
 
 
@@ -82,7 +85,7 @@ def balanced(A, norm):
     A.sort_indices()
     if norm is None:
         return A
-    nv = insulation.clean_norm(norm, A.shape[0])
+    nv = hicnorm.clean_norm(norm, A.shape[0])
     row = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
         return sp.csr_matrix((A.data / (nv[row] * nv[A.indices]), A.indices, A.indptr), shape=A.shape)
@@ -111,7 +114,7 @@ def loop_sums(a, norm, windows):
     """rule 2 as the literal double loop over the dense matrix: (S, K) with K the non-zero terms of each sum"""
     n = a.shape[0]
     if norm is not None:
-        nv = insulation.clean_norm(norm, n)
+        nv = hicnorm.clean_norm(norm, n)
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             a = a / (nv[:, None] * nv[None, :])
     rows = a.tolist()

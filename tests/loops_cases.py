@@ -7,7 +7,7 @@ import functools
 import numpy as np
 import scipy.sparse as sp
 
-from chromegcn_amd import insulation, loops
+from chromegcn_amd import hicmap, hicnorm, loops
 
 from insulation_cases import GRAPH_EDGES, RES, case, graph_case, noisy_norm  # noqa: F401
 
@@ -61,8 +61,8 @@ def distance_mean(A, norm):
     """the plain per-distance mean of the balanced values over the pairs of valid bins, float64 [n] (0 where no pair is valid)"""
     A = sp.csr_matrix(A, dtype=np.float64)
     n = A.shape[0]
-    valid = insulation.valid_bins(np.asarray(A.sum(axis=1)).ravel(), norm)
-    nv = np.ones(n) if norm is None else insulation.clean_norm(norm, n)
+    valid = hicmap.valid_bins(np.asarray(A.sum(axis=1)).ravel(), norm)
+    nv = np.ones(n) if norm is None else hicnorm.clean_norm(norm, n)
     coo = sp.triu(A).tocoo()
     k = valid[coo.row] & valid[coo.col]
     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
@@ -75,7 +75,6 @@ def distance_mean(A, norm):
 @functools.lru_cache(maxsize=None)
 def planted_vectors(seed):
     """(the VC vector, the plain per-distance mean under it) of a planted map, as the host computes them"""
-    from chromegcn_amd import hicnorm
     c = planted(seed)
     vc, _ = hicnorm.hic_norm_vector_host(c["pos1"], c["pos2"], c["count"], "VC", c["res"], c["n_bins"])
     return vc, distance_mean(hicnorm.contact_matrix_host(c["pos1"], c["pos2"], c["count"], c["res"], c["n_bins"]), vc)

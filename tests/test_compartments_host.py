@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from chromegcn_amd import bootstrap, build_hic_graph_host, hicnorm, insulation
+from chromegcn_amd import bootstrap, build_hic_graph_host, hicmap, hicnorm, insulation
 from chromegcn_amd import compartments as CP
 
 import compartment_cases as CC
@@ -26,7 +26,7 @@ def literal(c):
     """rules 1 to 6 of the docstring as plain Python loops over lists: dict of B, dsum, cnt, K (terms per distance), e, M, mean, ss"""
     A = hicnorm.contact_matrix_host(c["pos1"], c["pos2"], c["count"], c["res"], c["n_bins"]).toarray()
     n = A.shape[0]
-    nv = None if c["norm"] is None else insulation.clean_norm(c["norm"], n)
+    nv = None if c["norm"] is None else hicnorm.clean_norm(c["norm"], n)
     keep = [b for b in range(n) if sum(A[b]) > 0 and (nv is None or math.isfinite(nv[b]))]
     m = len(keep)
     B = [[A[a, b] if nv is None else A[a, b] / (nv[a] * nv[b]) for b in keep] for a in keep]
@@ -53,7 +53,7 @@ def test_restatements_against_literal_loops(case):
     keep, n, m = c["keep"], c["n_bins"], c["keep"].size
     assert L["keep"] == keep.tolist()
     A = hicnorm.contact_matrix_host(c["pos1"], c["pos2"], c["count"], c["res"], n)
-    valid = insulation.valid_bins(np.asarray(A.sum(axis=1)).ravel(), c["norm"])
+    valid = hicmap.valid_bins(np.asarray(A.sum(axis=1)).ravel(), c["norm"])
     got_keep, rank = CP.kept_bins(valid, c["res"])
     assert np.array_equal(got_keep, keep) and np.array_equal(np.flatnonzero(rank >= 0), keep) and rank[keep].tolist() == list(range(m))
     B = CP.balanced_dense_host(A, c["norm"], keep)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from chromegcn_amd import HicContacts, bootstrap, build_hic_graph_host, insulation
+from chromegcn_amd import HicContacts, bootstrap, build_hic_graph_host, hicmap
 from chromegcn_amd import compartments as CP
 
 import compartment_cases as CC
@@ -38,7 +38,7 @@ def stages(case):
     hc = HicContacts(c["pos1"], c["pos2"], c["count"], DEV)
     A = hc.contact_matrix(CC.RES, n)
     nv = None if c["norm"] is None else torch.from_numpy(c["norm"]).to(DEV)
-    valid = insulation.valid_bins(A.vc.cpu().numpy(), c["norm"])
+    valid = hicmap.valid_bins(A.vc.cpu().numpy(), c["norm"])
     assert np.array_equal(np.flatnonzero(valid), keep)
     Bd = CP.balanced_dense(A, nv, keep)
     B = twice(lambda: CP.balanced_dense(A, nv, keep))

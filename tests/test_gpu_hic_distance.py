@@ -41,11 +41,14 @@ def one_distance(m=10000, n_bins=300, d=5, seed=3):
                 count=rng.uniform(0.5, 30.0, m), res=HC.RES, n_bins=n_bins)
 
 
-def noisy_norm(n_bins, seed):
+def noisy_norm(n_bins, seed, inf=False):
     rng = np.random.default_rng(seed)
     nv = rng.lognormal(0.0, 0.5, n_bins)
     if n_bins > 8:
-        nv[rng.choice(n_bins, 4, replace=False)] = [np.nan, 0.0, np.nan, 0.0]
+        bad = rng.choice(n_bins, 4, replace=False)
+        nv[bad] = [np.nan, 0.0, np.nan, 0.0]
+        if inf:
+            nv[np.setdiff1d(np.arange(n_bins), bad)[0]] = np.inf
     return nv
 
 
@@ -100,6 +103,8 @@ def test_distance_sums_equal_the_host(name):
         dev = check_sums(c, noisy_norm(20, 9), name + " short vector", n_bins=None)
         assert dev.distance_sums(None, c["res"])[0].numel() == int(max(c["pos1"].max(), c["pos2"].max())) // c["res"] + 1
         check_sums(c, None, name + " wide", n_bins=300)
+    if name == "m70k_n257":   # NaN, 0 and +inf entries beside empty bins, n_bins no multiple of 64
+        check_sums(c, noisy_norm(c["n_bins"], 9, inf=True), name + " vector with +inf")
 
 
 def test_bad_records_are_refused():

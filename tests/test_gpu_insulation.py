@@ -33,10 +33,10 @@ def device_matrix(name):
     return hc, A, A.to_host()
 
 
-def check_sums(name, windows, with_norm):
+def check_sums(name, windows, with_norm, inf=False):
     c = IC.case(name)
     _, A, host = device_matrix(name)
-    norm = IC.noisy_norm(c["n_bins"], 40 + c["n_bins"]) if with_norm else None
+    norm = IC.noisy_norm(c["n_bins"], 40 + c["n_bins"], inf) if with_norm else None
     nv = None if norm is None else torch.from_numpy(norm).to(DEV)
     ref = insulation.diamond_sums_host(host, norm, windows)
     got = insulation.diamond_sums(A, nv, windows)
@@ -56,6 +56,13 @@ def test_diamond_sums(name, windows, with_norm):
     got = check_sums(name, windows, with_norm)
     if IC.case(name)["n_bins"] > 2 and not with_norm:
         assert np.all(got[:, 1:].sum(axis=1) > 0)
+
+
+def test_diamond_sums_with_every_kind_of_bad_norm_entry():
+    """n63: 63 bins, four of them empty; the vector is a bin short and holds NaN, 0 and +inf"""
+    norm = IC.noisy_norm(63, 40 + 63, inf=True)
+    assert norm.size == 62 and np.isnan(norm).any() and (norm == 0).any() and np.isinf(norm).any()
+    check_sums("n63", EIGHT, True, inf=True)
 
 
 @pytest.mark.parametrize("windows", [(1,), (63,), (65,), (63, 64, 65)])

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from chromegcn_amd import HicContacts, build_hic_graph_host, loops
+from chromegcn_amd import HicContacts, build_hic_graph_host, hicmap, loops
 
 import loops_cases as LC
 
@@ -34,10 +34,11 @@ def device_case(name):
 
 
 @functools.lru_cache(maxsize=None)
-def device_map(n, seed=0, density=0.5, reach=None, top=40):
-    """(the device matrix, the matrix read back, its row sums) of a sparse integer map with n bins"""
+def device_map(n, seed=0, density=0.5, reach=None, top=40, empty=()):
+    """(the device matrix, the matrix read back, its row sums) of a sparse integer map with n bins, the bins `empty` left out"""
     p1, p2, cnt = LC.records_of(LC.sparse_integer_map(n, n if reach is None else reach, 100 + n + seed, density=density, top=top))
-    A = HicContacts(p1, p2, cnt, DEV).contact_matrix(LC.RES, n)
+    k = ~np.isin(p1 // LC.RES, empty) & ~np.isin(p2 // LC.RES, empty)
+    A = HicContacts(p1[k], p2[k], cnt[k], DEV).contact_matrix(LC.RES, n)
     host = A.to_host()
     return A, host, np.asarray(host.sum(axis=1)).ravel()
 
@@ -50,10 +51,10 @@ def dev(v):
 def test_band(name):
     A, host = device_case(name)
     for width in (1, 63, 64, 65, 400):       # either side of a wavefront; 400 exceeds every n here
-        got = loops.loop_band(A, width).cpu().numpy()
-        assert same_bits(got, loops.band_host(host, width)), width
+        got = hicmap.device_band(A, width).cpu().numpy()
+        assert same_bits(got, hicmap.band_host(host, width)), width
     with pytest.raises(ValueError):
-        loops.loop_band(A, 0)
+        hicmap.device_band(A, 0)
 
 
 def d_values(n, md):
@@ -63,34 +64,46 @@ def d_values(n, md):
 @pytest.mark.parametrize("with_norm", [False, True], ids=["raw", "noisy_norm"])
 @pytest.mark.parametrize("n", [2, 15, 64, 65, 200, 257])
 def test_lambda_bit_for_bit(n, with_norm):
-    A, host, vc = device_map(n)
-    norm = LC.noisy_norm(n, 70 + n) if with_norm else None
+    check_lambda(n, with_norm)
+
+
+@pytest.mark.parametrize("with_norm", [False, True], ids=["raw", "noisy_norm"])
+def test_lambda_bit_for_bit_beside_empty_bins(with_norm):
+    """bins without a contact next to the vector's NaN, 0 and +inf bins and its missing last bin"""
+    A, host, vc = device_map(130, empty=(7, 64, 129))
+    assert np.all(vc[[7, 64, 129]] == 0)
+    check_lambda(130, with_norm, empty=(7, 64, 129))
+
+
+def check_lambda(n, with_norm, empty=()):
+    A, host, vc = device_map(n, empty=empty)
+    norm = LC.noisy_norm(n, 70 + n, inf=bool(empty)) if with_norm else None
     ex = np.random.default_rng(n).uniform(0.2, 3.0, n)
     candidates = 0
     for p, w in PW:
         for D in d_values(n, p + 3):
             r = loops.loop_rule(LC.RES, n, p=p, w=w, max_distance_bp=D * LC.RES)
             assert r.D == D and r.min_dist == p + 3
-            want_lam, want_cand = loops.loop_lambdas_host(loops.band_host(host, r.width), vc, norm, ex, p, w, D)
-            band = loops.loop_band(A, r.width)
+            want_lam, want_cand = loops.loop_lambdas_host(hicmap.band_host(host, r.width), vc, norm, ex, p, w, D)
+            band = hicmap.device_band(A, r.width)
             hist, flags, lam = loops.loop_histograms(band, A.vc, dev(norm), dev(ex), r, want_lambda=True)
             hist2, flags2, lam2 = loops.loop_histograms(band, A.vc, dev(norm), dev(ex), r, want_lambda=True)
             lam, lam2 = lam.cpu().numpy(), lam2.cpu().numpy()
             assert same_bits(lam, want_lam), (p, w, D)                    # the NaN pattern included
             assert same_bits(lam, lam2) and torch.equal(hist, hist2) and torch.equal(flags, flags2)
             assert np.array_equal((flags.cpu().numpy() < 0), want_cand)   # bit 31: the candidate
-            want_hist = loops.loop_histograms_host(loops.band_host(host, r.width), want_lam, want_cand)
+            want_hist = loops.loop_histograms_host(hicmap.band_host(host, r.width), want_lam, want_cand)
             assert np.array_equal(hist.cpu().numpy(), want_hist)
             candidates += int(want_cand.sum())
     assert candidates > 0 or n < 15
 
 
 def check_hist_and_pixels(A, host, vc, norm, ex, r, thresholds=("computed",)):
-    hband = loops.band_host(host, r.width)
+    hband = hicmap.band_host(host, r.width)
     t = loops.chunk_boundaries(r.K)
     want_lam, want_cand = loops.loop_lambdas_host(hband, vc, norm, ex, r.p, r.w, r.D, r.ignore_diags, r.min_dist)
     want_hist = loops.loop_histograms_host(hband, want_lam, want_cand, t, r.W - 1)
-    band = loops.loop_band(A, r.width)
+    band = hicmap.device_band(A, r.width)
     hist, flags, _ = loops.loop_histograms(band, A.vc, dev(norm), dev(ex), r, t)
     hist = hist.cpu().numpy()
     assert np.array_equal(hist, want_hist)

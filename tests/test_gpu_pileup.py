@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from chromegcn_amd import HicContacts, loops, pileup
+from chromegcn_amd import HicContacts, hicmap, pileup
 
 import pileup_cases as PC
 from pileup_cases import LC
@@ -38,11 +38,11 @@ def bands(n, w, value, norm_kind="noisy", empty=()):
     """(the rule, the device value band, the restatement's) of a map; the expected vector stops short of the band and has a zero"""
     A, host, vc = device_map(n, empty)
     r = PC.rule_for(n, w, value)
-    norm = {"none": None, "noisy": PC.noisy_norm(n, 70 + n)}[norm_kind]
+    norm = {"none": None, "noisy": PC.noisy_norm(n, 70 + n), "noisy_inf": PC.noisy_norm(n, 70 + n, inf=True)}[norm_kind]
     ex = np.random.default_rng(n + w).uniform(0.2, 3.0, r.max_dist + 1)       # min(n, max_dist + 1) at least; the band is wider
     ex[r.min_dist + 1] = 0.0
-    want = pileup.value_band_host(loops.band_host(host, r.width), vc, norm, ex, r)
-    got = pileup.value_band(loops.loop_band(A, r.width), A.vc, dev(norm), dev(ex) if value == "oe" else None, r)
+    want = pileup.value_band_host(hicmap.band_host(host, r.width), vc, norm, ex, r)
+    got = pileup.value_band(hicmap.device_band(A, r.width), A.vc, dev(norm), dev(ex) if value == "oe" else None, r)
     return r, got, want
 
 
@@ -60,6 +60,13 @@ def test_value_band_bit_for_bit(value, norm_kind):
             assert not took[empty[0]].any() and not took[empty[0] - 1, 1].any()
         if value == "oe":
             assert not took[:, r.min_dist + 1].any() and not took[:, r.max_dist + 1:].any()
+
+
+@pytest.mark.parametrize("value", pileup.VALUES)
+def test_value_band_with_every_kind_of_bad_norm_entry(value):
+    """257 bins, two of them empty; the vector is a bin short and holds NaN, 0 and +inf"""
+    r, got, want = bands(257, 10, value, "noisy_inf", (3, 100))
+    assert PC.same_bits(got.cpu().numpy(), want) and np.isfinite(want).any()
 
 
 def run_twice(vb, ci, cj, g, G, r):
@@ -127,7 +134,7 @@ def test_integer_counts_are_exact():
     A, host, vc = device_map(n)
     for w in (2, 10):
         r = PC.rule_for(n, w, "observed")
-        vb = pileup.value_band(loops.loop_band(A, r.width), A.vc, None, None, r)
+        vb = pileup.value_band(hicmap.device_band(A, r.width), A.vc, None, None, r)
         ci, cj, g = PC.centres(n, r, 3000, 3, seed=11 + w)
         got = run_twice(vb, ci, cj, g, 3, r)
         want, cnt = PC.integer_reference(host, ci, cj, g, 3, r)
@@ -144,7 +151,7 @@ def test_max_dist_at_the_guards_edge():
     assert r.width == width and n * width <= pileup.MAX_ELEMS < n * (width + 1)
     ci, cj = np.array([1, 1, 2, 1, 0]), np.array([4, 5, 5, 3, 4])
     got = pileup.pileup_of_matrix(A, None, None, (ci, cj), resolution_bp=PC.RES, **kw)
-    want = pileup.pileup_sums_host(pileup.value_band_host(loops.band_host(host, width), vc, None, None, r), ci, cj, None, 1, r)
+    want = pileup.pileup_sums_host(pileup.value_band_host(hicmap.band_host(host, width), vc, None, None, r), ci, cj, None, 1, r)
     PC.assert_same_pileup(got, want)
     assert got.kept.tolist() == [3] and got.skipped == {"group": 0, "edge": 1, "near": 1, "far": 0}
     before = torch.cuda.memory_allocated()

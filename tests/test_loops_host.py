@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 from scipy.stats import poisson
 
-from chromegcn_amd import build_hic_graph_host, hicnorm, loops
+from chromegcn_amd import build_hic_graph_host, hicmap, hicnorm, loops
 
 import loops_cases as LC
 
@@ -18,11 +18,10 @@ def same_bits(a, b):
 
 def literal_pixels(A, norm, ex, p, w, D, ignore_diags=2, min_dist=None):
     """rules 1 to 6, one pixel and one cell after the other from the dense matrix: (lam [4, n, D + 1], cand [n, D + 1])"""
-    from chromegcn_amd import insulation
     n = A.shape[0]
     md = p + ignore_diags + 1 if min_dist is None else min_dist
-    valid = insulation.valid_bins(A.sum(axis=1), norm)
-    nv = np.ones(n) if norm is None else insulation.clean_norm(norm, n)
+    valid = hicmap.valid_bins(A.sum(axis=1), norm)
+    nv = np.ones(n) if norm is None else hicnorm.clean_norm(norm, n)
     offs = [o.tolist() for o in loops.neighbourhood_offsets(p, w)]
     lam, cand = np.full((4, n, D + 1), np.nan), np.zeros((n, D + 1), bool)
     for i in range(n):
@@ -73,17 +72,6 @@ def test_chunk_boundaries_and_the_chunk_index():
     assert same_bits(t, np.power(2.0, np.arange(39) / 3.0))
 
 
-def test_band_host():
-    A = LC.sparse_integer_map(40, 12, 3)
-    dense = A.toarray()
-    for width in (1, 5, 13, 64, 70):
-        band = loops.band_host(A, width)
-        assert band.shape == (40, width)
-        for i in range(40):
-            for d in range(width):
-                assert band[i, d] == (dense[i, i + d] if i + d < 40 else 0.0)
-
-
 @pytest.mark.parametrize("p,w,D,with_norm", [(1, 3, 12, False), (1, 3, 30, True), (0, 1, 5, True), (2, 5, 9, False)])
 def test_the_band_restatement_equals_the_literal_loop(p, w, D, with_norm):
     n = 23
@@ -92,7 +80,7 @@ def test_the_band_restatement_equals_the_literal_loop(p, w, D, with_norm):
     norm = LC.noisy_norm(n, 9) if with_norm else None
     ex = np.random.default_rng(2).uniform(0.5, 3.0, n)
     want_lam, want_cand = literal_pixels(A, norm, ex, p, w, D)
-    lam, cand = loops.loop_lambdas_host(loops.band_host(A, D + 2 * w + 1), A.sum(axis=1), norm, ex, p, w, D)
+    lam, cand = loops.loop_lambdas_host(hicmap.band_host(A, D + 2 * w + 1), A.sum(axis=1), norm, ex, p, w, D)
     assert np.array_equal(cand, want_cand) and cand.sum() > 0
     assert same_bits(lam, want_lam)
 
@@ -102,7 +90,7 @@ def test_exact_plant_lambda_equals_the_count_bit_for_bit():
     g = np.round(300.0 / (1.0 + np.arange(n))) + 1.0              # integer counts falling with distance
     A = LC.constant_map(n, g)
     A[18, :] = A[:, 18] = 0.0                                     # an empty bin: not valid
-    band = loops.band_host(A, D + 2 * w + 1)
+    band = hicmap.band_host(A, D + 2 * w + 1)
     lam, cand = loops.loop_lambdas_host(band, A.sum(axis=1), None, g, p, w, D)
     i, d = np.nonzero(cand)
     for x in range(4):

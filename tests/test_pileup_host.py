@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from chromegcn_amd import hic, hicnorm, loops, pileup
+from chromegcn_amd import hic, hicmap, hicnorm, loops, pileup
 
 import pileup_cases as PC
 from pileup_cases import LC
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def host_band(A, norm, ex, r):
     A = sp.csr_matrix(A, dtype=np.float64)
-    return pileup.value_band_host(loops.band_host(A, r.width), np.asarray(A.sum(axis=1)).ravel(), norm, ex, r)
+    return pileup.value_band_host(hicmap.band_host(A, r.width), np.asarray(A.sum(axis=1)).ravel(), norm, ex, r)
 
 
 @pytest.mark.parametrize("value", pileup.VALUES)

@@ -22,7 +22,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from chromegcn_amd import compartments as CP  # noqa: E402
-from chromegcn_amd import hic, insulation  # noqa: E402
+from chromegcn_amd import hic, hicmap  # noqa: E402
 
 CHR1_BP = 249250621
 FP64_PEAK_TFLOPS = 78.6
@@ -64,7 +64,7 @@ def bench_one(torch, res, reps, steps, host):
     nv = hc.norm_vector("VC", res, n)
     torch.cuda.synchronize()
     out["aggregate_and_vc_s"] = time.perf_counter() - t0
-    valid = insulation.valid_bins(A.vc.cpu().numpy(), nv.cpu().numpy())
+    valid = hicmap.valid_bins(A.vc.cpu().numpy(), nv.cpu().numpy())
     keep, _ = CP.kept_bins(valid, res)
     m = int(keep.size)
     out["m"] = m

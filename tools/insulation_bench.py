@@ -26,7 +26,7 @@ import scipy.sparse as sp
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from chromegcn_amd import hic, hicnorm, insulation, synth  # noqa: E402
+from chromegcn_amd import hic, hicmap, hicnorm, insulation, synth  # noqa: E402
 
 
 def timed(fn, reps):
@@ -72,8 +72,8 @@ def main():
         sums_raw = timed(lambda: insulation.diamond_sums(A, None, w), opt.reps)
         sums_vc = timed(lambda: insulation.diamond_sums(A, vc, w), opt.reps)
         S = insulation.diamond_sums(A, None, w)
-        valid = insulation.valid_bins(A.vc.cpu().numpy(), None)
-        rule = timed(lambda: insulation.insulation_from_sums(S.cpu().numpy(), insulation.valid_bins(A.vc.cpu().numpy(), vc.cpu().numpy()), w),
+        valid = hicmap.valid_bins(A.vc.cpu().numpy(), None)
+        rule = timed(lambda: insulation.insulation_from_sums(S.cpu().numpy(), hicmap.valid_bins(A.vc.cpu().numpy(), vc.cpu().numpy()), w),
                      opt.reps)
 
         def end_to_end():

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from chromegcn_amd import hic, loops, synth  # noqa: E402
+from chromegcn_amd import hic, hicmap, loops, synth  # noqa: E402
 
 
 def timed(fn, reps):
@@ -67,8 +67,8 @@ def main():
         t = loops.chunk_boundaries(r.K)
         vc = c.norm_vector("VC", opt.res, n_bins=A.n)
         ex = c.expected_vector("VC", opt.res, n_bins=A.n)
-        band_ms = timed(lambda: loops.loop_band(A, r.width), opt.reps)
-        band = loops.loop_band(A, r.width)
+        band_ms = timed(lambda: hicmap.device_band(A, r.width), opt.reps)
+        band = hicmap.device_band(A, r.width)
         pass1_ms = timed(lambda: loops.loop_histograms(band, A.vc, vc, ex, r, t), opt.reps)
         hist, flags, _ = loops.loop_histograms(band, A.vc, vc, ex, r, t)
         thr = loops.loop_thresholds(hist.cpu().numpy(), r.fdr, t)
@@ -91,7 +91,7 @@ def main():
               "pass2_ms": round(pass2_ms, 3), "host_part_ms": round(host_part_ms, 1), "loops_ms": round(loops_ms, 3)}
         if not opt.no_host:
             host = A.to_host()
-            hband = loops.band_host(host, r.width)
+            hband = hicmap.band_host(host, r.width)
             nv, exh = vc.cpu().numpy(), ex.cpu().numpy()
             (lam, cand), t_lam = host_ms(lambda: loops.loop_lambdas_host(hband, np.asarray(host.sum(axis=1)).ravel(), nv, exh, r.p,
                                                                          r.w, r.D, r.ignore_diags, r.min_dist))

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from chromegcn_amd import _lib, hic, loops, pileup, synth  # noqa: E402
+from chromegcn_amd import _lib, hic, hicmap, pileup, synth  # noqa: E402
 
 
 def timed(fn, reps):
@@ -79,8 +79,8 @@ def main():
         ci, cj = b1[top].contiguous(), b2[top].contiguous()
         group = None if G == 1 else torch.from_numpy(pileup.quantile_groups(d[top].cpu().numpy(), G)).to(dev)
         M = int(ci.numel())
-        band_ms = timed(lambda: loops.loop_band(A, r.width), opt.reps)
-        band = loops.loop_band(A, r.width)
+        band_ms = timed(lambda: hicmap.device_band(A, r.width), opt.reps)
+        band = hicmap.device_band(A, r.width)
         values_ms = timed(lambda: pileup.value_band(band, A.vc, vc, ex, r), opt.reps)
         vb = pileup.value_band(band, A.vc, vc, ex, r)
         g = torch.zeros_like(ci) if group is None else group
@@ -108,7 +108,7 @@ def main():
               "P2M": round(float(s["P2M"][0]), 4)}
         if not opt.no_host:
             host = A.to_host()
-            hband = loops.band_host(host, r.width)
+            hband = hicmap.band_host(host, r.width)
             nv, exh = vc.cpu().numpy(), ex.cpu().numpy()
             hvb, t_vb = host_ms(lambda: pileup.value_band_host(hband, np.asarray(host.sum(axis=1)).ravel(), nv, exh, r))
             hci, hcj, hg = ci.cpu().numpy(), cj.cpu().numpy(), None if group is None else group.cpu().numpy()
