@@ -30,6 +30,8 @@ from .loops import (Loops, chunk_boundaries, enriched_pixels, enriched_pixels_ho
 from .pileup import (Pileup, PileupRule, apa_scores, centres_of_graph, distance_groups, pileup_host,  # noqa: F401
                      pileup_of_matrix, pileup_rule, pileup_sums, pileup_sums_host, quantile_groups, shifted_centres,
                      value_band, value_band_host)
+from .mapcompare import (MapComparison, SccRule, graph_edge_overlap, map_scc, map_scc_host, scc_from_sums,  # noqa: F401
+                         scc_rule, smooth_strata, smooth_strata_host, stratum_sums, stratum_sums_host)
 from .labelstats import LabelStats, label_stats, label_stats_host, label_stats_split  # noqa: F401
 from .nullgraph import (NullGraphTest, null_chrom_graph, null_graph, null_graph_host, null_graph_test,  # noqa: F401
                         null_statistics)
@@ -63,4 +65,6 @@ __all__ = ["ChromeGCN", "GraphConvolution", "ChromGraph", "HostCSR", "normalize_
            "enriched_pixels_host", "loops_host", "device_band", "loop_histograms", "enriched_pixels", "loops_of_matrix",
            "same_loop_host", "loop_edge_share", "Pileup", "PileupRule", "pileup_rule", "apa_scores", "value_band_host",
            "pileup_sums_host", "pileup_host", "value_band", "pileup_sums", "pileup_of_matrix", "centres_of_graph",
-           "shifted_centres", "distance_groups", "quantile_groups"]
+           "shifted_centres", "distance_groups", "quantile_groups", "MapComparison", "SccRule", "scc_rule", "scc_from_sums",
+           "smooth_strata_host", "stratum_sums_host", "map_scc_host", "smooth_strata", "stratum_sums", "map_scc",
+           "graph_edge_overlap"]

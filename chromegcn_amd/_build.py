@@ -24,7 +24,8 @@ SRC = [os.path.join(PKG, "csrc", "cgcn_kernels.hip"), os.path.join(PKG, "csrc", 
        os.path.join(PKG, "csrc", "cgcn_labelstats.hip"), os.path.join(PKG, "csrc", "cgcn_effects.hip"),
        os.path.join(PKG, "csrc", "cgcn_nullgraph.hip"), os.path.join(PKG, "csrc", "cgcn_bootstrap.hip"),
        os.path.join(PKG, "csrc", "cgcn_insulation.hip"), os.path.join(PKG, "csrc", "cgcn_compartment.hip"),
-       os.path.join(PKG, "csrc", "cgcn_loops.hip"), os.path.join(PKG, "csrc", "cgcn_pileup.hip")]
+       os.path.join(PKG, "csrc", "cgcn_loops.hip"), os.path.join(PKG, "csrc", "cgcn_pileup.hip"),
+       os.path.join(PKG, "csrc", "cgcn_mapcompare.hip")]
 HDR = [os.path.join(ROOT, "include", "chromegcn.h"), os.path.join(PKG, "csrc", "cgcn_common.hpp"),
        os.path.join(PKG, "csrc", "cgcn_compact.hpp"), os.path.join(PKG, "csrc", "cgcn_hicmap.hpp")]
 LIB = os.path.join(PKG, "libchromegcn_hip.so")

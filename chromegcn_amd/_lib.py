@@ -176,6 +176,9 @@ _HEADER = {
     "cgcn_pileup_slices": (_c_int, "stream n:i width:i vband w:i n_slices:ll slice_off n_centres:ll ci cj workspace "
                                    "workspace_bytes:z"),
     "cgcn_pileup_fold": (_c_int, "stream n_groups:i w:i n_slices:ll group_off workspace workspace_bytes:z P N"),
+    "cgcn_mapcmp_smooth": (_c_int, "stream n:i D:i h:i width:i band norm n_norm:ll ld:i S"),
+    "cgcn_mapcmp_workspace_bytes": (_c_sz, "n:i D:i"),
+    "cgcn_mapcmp_sums": (_c_int, "stream n:i D:i ld:i Sa Sb valid min_dist:i pass_no:i workspace workspace_bytes:z cells stats"),
 }
 _ABI = {fn: (res, tuple((p.partition(":")[0], _TYPES[p.partition(":")[2]] if ":" in p else _c_vp) for p in spec.split()))
         for fn, (res, spec) in _HEADER.items()}   # name: (restype, ((parameter name, ctypes type), ...))

@@ -65,7 +65,10 @@ from ALL records; the kept records stay in file order; with domains both tests m
 for bit.
 
 Pile-ups (chromegcn_amd/pileup.py holds the rule).  HicContacts.pileup sums the map in a window around
-every centre of a list (loops, graph edges, their shifted controls), per group; it reads the records and changes no graph."""
+every centre of a list (loops, graph edges, their shifted controls), per group; it reads the records and changes no graph.
+
+Two maps compared (chromegcn_amd/mapcompare.py holds the rule).  HicContacts.scc is the stratum-adjusted
+correlation coefficient of this object's map and another's; it reads the records of both and changes no graph."""
 from __future__ import annotations
 
 from typing import Dict, NamedTuple, Optional
@@ -633,6 +636,32 @@ class HicContacts:
                 self._pileup_values[key] = vb
         return PU.pileup_sums(vb, ci, cj, group, G, r)
 
+    def scc(self, other: "HicContacts", norm=None, resolution_bp=40000, h=5, max_distance_bp=5_000_000, min_dist=1, n_bins=None,
+            norm_args=None):
+        """The stratum-adjusted correlation coefficient of this map and `other` (chromegcn_amd/mapcompare.py's rule), a
+        MapComparison.  Both are binned at resolution_bp with n_bins = the larger of the two unless n_bins says it.  norm: None
+        (the observed counts), 'KR' / 'VC' / 'SQRTVC' (each map's vector from its own records, norm_vector with norm_args), a
+        vector for both, or a pair with one entry per map.  h: the box half-width, or a sequence of them: a list with one
+        result per value, the bands and the validity bytes formed once.  One read-back of the sums per h (and one of the
+        validity bytes)."""
+        from . import mapcompare as MC
+        many = isinstance(h, (tuple, list, np.ndarray))
+        hs = [int(v) for v in h] if many else [int(h)]
+        for v in hs:
+            MC.scc_rule(resolution_bp, 0, v, max_distance_bp, min_dist)
+        res = int(MC.scc_rule(resolution_bp, 0, 0, max_distance_bp, min_dist).res)
+        if n_bins is None:
+            n = max(self.contact_matrix(res).n, other.contact_matrix(res).n)
+        else:
+            n = int(n_bins)
+        rules = [MC.scc_rule(res, n, v, max_distance_bp, min_dist) for v in hs]   # the size guard, before anything is allocated
+        a, b = self.contact_matrix(res, n), other.contact_matrix(res, n)
+        norm_a, norm_b = MC.norm_pair(norm)
+        nva, _ = self._map_vectors(a, norm_a, res, norm_args)
+        nvb, _ = other._map_vectors(b, norm_b, res, norm_args)
+        out = MC.scc_of_matrices(a, b, nva, nvb, rules)
+        return out if many else out[0]
+
     def within_loops(self, loops, pad_bins=1) -> "HicContacts":
         """the records whose pixel lies in some loop's footprint (loops.py's rule 12), in file order, as a HicContacts of their
         own: a sorted int64 key table, torch.searchsorted, boolean indexing -- one host sync for the size"""
@@ -851,7 +880,8 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                                domain_report: Optional[dict] = None, compartments: Optional[dict] = None,
                                compartment_report: Optional[dict] = None, loops: Optional[dict] = None,
                                loop_report: Optional[dict] = None, apa: Optional[dict] = None,
-                               apa_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
+                               apa_report: Optional[dict] = None, compare: Optional[dict] = None,
+                               compare_report: Optional[dict] = None) -> Dict[str, G.ChromGraph]:
     """{chrom: ChromGraph} from `<root>/<chrom>.cghic` (save_contacts_cache, with the chromosome's windows) for the edge
     budget `hicsize` and the norm vector named `hicnorm` ('' = none): what `chromegcn_amd.train -hic_contacts` loads
     instead of `{split}_graphs_{hicsize}_{hicnorm}norm.pkl`.  sizes: the expected window count per chromosome.  window_bp
@@ -874,7 +904,11 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
     that receives {chrom: (Loops, entries in a footprint, nnz)} of the UNRESTRICTED top-K matrix (loops.loop_edge_share).
     apa (`-hic_apa`): a dict of HicContacts.pileup's keywords; apa_report: a dict that receives {chrom: {"edges", "control"[,
     "loops"]: Pileup}}: the pile-up around the edges of the UNRESTRICTED top-K matrix (pileup.centres_of_graph), around the
-    same edges shifted by 3 w bins along the diagonal and, with `loops`, around the loops.  No graph depends on it."""
+    same edges shifted by 3 w bins along the diagonal and, with `loops`, around the loops.  No graph depends on it.
+    compare (`-hic_compare`): a dict of HicContacts.scc's keywords plus `root`, a second cache directory; compare_report: a dict
+    that receives {chrom: (MapComparison of this cache's records and `<compare root>/<chrom>.cghic`'s, mapcompare.
+    graph_edge_overlap of the two UNRESTRICTED top-K matrices, the second one built from the second cache's records, windows and
+    `hicnorm` vector with the same budget and distance rule)}.  No graph depends on it."""
     from . import hicnorm as HN
     from . import nullgraph
     out = {}
@@ -947,6 +981,28 @@ def graphs_from_contact_caches(root: str, chroms, hicsize, hicnorm: str, adj_typ
                 piles["loops"] = rec[0].pileup(called, **kw)
             if apa_report is not None:
                 apa_report[chrom] = piles
+        if compare is not None:
+            from . import mapcompare as MC
+            kw = dict(compare)
+            c2 = load_contacts_cache(contact_cache_path(kw.pop("root"), chrom))
+            if c2.window_start is None:
+                raise ValueError("%s holds no window list" % contact_cache_path(compare["root"], chrom))
+            if hicnorm and hicnorm not in c2.norms and not (bool(compute_norm) and hicnorm in HN.KINDS):
+                raise ValueError("%s holds no %r norm vector (has: %s)" % (contact_cache_path(compare["root"], chrom), hicnorm,
+                                                                           ", ".join(sorted(c2.norms)) or "none"))
+            if not isinstance(rec[0], HicContacts):
+                rec = (HicContacts(c.pos1, c.pos2, c.count, device), None, None)
+            other = HicContacts(c2.pos1, c2.pos2, c2.count, device)
+            up2 = {"window_bp": int(window_bp)} if window_bp is not None and c2.resolution_bp > int(window_bp) else {}
+            ga = rec[0].build_raw(norm, c.resolution_bp, c.window_start, int(hicsize), min_distance_bp=min_distance_bp,
+                                  expected=ex, expected_args=expected_args, **up)
+            gb = other.build_raw(c2.norms[hicnorm] if hicnorm in c2.norms else (hicnorm or None), c2.resolution_bp,
+                                 c2.window_start, int(hicsize), min_distance_bp=min_distance_bp,
+                                 expected=c2.norms.get(expected, expected) if isinstance(expected, str) else expected,
+                                 expected_args=expected_args, **up2)
+            pair = (rec[0].scc(other, **kw), MC.graph_edge_overlap(ga[:2], gb[:2]))
+            if compare_report is not None:
+                compare_report[chrom] = pair
         out[chrom] = build_hic_graph(*rec, norm, c.resolution_bp,
                                      c.window_start, int(hicsize), adj_type=adj_type, device=device,
                                      min_distance_bp=min_distance_bp, expected=ex, expected_args=expected_args,

@@ -18,7 +18,9 @@ iteration's record and the AA / BB / AB share of the graph the run trains on, an
 every chromosome's chromatin loops from its cache's records (chromegcn_amd/loops.py) and prints the loop count and the share of the
 unrestricted graph inside loop footprints; `-hic_loop_restrict` trains on the graphs of the contacts inside the footprints.
 `-hic_apa W` (with `-hic_contacts`) prints the aggregate peak analysis (chromegcn_amd/pileup.py) of the unrestricted graph's edges,
-of their shifted control and, with `-hic_loops`, of the loops; it changes no graph."""
+of their shifted control and, with `-hic_loops`, of the loops; it changes no graph.  `-hic_compare DIR2` (with `-hic_contacts`) prints,
+per chromosome, the stratum-adjusted correlation coefficient (chromegcn_amd/mapcompare.py) of the run's contact map and the map of
+`DIR2/<chrom>.cghic`, and the overlap of the two unrestricted graphs' edges; it changes no graph either."""
 from __future__ import annotations
 
 import argparse
@@ -83,6 +85,14 @@ def parse(argv=None):
                          "edges of every chromosome's unrestricted graph, around the same edges shifted by 3 W bins and, with "
                          "-hic_loops, around the loops; prints P2LL, P2M and ZscoreLL of each.  0: off")
     ap.add_argument("-hic_apa_res", type=int, default=10000, metavar="BP", help="-hic_apa: the bin size of the piled-up map")
+    ap.add_argument("-hic_compare", type=str, default=None, metavar="DIR2",
+                    help="-hic_contacts: compare every chromosome's contact map with DIR2/<chrom>.cghic (chromegcn_amd.mapcompare); "
+                         "prints the stratum-adjusted correlation coefficient of the two maps and the overlap of the two "
+                         "unrestricted graphs' edges")
+    ap.add_argument("-hic_compare_res", type=int, default=40000, metavar="BP", help="-hic_compare: the bin size of the compared maps")
+    ap.add_argument("-hic_compare_h", type=int, default=5, metavar="H", help="-hic_compare: the smoothing half-width, 0 to 20 bins")
+    ap.add_argument("-hic_compare_norm", type=str, default="NONE", choices=["KR", "VC", "SQRTVC", "NONE"],
+                    help="-hic_compare: the balancing of the compared maps (NONE: the observed counts)")
     ap.add_argument("-hic_null", type=str, default=None, choices=["distance", "degree", "uniform"],
                     help="the control the reference's `-adj_type random` advertises: every Hi-C matrix of every split is replaced "
                          "by its null graph (chromegcn_amd.nullgraph) before it is normalised by -adj_type hic / both")
@@ -123,7 +133,21 @@ def parse(argv=None):
             ap.error("-hic_apa: the window half-width is 1 to 10 bins")
         if opt.hic_apa_res < 1:
             ap.error("-hic_apa_res must be positive")
+    if opt.hic_compare:
+        if not opt.hic_contacts:
+            ap.error("-hic_compare needs -hic_contacts: the comparison reads the contact records of both directories")
+        if not 0 <= opt.hic_compare_h <= 20:
+            ap.error("-hic_compare_h: the smoothing half-width is 0 to 20 bins")
+        if opt.hic_compare_res < 1:
+            ap.error("-hic_compare_res must be positive")
     return opt
+
+
+def report_compare(split, report, out=None):
+    """-hic_compare: one line per chromosome of graphs_from_contact_caches' compare_report"""
+    for c, (cmp, ov) in report.items():
+        print("[hic_compare] %s %s: SCC %.4f, N strata %d, edges shared/only/only %d/%d/%d, Jaccard %.4f"
+              % (split, c, cmp.scc, cmp.n_strata, ov["shared"], ov["only_a"], ov["only_b"], ov["jaccard"]), file=out)
 
 
 def report_apa(split, report, out=None):
@@ -216,6 +240,10 @@ def _load_inputs(opt):
             apa = {}
             if getattr(opt, "hic_apa", 0):
                 apa = dict(apa=dict(w=opt.hic_apa, resolution_bp=opt.hic_apa_res), apa_report={})
+            if getattr(opt, "hic_compare", None):
+                apa.update(compare=dict(root=opt.hic_compare, resolution_bp=opt.hic_compare_res, h=opt.hic_compare_h,
+                                        norm=None if opt.hic_compare_norm == "NONE" else opt.hic_compare_norm),
+                           compare_report={})
             graphs[sp] = hic.graphs_from_contact_caches(opt.hic_contacts, list(data[sp]), opt.hicsize, opt.hicnorm, opt.adj_type,
                                                         torch.device("cuda", opt.gpu_id),
                                                         {c: f["forward"].shape[0] for c, f in data[sp].items()},
@@ -230,6 +258,7 @@ def _load_inputs(opt):
                                                         loops=loops, loop_report=loop_report, **apa)
             report_compartments(opt, sp, comp_report)
             report_apa(sp, apa.get("apa_report", {}))
+            report_compare(sp, apa.get("compare_report", {}))
             for c, (called, inside, nnz) in loop_report.items():
                 print("[hic_loops] %s %s: %d loops from %d candidates (%d enriched pixels, %d after the ratios); %d of %d entries of the "
                       "unrestricted graph inside a footprint (%.1f %%)"

@@ -1419,6 +1419,39 @@ int cgcn_pileup_slices(cgcn_stream_t stream, int n, int width, const double *vba
 int cgcn_pileup_fold(cgcn_stream_t stream, int n_groups, int w, long long n_slices, const int32_t *group_off,
                      const void *workspace, size_t workspace_bytes, double *P, long long *N);
 
+/* ---- Two maps compared: the stratum-adjusted correlation coefficient (chromegcn_amd/mapcompare.py holds the rule; DESIGN.md
+ * section 4.22).  These three functions are additions to ABI 26 like the functions above: CGCN_ABI_VERSION stays 26, nothing
+ * above changes.
+ *
+ * band fp64 [n][width] is cgcn_hicloops_band's raw band, width >= D + 2 h + 1; h <= 20 is the box half-width; D the largest
+ * distance; ld >= n the leading dimension of the strata (the Python layer rounds n up to even).  n width and (D + 1) (ld + 1)
+ * must not exceed 2^28: CGCN_ERR_UNSUPPORTED beyond these limits.
+ *
+ * cgcn_mapcmp_smooth: S fp64 [D + 1][ld], every entry written: S[d][i] = sum over da = -h .. h of R_da, R_da = sum over
+ *   db = -h .. h of V(i + da, i + d + db), both plain sequential fp64 sums from 0.0 in ascending order.  V(p, q) is the value
+ *   of the cell (min(p, q), max(p, q)), band / (nv[p] * nv[q]) with a norm vector (NaN, 0 and the bins beyond n_norm read as
+ *   +inf) and band itself with norm NULL; 0 where p or q is outside [0, n).  S[d][i] = 0 where i + d >= n.
+ * cgcn_mapcmp_sums: the sums per stratum d = 0 .. D of the cells (i, i + d) with valid[i] and valid[i + d] (uint8 [n], device)
+ *   and Sa[d][i] != 0 or Sb[d][i] != 0; no cell of a stratum below min_dist takes part.  The rows 0 .. n - d - 1 are cut into
+ *   chunks of 2048; lane l of 64 adds the rows c0 + l, c0 + l + 64, ... of its chunk in ascending order from 0.0, the lanes
+ *   are added by the xor butterfly 32 .. 1, and the chunks' sums are added in chunk order from 0.0.  pass_no = 1 writes
+ *   cells int64 [D + 1] and the rows 0 .. 3 of stats fp64 [7][D + 1]: sum x, sum y, sum x / cells, sum y / cells.  pass_no = 2
+ *   reads the rows 2 and 3 as the means and writes the rows 4 .. 6: sum (x - mx)^2, sum (y - my)^2, sum (x - mx)(y - my), every
+ *   difference, product and sum rounded on its own.  The partial sums live in the workspace.
+ *
+ * No atomics and a fixed order: the same bits in every run.  Enqueue only: no allocation, no synchronisation.
+ * CGCN_ERR_BAD_ARG: a NULL pointer that would be read or written, a negative size, width < D + 2 h + 1, ld < n, a pass_no that is
+ * neither 1 nor 2, norm with n_norm < 1; CGCN_ERR_WORKSPACE: workspace_bytes below cgcn_mapcmp_workspace_bytes (0 for an
+ * unsupported shape).
+ */
+int cgcn_mapcmp_smooth(cgcn_stream_t stream, int n, int D, int h, int width, const double *band, const double *norm,
+                       long long n_norm, int ld, double *S);
+
+size_t cgcn_mapcmp_workspace_bytes(int n, int D);
+
+int cgcn_mapcmp_sums(cgcn_stream_t stream, int n, int D, int ld, const double *Sa, const double *Sb, const uint8_t *valid,
+                     int min_dist, int pass_no, void *workspace, size_t workspace_bytes, long long *cells, double *stats);
+
 #ifdef __cplusplus
 }
 #endif
